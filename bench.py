@@ -2,17 +2,28 @@
 """bench.py -- pivots/sec + arcs-priced/sec of the MI355X network-simplex engine.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--rule R] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
 
 A *step* is one pivot: one pass of the hot path (pricing sweep -> ratio test / flow update
 -> tree + potential update) over the device-resident instance.  W untimed pivots, then
 EXACTLY K timed pivots between barrier + device synchronisation on both sides; rank 0 prints
 ONE JSON line.  Inputs are resident in HBM before the timed region starts.
 
+A plain run measures the headline only: set-up, warm-up, the K timed pivots, the line.  The
+secondary measurements below (the profiled kernel-per-phase pass, the larger and other config
+points, the batched points, the CPU baseline) run only with ``--full``.
+
+``--dump-outputs DIR`` (one GPU): after the timed pivots, what a caller of the solve path would
+receive for the basis the last timed pivot left -- flow per arc, potential per node, tree
+membership per arc, objective -- as DIR/<name>.npy (float64; in_tree float32).  The instance is
+seeded, so the same arguments give the same inputs on every run.  Arrays longer than 2 M entries
+are written as a fixed seeded sample of their entries (<= 40 MB in all).
+
 Workload at N=1 (default): BASELINE.json configs[1] -- "netgen_8_08a, 1xMI355X, full-scan
 Dantzig pricing kernel" -- as a seeded synthetic stand-in (the LEMON file is not obtainable
 offline).  That instance is 27 KB per sweep: it runs as ONE persistent LDS-resident workgroup
 (k_solve_small) and is latency-bound by construction, which is what its `roofline` object says.
-The same line therefore also carries
+With ``--full`` the same line also carries
   * ``hbm_point``: configs[4]'s shape (1 M nodes / 16 M arcs), where the pricing sweep (k_price_v) is the dominant,
     bandwidth-bound kernel -- its 67 MB working set fits the 256 MiB Infinity Cache;
   * ``hbm_point_beyond_infinity_cache``: 6 M nodes / 96 M arcs (403 MB of key codes per sweep), where the same
@@ -130,10 +141,12 @@ def pmc_traffic(workload: str, kernel: str):
     return None, None
 
 
-def measure_single(workload: str, steps: int, warmup: int, rule: int, profile_pass: bool = True, full_sweeps: int = 1) -> dict:
+def measure_single(workload: str, steps: int, warmup: int, rule: int, profile_pass: bool = True, full_sweeps: int = 1,
+                   outputs: dict | None = None) -> dict:
     """full_sweeps=1: every Dantzig / candidate-list sweep prices every arc (BASELINE.json's "full-scan" configs and
     the roofline measurement); 0: the engine's default, which from 4 M arcs on skips pricing workgroups whose arcs have
-    not changed since they last swept them (same entering arcs, fewer bytes)."""
+    not changed since they last swept them (same entering arcs, fewer bytes).  ``outputs``: filled with the engine's
+    result after the timed pivots (read outside the timed region)."""
     import torch
 
     from network_flow_solver_amd import engine
@@ -149,6 +162,8 @@ def measure_single(workload: str, steps: int, warmup: int, rule: int, profile_pa
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     s1 = eng.stats()
+    if outputs is not None:
+        outputs["result"] = eng.result()
     mode = int(s1.get("pricing_mode", 0))
     pivots = s1["pivots"] - s0["pivots"] if restarts == 0 else steps
     arcs = s1["arcs_priced"] - s0["arcs_priced"] if restarts == 0 else steps * inst.m
@@ -370,6 +385,27 @@ def batched_point(rule: int, instances: int = 1024, nodes: int = 256, arcs: int 
             "note": "wall = host call incl. job upload and control-block read-back; handles created beforehand (instances resident in HBM)"}
 
 
+DUMP_MAX_ENTRIES = 2_000_000     # per array: flow + potential (float64) + in_tree (float32) stay under 40 MB
+
+
+def dump_outputs(out_dir: str, res) -> None:
+    """The engine's result after the last timed pivot as DIR/<name>.npy.  An array longer than DUMP_MAX_ENTRIES is
+    written as the entries at a fixed seeded set of indices (the same on every run for the same arguments)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+
+    def sample(a: np.ndarray) -> np.ndarray:
+        if a.shape[0] <= DUMP_MAX_ENTRIES:
+            return a
+        idx = np.unique(np.random.default_rng(20240601).integers(0, a.shape[0], size=DUMP_MAX_ENTRIES))
+        return a[idx]
+
+    np.save(out / "flow.npy", sample(res.flow).astype(np.float64))
+    np.save(out / "potential.npy", sample(res.potential).astype(np.float64))
+    np.save(out / "in_tree.npy", sample(res.in_tree).astype(np.float32))
+    np.save(out / "objective.npy", np.array([float(res.objective)], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -379,8 +415,13 @@ def main():
     ap.add_argument("--rule", default="dantzig", choices=["dantzig", "devex", "candidate_list"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = arcs per GPU fixed (the instance grows with N); strong = the BASELINE instance fixed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-hbm-point", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: profiled kernel pass, larger and other config points, "
+                         "batched points, CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-hbm-point", action="store_true", help="with --full: skip the larger and other config points")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pivot left (flow, potential, in_tree, objective) as DIR/<name>.npy")
     args = ap.parse_args()
     rule = {"dantzig": 0, "devex": 1, "candidate_list": 2}[args.rule]
 
@@ -388,8 +429,11 @@ def main():
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
     if args.gpus > 1 or world > 1 or os.environ.get("MCF_BENCH_FORCE_DIST") == "1":  # env: rehearse the sharded path on 1 GPU
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs is supported on the single-GPU path only")
         from network_flow_solver_amd import distributed
 
+        args.no_hbm_point = args.no_hbm_point or not args.full   # the sharded line's secondary points: --full only
         distributed.bench_main(args, WORKLOADS, HBM_PEAK_GBPS)
         return
 
@@ -397,7 +441,10 @@ def main():
 
     ge.build_hip()
     workload = args.workload or "netgen_8_08a"
-    head = measure_single(workload, args.steps, args.warmup, rule)
+    outputs = {} if args.dump_outputs else None
+    head = measure_single(workload, args.steps, args.warmup, rule, profile_pass=args.full, outputs=outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs["result"])
     line = {
         "metric": "pivots/sec + arcs-priced/sec (value = arcs-priced/sec; pivots_per_sec alongside) on netgen_8-style DIMACS",
         "value": head["arcs_priced_per_sec"], "unit": "arcs/s", "pivots_per_sec": head["pivots_per_sec"],
@@ -412,7 +459,7 @@ def main():
         "reference_published": {"pivots_per_sec": 52, "instance": "netgen_8_08a (real file)", "hardware": "unstated CPU",
                                 "source": "benchmarks/results/after-iteration-fix.json:89-98"},
     }
-    default_run = not args.no_hbm_point and workload == "netgen_8_08a"
+    default_run = args.full and not args.no_hbm_point and workload == "netgen_8_08a"
     if default_run:
         big = measure_single("netgen_1m_16m", min(args.steps, 200), min(args.warmup, 20), rule)
         line["hbm_point"] = {
@@ -461,7 +508,7 @@ def main():
             line["batched_point_netgen_8_12a"] = batched_point(1, instances=256, nodes=4096, arcs=32768, label="netgen_8_12a")
         except Exception as exc:  # noqa: BLE001
             line["batched_point_error"] = f"{type(exc).__name__}: {exc}"
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(workload)
         if "hbm_point" in line:
             line["hbm_point"]["cpu_baseline"] = cpu_baseline("netgen_1m_16m", budget_seconds=10.0)

@@ -8,13 +8,13 @@ mkdir -p $O
 cd $R
 PART=${PART:-ABC}   # A: bench lines + rocprofv3 kernel summaries, B: PMC passes + solve times, C: stamps + windowed profile (one gpurun call each)
 case $PART in *A*)
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench default exit=$?"
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-hbm-point > $O/bench_default_20steps.json 2> $O/bench_20.err; echo "bench 20 steps exit=$?"
-timeout -k 10 300 python bench.py --workload netgen_1m_16m --no-hbm-point > $O/bench_netgen_1m_16m.json 2> $O/bench_1m.err; echo "bench 1m exit=$?"
-timeout -k 10 500 python bench.py --workload netgen_6m_96m --steps 100 --warmup 10 --no-cpu-baseline --no-hbm-point > $O/bench_netgen_6m_96m.json 2> $O/bench_4m.err; echo "bench 4m exit=$?"
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench default exit=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-hbm-point > $O/bench_default_20steps.json 2> $O/bench_20.err; echo "bench 20 steps exit=$?"
+timeout -k 10 300 python bench.py --full --workload netgen_1m_16m --no-hbm-point > $O/bench_netgen_1m_16m.json 2> $O/bench_1m.err; echo "bench 1m exit=$?"
+timeout -k 10 500 python bench.py --full --workload netgen_6m_96m --steps 100 --warmup 10 --no-cpu-baseline --no-hbm-point > $O/bench_netgen_6m_96m.json 2> $O/bench_4m.err; echo "bench 4m exit=$?"
 cd /tmp && export TMPDIR=/tmp
 for tag in default netgen_1m_16m netgen_6m_96m; do
-  args="--no-cpu-baseline --no-hbm-point"
+  args="--full --no-cpu-baseline --no-hbm-point"
   [ $tag = netgen_1m_16m ] && args="$args --workload netgen_1m_16m"
   [ $tag = netgen_6m_96m ] && args="$args --workload netgen_6m_96m --steps 100 --warmup 10"
   MCF_USE_GRAPH=0 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag -o run -- python3 $R/bench.py $args > $O/prof_${tag}_bench.json 2> $O/prof_$tag.err
