@@ -193,10 +193,33 @@ typedef int (*mcf_progress_cb)(void* user, int64_t pivots, int64_t max_pivots, d
 /* Fill *opt with defaults. */
 void mcf_default_options(mcf_options* opt);
 
+/* ---- Numeric domain.  Everything is exact integer arithmetic; mcf_create checks what follows on the host, before
+ * anything reaches a device, and refuses an instance outside it with MCF_E_RANGE and a message (mcf_last_error(NULL)).
+ *   sizes       n >= 1, m >= 0, m + n < 2^30.
+ *   costs       |cost| <= INT32_MAX = 2^31 - 1 (negative and zero costs included; -2^31 is refused), and
+ *               big-M = (max|cost| + 1) * (n + 2) < 2^44: the cost of an artificial arc, above any simple path's cost.
+ *               INT32_MAX is therefore admissible up to n = 8 189.  Potentials (+-big-M plus the cost of a tree path) stay below
+ *               2 * big-M < 2^45 in magnitude and reduced costs below 4 * big-M < 2^46, which is what leaves bit 61 free for the key variants and lets the Devex
+ *               merit rc^2 / w be formed in double precision (convert, multiply, divide; never contracted).
+ *   capacities  int64.  0 <= cap < 2^60 is a bound and is honoured exactly (2^60 - 1 included); cap < 0 (MCF_CAP_INF)
+ *               or cap >= 2^60 means uncapacitated.  2^60 is also the ratio test's "no bound": a pivot whose cycle has
+ *               no bound at all ends the solve as MCF_ST_UNBOUNDED.
+ *   supplies    int64, summed in 128 bits: sum(supply) must be 0, and the sum of the POSITIVE supplies must stay below
+ *               2^60.  That sum bounds the flow of every artificial arc at every pivot (a pivot cycle passes the root
+ *               through one artificial arc in each sense, so their total never grows beyond the start basis'), and an
+ *               artificial arc at 2^60 would read as unbounded.  The limit is 2^60 itself, not something tighter: below
+ *               it every residual the ratio test compares is < 2^60, and flow + residual < 2^61 cannot overflow.
+ *   flows       a capped arc never carries more than its capacity.  An UNCAPACITATED arc on a negative-cost cycle
+ *               closed by capped arcs carries up to the sum of those capacities: keeping that below 2^60 is the
+ *               caller's part (it cannot be checked without solving).
+ *   objective   sum(flow * cost) as an exact 128-bit integer, handed over as two 64-bit halves (mcf_get_result);
+ *               |objective| < m * 2^60 * 2^31 < 2^121. */
+
 /* Build the device-resident problem: arc SoA, potentials, preorder spanning tree with the
  * all-artificial start basis.  n = real nodes (ids 0..n-1), m = arcs, lower bounds already
- * shifted out.  cap[i] < 0 or >= 2^60 means uncapacitated.  sum(supply) must be 0.
- * |cost| must fit int32 and m + n must stay below 2^30. */
+ * shifted out.  cap[i] < 0 or >= 2^60 means uncapacitated.  sum(supply) must be 0 and the positive
+ * supplies must add up to less than 2^60.  |cost| must fit int32 (and big-M stay below 2^44, see
+ * "Numeric domain" above) and m + n must stay below 2^30; outside: MCF_E_RANGE. */
 int mcf_create(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, const int64_t* cost,
                const int64_t* cap, const int64_t* supply, const mcf_options* opt, mcf_handle** out);
 

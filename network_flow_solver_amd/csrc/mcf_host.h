@@ -211,13 +211,21 @@ inline std::string mcf_apply_basis(McfHostImage& im, const int8_t* in_tree, cons
                 int32_t& b = best[find(v)];
                 if (b < 0 || viol[v] < viol[b] || (viol[v] == viol[b] && v < b)) b = v;
             }
+            // Only a component whose artificial arc carries NO flow may move: the flows the counts were taken from are those
+            // of the current hanging node, and moving it shifts every flow on the path between the two nodes by the component's
+            // balance (a supply change since the basis was taken leaves such a balance).  A component with a balance stays
+            // where it is and goes through the repair below.
+            const std::vector<int8_t> rep0(rep);
             bool moved = false;
             for (int32_t v = 0; v < n; ++v) {
-                if (!rep[v]) continue;
+                if (!rep0[v] || art_flow[v] != 0) continue;
                 const int32_t b = best[find(v)];
                 if (b != v && viol[b] < viol[v]) { rep[v] = 0; rep[b] = 1; moved = true; }
             }
-            if (moved && (!dfs() || !flows_ok())) return "internal: re-hanging a basis component failed";
+            if (moved && (!dfs() || !flows_ok())) {   // never expected; the basis itself was fine: back to where it hung
+                rep = rep0;
+                if (!dfs() || !flows_ok()) return "internal: re-hanging a basis component failed";
+            }
         }
     }
     // --- strong feasibility: drop wrong-way degenerate basic arcs, re-hang their subtrees on the root
@@ -311,9 +319,15 @@ inline std::string mcf_build_image(int32_t n, int64_t m, const int32_t* tail, co
     im.arcw.assign(m + n, McfArcW{0, 0});
     im.supply.assign(supply, supply + n);
 
-    int64_t max_abs_cost = 0, total = 0;
-    for (int32_t v = 0; v < n; ++v) total += supply[v];
+    // Supplies: summed in 128 bits (n values of up to 63 bits), and the sum of the positive ones -- the bound on the flow
+    // of any single artificial arc, see "Numeric domain" in include/mcf.h -- has to stay below MCF_INF, which the ratio
+    // test reads as "no bound": an artificial arc carrying 2^60 would look uncapacitated in both directions and the
+    // solve would end as "unbounded".
+    int64_t max_abs_cost = 0;
+    __int128 total = 0, positive = 0;
+    for (int32_t v = 0; v < n; ++v) { total += supply[v]; if (supply[v] > 0) positive += supply[v]; }
     if (total != 0) return "supplies do not balance";
+    if (positive >= (__int128)MCF_INF) { *err_code = -5; return "the sum of the positive supplies must stay below 2^60"; }
     for (int64_t i = 0; i < m; ++i) {
         if (tail[i] < 0 || tail[i] >= n || head[i] < 0 || head[i] >= n) return "arc end point out of range";
         if (tail[i] == head[i]) return "self-loop";

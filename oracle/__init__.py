@@ -465,6 +465,40 @@ def emul_solve(n, tail, head, cost, cap, supply, rule: int = 0, block_size: int 
     }
 
 
+def emul_vkey(viol: int, bigm: int, half: int) -> int:
+    """csrc/mcf_core.h:mcf_vkey itself (the compressed Dantzig key of a violation)."""
+    lib = _load_emul()
+    lib.emul_vkey.restype = ctypes.c_int32
+    lib.emul_vkey.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]
+    return int(lib.emul_vkey(int(viol), int(bigm), int(half)))
+
+
+def emul_vkey_decode(code: int, bigm: int, half: int) -> int:
+    """csrc/mcf_core.h:mcf_vkey_decode itself."""
+    lib = _load_emul()
+    lib.emul_vkey_decode.restype = ctypes.c_int64
+    lib.emul_vkey_decode.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]
+    return int(lib.emul_vkey_decode(int(code), int(bigm), int(half)))
+
+
+def emul_validate(n, tail, head, cost, cap, supply) -> tuple[int, str, int]:
+    """mcf_build_image alone -- the host-side validation mcf_create runs before anything reaches a device:
+    (0 or the MCF_E_* code, its message, big-M of an accepted instance)."""
+    lib = _load_emul()
+    i32p, i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+    lib.emul_validate.restype = ctypes.c_int32
+    lib.emul_validate.argtypes = [ctypes.c_int32, ctypes.c_int64, i32p, i32p, i64p, i64p, i64p, ctypes.c_char_p,
+                                  ctypes.c_int32, i64p]
+    tail = np.ascontiguousarray(tail, np.int32); head = np.ascontiguousarray(head, np.int32)
+    cost = np.ascontiguousarray(cost, np.int64); cap = np.ascontiguousarray(cap, np.int64)
+    supply = np.ascontiguousarray(supply, np.int64)
+    msg = ctypes.create_string_buffer(256)
+    big_m = ctypes.c_int64(0)
+    rc = lib.emul_validate(int(n), len(tail), _ptr(tail, ctypes.c_int32), _ptr(head, ctypes.c_int32), _ptr(cost, ctypes.c_int64),
+                           _ptr(cap, ctypes.c_int64), _ptr(supply, ctypes.c_int64), msg, 256, ctypes.byref(big_m))
+    return int(rc), msg.value.decode(), int(big_m.value)
+
+
 class EmulStepper:
     """Step-wise handle on the CPU emulation (one replica): price a shard, apply a pivot.
     Mirrors how the HIP engine is driven per pivot in the arc-sharded multi-GPU loop."""

@@ -450,4 +450,20 @@ int64_t emul_check_block_map(int32_t n, int64_t m, const int32_t* tail, const in
     return bad;
 }
 
+// ---- numeric-domain hooks for the tests: the shared header's own functions, not restatements
+int32_t emul_vkey(int64_t viol, int64_t bigm, int32_t half) { return mcf_vkey(viol, bigm, half); }
+int64_t emul_vkey_decode(int32_t code, int64_t bigm, int32_t half) { return mcf_vkey_decode(code, bigm, half); }
+
+// mcf_build_image alone: 0 or the MCF_E_* code mcf_create would return for these arrays, with its message; *big_m (may be
+// null) <- the big-M of an accepted instance
+int32_t emul_validate(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, const int64_t* cost, const int64_t* cap,
+                      const int64_t* supply, char* msg, int32_t msg_len, int64_t* big_m) {
+    McfHostImage im;
+    int err = 0;
+    const std::string text = mcf_build_image(n, m, tail, head, cost, cap, supply, im, &err, true);
+    if (msg && msg_len > 0) { std::strncpy(msg, text.c_str(), (size_t)msg_len - 1); msg[msg_len - 1] = 0; }
+    if (big_m) *big_m = err ? 0 : im.big_m;
+    return err;
+}
+
 }  // extern "C"

@@ -136,8 +136,7 @@ def test_warm_start_after_a_supply_change_reaches_the_cold_optimum():
     cold = oracle.emul_solve(inst.n, inst.tail, inst.head, inst.cost, inst.cap, supply)
     warm = oracle.emul_solve(inst.n, inst.tail, inst.head, inst.cost, inst.cap, supply, warm_in_tree=it, warm_at_upper=au)
     assert warm["status"] == cold["status"] == "optimal" and warm["objective"] == cold["objective"]
-    if warm["warm_applied"]:
-        assert warm["pivots"] < cold["pivots"]
+    assert warm["warm_applied"] and warm["pivots"] < cold["pivots"]
 
 
 def test_warm_start_rejects_cycles_and_empty_bases_then_solves_cold():

@@ -20,6 +20,7 @@ import network_flow_solver_amd as nfs
 from conftest import (CASE_IDS, CASES, check_optimality, check_tree_invariants, golden_flows, load_synthetic,
                       optimum_is_unique)
 from network_flow_solver_amd import generators
+from wide_range_instances import _vkey_code
 
 pytestmark = pytest.mark.gpu
 
@@ -100,19 +101,6 @@ def test_resident_reduced_costs_stay_exact(gpu_engine_module, rule, mid_loop):
     assert res.status == ref.status == "optimal" and res.stats["pivots"] == ref.stats["pivots"]
     assert np.array_equal(res.flow, ref.flow) and np.array_equal(res.potential, ref.potential)
     assert np.array_equal(tree["order"], rtree["order"]) and res.stats["arcs_priced"] == ref.stats["arcs_priced"]
-
-
-def _vkey_code(viol: np.ndarray, bigm: int, half: int) -> np.ndarray:
-    """csrc/mcf_core.h:mcf_vkey in numpy: the compressed Dantzig key of a violation."""
-    SAT = 0x7fffffff
-    viol = viol.astype(np.int64)
-    if bigm < (1 << 29) and half >= (1 << 28):
-        return np.where(viol <= 0, 0, np.where(viol < SAT, viol, SAT)).astype(np.int32)
-    j = np.where(2 * viol < bigm, 0, np.where(2 * viol < 3 * bigm, 1, np.where(2 * viol < 5 * bigm, 2, 3)))
-    d = viol - j * bigm
-    ok = (j < 3) & (d < half) & (d > -half)
-    code = (j.astype(np.int64) << 29) + d + (1 << 28)
-    return np.where(viol <= 0, 0, np.where(ok, code, SAT)).astype(np.int32)
 
 
 @pytest.mark.parametrize("rule", [0, 2], ids=["dantzig", "candidate_list"])

@@ -197,3 +197,20 @@ def test_engine_warm_start_at_scale(gpu_engine_module, name, rule):
         assert r.status == ref["status"] == "optimal" and r.objective == ref["objective"]
         if applied:
             assert r.stats["pivots"] < cold.stats["pivots"] // 2
+
+
+def test_warm_start_keeps_a_basis_whose_component_has_a_balance(gpu_engine_module):
+    """The 3-node case of tests/test_numeric_range_cpu.py through mcf_set_basis: the basis {0 -> 1} is valid for the
+    supplies [5, 0, -5] and must be applied (it used to be rejected by the re-hanging step); one pivot brings 0 -> 2 in."""
+    e = gpu_engine_module
+    tail, head = np.array([0, 0], np.int32), np.array([1, 2], np.int32)
+    cost, cap, supply = np.array([1, 5], np.int64), np.array([3, 10], np.int64), np.array([5, 0, -5], np.int64)
+    for kw in ({}, dict(fused=False, mid_loop=-1), dict(fused=False, mid_loop=1)):
+        with e.McfEngine(3, tail, head, cost, cap, supply, **kw) as eng:
+            assert eng.set_basis([1, 0]), eng.last_error()
+            eng.solve()
+            res = eng.result()
+            assert res.status == "optimal" and res.flow.tolist() == [0, 5] and res.objective == 25 and res.stats["pivots"] == 1
+            assert eng.set_basis(res.in_tree.astype(np.int8))
+            eng.solve()
+            assert eng.result().stats["pivots"] == 0 and eng.result().flow.tolist() == [0, 5]
