@@ -18,6 +18,9 @@
  *   ProgressCallback cadence  simplex.py:1143-1154 ...........................  mcf_progress_cb
  *   UnboundedProblemError(entering_arc, reduced_cost)  exceptions.py:65-93 ...  MCF_ST_UNBOUNDED + stats.unbounded_arc
  *   warm start  simplex.py:740-1010, 1491-1532 ..............................  mcf_set_basis
+ *   solving again after arc costs changed: the reference builds a new NetworkSimplex
+ *       from the edited problem and passes solve(warm_start_basis=...)
+ *       simplex.py:99-265, 1491-1532 .........................................  mcf_update_costs (the resident basis stays)
  *   AdaptiveTuner.adapt_block_size  simplex_adaptive.py:98-151 and the
  *       periodic Devex reset  simplex.py:1370-1400 ..........................  inside mcf_solve (MCF_RULE_DEVEX_BLOCK)
  *   specialised pivot strategies  specialized_pivots.py:69-424, 452-527 .....  mcf_options.key_mode (+ arc_priority): row scan,
@@ -262,6 +265,31 @@ int mcf_reset(mcf_handle* h);
  * empty, flows outside the bounds): the handle is then at the cold start and can be solved as usual -- the
  * reference's fall-back (simplex.py:1527-1531).  Counters are reset either way. */
 int mcf_set_basis(mcf_handle* h, const int8_t* in_tree, const int8_t* at_upper);
+
+/* Re-optimise after arc costs changed: arc[i] (caller's arc index) now costs new_cost[i]; the basis the handle holds stays.
+ * Flows, arc states and the tree do not depend on costs, so that basis stays primal (and strongly) feasible under any cost
+ * vector: only the potentials below a changed tree arc move, and after them the reduced costs and key codes.  All of it is
+ * done on the device, on the arrays that are already there -- no new handle, no upload of the instance, no host walk of the
+ * tree -- and the next mcf_solve simply goes on pivoting from that basis.
+ *   valid      between solves in any state of the handle (fresh, after mcf_reset / mcf_set_basis, after a solve that ended
+ *              with any status), on every engine path, tree layout, rule and key_mode.  Duplicate indices: the LAST entry
+ *              wins (resolved on the host).  Handles with shard_count > 1: MCF_E_STATE.
+ *   errors     MCF_E_BAD_ARG: null handle, count < 0, null arrays with count > 0, an index outside [0, m).  MCF_E_RANGE: a
+ *              cost outside "Numeric domain" above (|cost| > INT32_MAX, or big-M would reach 2^44).  Everything is checked
+ *              before anything changes: after either error the handle is exactly as it was.
+ *   big-M      grows in the same call when a new cost needs it ((max|cost| + 1) * (n + 2), as in mcf_create) -- every
+ *              artificial arc touches the root, so that is a cost change on the tree arc of every root child that still hangs
+ *              on one -- and never shrinks.
+ *   afterwards the handle is what mcf_create with the new costs followed by an installation of this basis would give:
+ *              flows, states, parent / pred_arc / size / pos / order / depth / psize unchanged; the root's potential
+ *              unchanged and pi[child] - pi[parent] = +-cost(pred arc) on every tree arc; resident reduced costs and key
+ *              codes (where the handle keeps them; a handle that dropped them stays dropped) exact for every arc.  The
+ *              solve status is back to "running"; mcf_stats.pivots and the other counters keep counting (mcf_solve(h, k)
+ *              means k MORE pivots).  Everything derived for pricing starts over: the candidate list and its cache are
+ *              emptied, every pricing workgroup of an incremental sweep is due again, the Devex weights are 1.0, the
+ *              block cursor and the block-size tuner are at their start values.  A later mcf_reset / mcf_set_basis and
+ *              the objective of mcf_get_result use the new costs. */
+int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int64_t* new_cost);
 
 /* ---- arc-sharded multi-GPU pivoting: one handle per rank, every rank holds the full
  * replicated state and prices only its shard (options.shard_rank / shard_count).  Per pivot:

@@ -1890,6 +1890,154 @@ __global__ void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
 }
 
+// ------------------------------------------------------------------ mcf_update_costs: re-price a resident basis
+// Flows, states and the tree do not depend on costs, so a cost change on a handle that holds a basis moves only the
+// potentials below a changed TREE arc and, after them, the reduced costs / key codes.  Four kinds of launches, none of
+// which depends on how many arcs changed or (beyond a logarithm) on the depth of the tree:
+//   k_uc_seed     one lane per node: jump record {val = 0 (root children on an artificial arc: +-(growth of big-M)),
+//                 anc = parent}, and the greatest depth of the tree (decides the number of jump rounds);
+//   k_uc_scatter  one lane per changed arc: store cost[e]; a basic arc adds +-delta to the record of the end point it is
+//                 the tree arc of (every node has its own tree arc: plain stores, nothing to resolve);
+//   k_uc_jump     pointer jumping, ceil(log2(max depth)) rounds over double buffers: val[v] += val[anc[v]],
+//                 anc[v] = anc[anc[v]] -- after the last round val[v] is the sum of the deltas on v's root path.  Reads
+//                 parent pointers only, so it serves the dense preorder array and the blocked preorder list alike;
+//                 the last round adds the sum to pi[v] itself;
+//   k_uc_rebuild  one streaming pass over all m_pad arcs in the shape of k_price's gather: rc = cost + pi[tail] - pi[head]
+//                 into rcache (and the key code into vkey), 16-byte accesses throughout.
+struct alignas(16) McfJump {
+    int64_t val;   // sum of the potential shifts of the tree arcs from this node up to (excluding) anc
+    int32_t anc;   // -1: the path has reached the root
+    int32_t pad;
+};
+
+constexpr int kUcThreads = 256;
+
+__global__ __launch_bounds__(kUcThreads) void k_uc_seed(const McfNode* __restrict__ node, int32_t n_nodes, int64_t m, int64_t d_bigm,
+                                                        McfJump* __restrict__ out, int32_t* __restrict__ info) {
+    __shared__ int32_t s_depth;
+    if (threadIdx.x == 0) s_depth = 0;
+    __syncthreads();
+    int32_t deepest = 0;
+    const int32_t stride = (int32_t)(gridDim.x * kUcThreads);
+    for (int32_t v = (int32_t)(blockIdx.x * kUcThreads + threadIdx.x); v < n_nodes; v += stride) {
+        const McfNode r = node[v];
+        McfJump j;
+        j.val = 0; j.anc = r.parent; j.pad = 0;
+        // an artificial arc costs big-M: a larger big-M is a cost change on the tree arc of every node that still hangs on one
+        if (r.pred >= 0 && (int64_t)(r.pred >> 1) >= m) j.val = (r.pred & 1) ? -d_bigm : d_bigm;
+        out[v] = j;
+        deepest = r.depth > deepest ? r.depth : deepest;
+    }
+    atomicMax(&s_depth, deepest);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_depth > 0) atomicMax(&info[0], s_depth);
+}
+
+__global__ __launch_bounds__(kUcThreads) void k_uc_scatter(int64_t count, const int32_t* __restrict__ arc, const int32_t* __restrict__ new_cost,
+                                                           int32_t* __restrict__ cost, const int8_t* __restrict__ state,
+                                                           const int32_t* __restrict__ tail, const int32_t* __restrict__ head,
+                                                           const McfNode* __restrict__ node, McfJump* __restrict__ jump, int32_t* __restrict__ info) {
+    const int64_t stride = (int64_t)gridDim.x * kUcThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kUcThreads + threadIdx.x; i < count; i += stride) {
+        const int32_t e = arc[i];
+        const int64_t delta = (int64_t)new_cost[i] - (int64_t)cost[e];
+        cost[e] = new_cost[i];
+        if (delta == 0 || state[e] != 0) continue;
+        // basic: the arc is the tree arc of exactly one of its end points; pi[x] = pi[parent] -+ cost (up / down)
+        const int32_t t = tail[e], hd = head[e];
+        const int32_t pt = node[t].pred, ph = node[hd].pred;
+        int32_t x = -1;
+        if (pt >= 0 && (pt >> 1) == e) x = t; else if (ph >= 0 && (ph >> 1) == e) x = hd;
+        if (x < 0) continue;
+        jump[x].val = x == t ? -delta : delta;
+        atomicAdd(&info[1], 1);
+    }
+}
+
+template <bool LAST>   // LAST: the sums are complete after this round and go straight into the potentials
+__global__ __launch_bounds__(kUcThreads) void k_uc_jump(const McfJump* __restrict__ in, McfJump* __restrict__ out, int64_t* __restrict__ pi, int32_t n_nodes) {
+    const int32_t stride = (int32_t)(gridDim.x * kUcThreads);
+    for (int32_t v = (int32_t)(blockIdx.x * kUcThreads + threadIdx.x); v < n_nodes; v += stride) {
+        McfJump a = in[v];
+        if (a.anc >= 0) {
+            const McfJump b = in[a.anc];
+            a.val += b.val;
+            a.anc = b.anc;
+        }
+        if (LAST) { if (a.val != 0) pi[v] += a.val; }
+        else out[v] = a;
+    }
+}
+
+// Bucket x's share of the 4-arc groups: a group that straddles a bucket boundary belongs to the lower bucket, the last
+// bucket takes the padding.  Workgroup b sweeps bucket b % 8 like k_price, so that the head gathers of an XCD's workgroups
+// stay inside one eighth of the potential array.
+__device__ __forceinline__ int64_t uc_group_lo(const McfView& v, int x, int64_t ngroups) {
+    if (x <= 0) return 0;
+    if (x >= MCF_NUM_BUCKETS) return ngroups;
+    return (v.bucket_off[x] + 3) >> 2;
+}
+
+constexpr int kUcUnroll = 2;   // 4-arc groups in flight per lane, as in k_price
+
+__global__ __launch_bounds__(kUcThreads) void k_uc_rebuild(McfView v, int64_t m_pad) {
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t ngroups = m_pad >> 2;
+    const int64_t g_lo = uc_group_lo(v, x, ngroups), g_hi = uc_group_lo(v, x + 1, ngroups);
+    const int4* __restrict__ tail4 = reinterpret_cast<const int4*>(v.tail);
+    const int4* __restrict__ head4 = reinterpret_cast<const int4*>(v.head);
+    const int4* __restrict__ cost4 = reinterpret_cast<const int4*>(v.cost);
+    const int32_t* __restrict__ state4 = reinterpret_cast<const int32_t*>(v.state);
+    const int64_t* __restrict__ pi = v.pi;
+    longlong2* __restrict__ rc2 = reinterpret_cast<longlong2*>(v.rcache);
+    int4* __restrict__ vk4 = reinterpret_cast<int4*>(v.vkey);
+    const int64_t bigm = v.vk_bigm;
+    const int32_t half = v.vk_half;
+    const int64_t stride = nlb * kUcThreads;
+    for (int64_t g0 = g_lo + lb * kUcThreads + threadIdx.x; g0 < g_hi; g0 += stride * kUcUnroll) {
+        int4 t[kUcUnroll], h[kUcUnroll], cc[kUcUnroll];
+        int32_t st[kUcUnroll];
+#pragma unroll
+        for (int u = 0; u < kUcUnroll; ++u) {
+            const int64_t g = g0 + u * stride;
+            const int64_t gs = g < g_hi ? g : g_lo;   // clamp: the loads stay unconditional and in range
+            t[u] = tail4[gs]; h[u] = head4[gs]; cc[u] = cost4[gs]; st[u] = state4[gs];
+        }
+        int64_t pt[kUcUnroll][4], ph[kUcUnroll][4];
+#pragma unroll
+        for (int u = 0; u < kUcUnroll; ++u) {
+            pt[u][0] = pi[t[u].x]; pt[u][1] = pi[t[u].y]; pt[u][2] = pi[t[u].z]; pt[u][3] = pi[t[u].w];
+            ph[u][0] = pi[h[u].x]; ph[u][1] = pi[h[u].y]; ph[u][2] = pi[h[u].z]; ph[u][3] = pi[h[u].w];
+        }
+#pragma unroll
+        for (int u = 0; u < kUcUnroll; ++u) {
+            const int64_t g = g0 + u * stride;
+            if (g >= g_hi) continue;
+            const int64_t r0 = (int64_t)cc[u].x + pt[u][0] - ph[u][0], r1 = (int64_t)cc[u].y + pt[u][1] - ph[u][1];
+            const int64_t r2 = (int64_t)cc[u].z + pt[u][2] - ph[u][2], r3 = (int64_t)cc[u].w + pt[u][3] - ph[u][3];
+            longlong2 a, b;
+            a.x = r0; a.y = r1; b.x = r2; b.y = r3;
+            rc2[2 * g] = a;
+            rc2[2 * g + 1] = b;
+            if (vk4) {
+                const int32_t s = st[u];
+                int4 k;
+                k.x = mcf_vkey(-(int64_t)(int8_t)s * r0, bigm, half);
+                k.y = mcf_vkey(-(int64_t)(int8_t)(s >> 8) * r1, bigm, half);
+                k.z = mcf_vkey(-(int64_t)(int8_t)(s >> 16) * r2, bigm, half);
+                k.w = mcf_vkey(-(int64_t)(int8_t)(s >> 24) * r3, bigm, half);
+                vk4[g] = k;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kUcThreads) void k_uc_ones(float4* __restrict__ w4, int64_t n4) {
+    const int64_t stride = (int64_t)gridDim.x * kUcThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kUcThreads + threadIdx.x; i < n4; i += stride) w4[i] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+}
+
 }  // namespace
 
 // ====================================================================== handle
@@ -1974,6 +2122,14 @@ struct mcf_handle {
     bool ctx_current = false;  // *h_ctx equals the device control block (no kernel was enqueued since it was read)
     bool external_driver = false;  // the caller enqueues the pivots itself (mcf_enqueue_*), possibly by replaying a graph it
                                    // captured: the library cannot know when the control block changes, so every read goes to the device
+    // mcf_update_costs: everything allocated on first use
+    std::vector<int32_t> uc_inv;     // caller's arc index -> engine arc index (inverse of im.orig)
+    std::vector<uint32_t> uc_stamp;  // per engine arc: the call that last named it (duplicates: the last entry wins)
+    uint32_t uc_gen = 0;
+    int32_t *d_uc_arc = nullptr, *d_uc_cost = nullptr;   // the changes, engine indices
+    int64_t uc_cap = 0;              // entries the two arrays hold
+    McfJump* d_uc_jump[2] = {nullptr, nullptr};          // pointer-jumping records, double buffered
+    int32_t* d_uc_info = nullptr;    // [0] greatest depth of the tree, [1] basic arcs among the changes
 };
 
 namespace {
@@ -2402,6 +2558,7 @@ void free_all(mcf_handle* h) {
     (void)hipFree(h->d_pos0); (void)hipFree(h->d_pos1); (void)hipFree(h->d_psz0); (void)hipFree(h->d_psz1); (void)hipFree(h->d_reach); (void)hipFree(h->d_chg); (void)hipFree(h->d_dirty); (void)hipFree(h->d_swept); (void)hipFree(h->d_dx); (void)hipFree(h->d_full_tab);
     (void)hipFree(h->d_rcache); (void)hipFree(h->d_adj_off); (void)hipFree(h->d_adj); (void)hipFree(h->d_vkey); (void)hipFree(h->d_candx);
     for (int a = 0; a < 2; ++a) { (void)hipFree(h->d_bmeta[a]); (void)hipFree(h->d_bext[a]); }
+    (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost); (void)hipFree(h->d_uc_jump[0]); (void)hipFree(h->d_uc_jump[1]); (void)hipFree(h->d_uc_info);
     if (h->h_ctx) pinned_give(reinterpret_cast<char*>(h->h_ctx));   // (h_one lives in the same slot)
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
 }
@@ -2782,6 +2939,136 @@ int mcf_set_basis(mcf_handle* h, const int8_t* in_tree, const int8_t* at_upper) 
     const int rc = upload_image(h);
     if (rc) return rc;
     if (!msg.empty()) { h->err = "warm-start basis rejected: " + msg; return MCF_E_STATE; }
+    return MCF_OK;
+}
+
+// Re-optimise after a cost change: the resident basis stays, potentials / reduced costs / key codes follow the new costs
+// (kernels k_uc_* above).  Everything is validated on the host before the first byte moves.
+int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int64_t* new_cost) {
+    if (!h) return MCF_E_BAD_ARG;
+    if (h->shards != 1) {
+        h->err = "mcf_update_costs: handle was created with shard_count > 1; sharded handles cannot change their costs";
+        return MCF_E_STATE;
+    }
+    if (count < 0 || (count > 0 && (!arc || !new_cost))) { h->err = "mcf_update_costs: bad count / null array"; return MCF_E_BAD_ARG; }
+    McfHostImage& im = h->im;
+    for (int64_t i = 0; i < count; ++i)
+        if (arc[i] < 0 || arc[i] >= im.m) { h->err = "mcf_update_costs: arc index out of range"; return MCF_E_BAD_ARG; }
+    for (int64_t i = 0; i < count; ++i)
+        if (new_cost[i] > INT32_MAX || new_cost[i] < -(int64_t)INT32_MAX) { h->err = "mcf_update_costs: |cost| must fit int32"; return MCF_E_RANGE; }
+    if (count > 0 && h->uc_inv.empty()) {
+        h->uc_inv.assign((size_t)im.m, 0);
+        for (int64_t e = 0; e < im.m; ++e) h->uc_inv[(size_t)im.orig[(size_t)e]] = (int32_t)e;
+        h->uc_stamp.assign((size_t)im.m, 0);
+        h->uc_gen = 0;
+    }
+    if (++h->uc_gen == 0) { std::fill(h->uc_stamp.begin(), h->uc_stamp.end(), 0u); h->uc_gen = 1; }
+    // duplicates: the last entry wins (walk backwards, keep the first sighting of every arc)
+    std::vector<int32_t> ue, uc;
+    ue.reserve((size_t)count); uc.reserve((size_t)count);
+    int64_t max_abs = 0;
+    for (int64_t i = count - 1; i >= 0; --i) {
+        const int32_t e = h->uc_inv[(size_t)arc[i]];
+        if (h->uc_stamp[(size_t)e] == h->uc_gen) continue;
+        h->uc_stamp[(size_t)e] = h->uc_gen;
+        ue.push_back(e); uc.push_back((int32_t)new_cost[i]);
+        const int64_t a = new_cost[i] < 0 ? -new_cost[i] : new_cost[i];
+        if (a > max_abs) max_abs = a;
+    }
+    // big-M never shrinks; it grows when a new cost needs it (same rule as mcf_build_image)
+    int64_t big_m = im.big_m;
+    if ((max_abs + 1) * ((int64_t)im.n + 2) > big_m) big_m = (max_abs + 1) * ((int64_t)im.n + 2);
+    if (big_m >= ((int64_t)1 << 44)) { h->err = "mcf_update_costs: max|cost| * n too large for big-M"; return MCF_E_RANGE; }
+    const int64_t d_bigm = big_m - im.big_m;
+    const int64_t nu = (int64_t)ue.size();
+
+    HIP_TRY(h, hipSetDevice(h->device));
+    // temporaries
+    if (!h->d_uc_info) {
+        for (int a = 0; a < 2; ++a)
+            if (dalloc(&h->d_uc_jump[a], (size_t)im.n_nodes) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc jump records"; return MCF_E_ALLOC; }
+        if (dalloc(&h->d_uc_info, 2) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc update info"; return MCF_E_ALLOC; }
+    }
+    if (nu > h->uc_cap) {
+        (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost);
+        h->d_uc_arc = nullptr; h->d_uc_cost = nullptr; h->uc_cap = 0;
+        const int64_t cap = nu + nu / 2 + 1024;
+        if (dalloc(&h->d_uc_arc, (size_t)cap) != hipSuccess || dalloc(&h->d_uc_cost, (size_t)cap) != hipSuccess) {
+            (void)hipGetLastError();
+            h->err = "hipMalloc cost changes";
+            return MCF_E_ALLOC;
+        }
+        h->uc_cap = cap;
+    }
+    int rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    if (h->h_ctx->status == MCF_INTERNAL_ERROR) { h->err = "mcf_update_costs: the handle's tree is not usable"; return MCF_E_STATE; }
+
+    hipStream_t s = h->stream;
+    const int32_t N = im.n_nodes;
+    auto blocks_for = [](int64_t items) { const int64_t b = (items + kUcThreads - 1) / kUcThreads; return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); };
+    if (nu > 0) {
+        HIP_TRY(h, hipMemcpyAsync(h->d_uc_arc, ue.data(), (size_t)nu * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(h->d_uc_cost, uc.data(), (size_t)nu * 4, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipMemsetAsync(h->d_uc_info, 0, 2 * sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_uc_seed, dim3(blocks_for(N)), dim3(kUcThreads), 0, s, (const McfNode*)h->d_node, N, im.m, d_bigm, h->d_uc_jump[0], h->d_uc_info);
+    if (nu > 0)
+        hipLaunchKernelGGL(k_uc_scatter, dim3(blocks_for(nu)), dim3(kUcThreads), 0, s, nu, (const int32_t*)h->d_uc_arc, (const int32_t*)h->d_uc_cost,
+                           h->d_cost, (const int8_t*)h->d_state, (const int32_t*)h->d_tail, (const int32_t*)h->d_head, (const McfNode*)h->d_node,
+                           h->d_uc_jump[0], h->d_uc_info);
+    HIP_TRY(h, hipGetLastError());
+    int32_t info[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(info, h->d_uc_info, sizeof info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));   // (also: the pageable sources above are free again)
+    // potentials: only when a tree arc changed (or big-M grew); rounds = ceil(log2(greatest depth)), at least the final one
+    if (info[1] > 0 || d_bigm != 0) {
+        int rounds = 1;
+        while (((int64_t)1 << rounds) < (int64_t)info[0]) ++rounds;
+        int cur = 0;
+        for (int r = 0; r < rounds; ++r) {
+            if (r + 1 < rounds) hipLaunchKernelGGL(k_uc_jump<false>, dim3(blocks_for(N)), dim3(kUcThreads), 0, s, (const McfJump*)h->d_uc_jump[cur], h->d_uc_jump[cur ^ 1], h->d_pi, N);
+            else hipLaunchKernelGGL(k_uc_jump<true>, dim3(blocks_for(N)), dim3(kUcThreads), 0, s, (const McfJump*)h->d_uc_jump[cur], h->d_uc_jump[cur ^ 1], h->d_pi, N);
+            cur ^= 1;
+        }
+    }
+    // the view's big-M first: the key codes below are formed with it, and captured graphs carry the view by value
+    if (d_bigm != 0) {
+        h->view.vk_bigm = big_m;
+        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+        if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+        h->graph_batch = 0;
+    }
+    if (h->rcached) {   // (a handle that dropped its reduced costs, or never kept any, prices from the potentials)
+        int64_t pb = (im.m_pad / 4 / MCF_NUM_BUCKETS + kUcThreads * kUcUnroll - 1) / (kUcThreads * kUcUnroll);
+        pb = pb < 1 ? 1 : (pb > 2048 / MCF_NUM_BUCKETS ? 2048 / MCF_NUM_BUCKETS : pb);
+        hipLaunchKernelGGL(k_uc_rebuild, dim3((unsigned)pb * MCF_NUM_BUCKETS), dim3(kUcThreads), 0, s, h->view, im.m_pad);
+    }
+    // derived pricing state: candidate list and cache, clean / dirty marks, Devex weights, block cursor, tuner
+    HIP_TRY(h, hipMemsetAsync(h->d_cand, 0xff, kMaxPriceBlocks * sizeof(McfCand), s));
+    if (h->d_candx) HIP_TRY(h, hipMemsetAsync(h->d_candx, 0xff, kMaxPriceBlocks * sizeof(McfCandX), s));
+    if (h->d_dirty) HIP_TRY(h, hipMemsetAsync(h->d_dirty->flag, 1, sizeof(h->d_dirty->flag), s));
+    if (h->opt.rule == MCF_RULE_DEVEX_BLOCK) hipLaunchKernelGGL(k_uc_ones, dim3(blocks_for(im.m_pad / 4)), dim3(kUcThreads), 0, s, reinterpret_cast<float4*>(h->d_weight), im.m_pad / 4);
+    HIP_TRY(h, hipGetLastError());
+    {
+        McfCtx& c = *h->h_ctx;   // current (sync_ctx above; nothing since has touched the device's copy)
+        c.status = MCF_RUNNING;
+        c.limit_checked = 0;
+        c.unbounded_arc = -1;
+        c.minor_left = 0;
+        mcf_init_block_state(&c, h->opt.rule, im.m, h->opt.block_size);
+        if (h->opt.rule == MCF_RULE_DEVEX_BLOCK) {
+            if (h->opt.devex_tuner > 0) c.auto_tune = 1; else if (h->opt.devex_tuner < 0) c.auto_tune = 0;
+            if (h->opt.devex_stay > 0) c.devex_cyclic = 0;
+        }
+        HIP_TRY(h, hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->ctx_current = false;
+    // host image: a later mcf_reset / mcf_set_basis (which rebuild its potentials and reduced costs from these) and the
+    // objective of mcf_get_result use the new costs
+    for (int64_t i = 0; i < nu; ++i) { im.cost[(size_t)ue[(size_t)i]] = uc[(size_t)i]; im.cost64[(size_t)ue[(size_t)i]] = uc[(size_t)i]; }
+    im.big_m = big_m;
     return MCF_OK;
 }
 

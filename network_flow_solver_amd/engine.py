@@ -29,7 +29,7 @@ KEY_PLAIN, KEY_FORWARD_FIRST, KEY_PRIORITY, KEY_CAPACITY = 0, 1, 2, 3   # mcf_op
 
 # every symbol include/mcf.h declares (tests check that the library exports each one)
 ABI_SYMBOLS = (
-    "mcf_default_options", "mcf_create", "mcf_solve", "mcf_solve_batch", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis",
+    "mcf_default_options", "mcf_create", "mcf_solve", "mcf_solve_batch", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs",
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
 )
@@ -109,6 +109,7 @@ def load_library():
     lib.mcf_solve_batch.argtypes = [ctypes.POINTER(vp), ctypes.c_int32, i64p, ctypes.POINTER(ctypes.c_double)]
     lib.mcf_reset.argtypes = [vp]
     lib.mcf_set_basis.argtypes = [vp, i8p, i8p]
+    lib.mcf_update_costs.argtypes = [vp, ctypes.c_int64, i64p, i64p]
     lib.mcf_enqueue_price.argtypes = [vp, vp, vp]
     lib.mcf_enqueue_pivot.argtypes = [vp, vp, vp, ctypes.c_int32]
     lib.mcf_shard_info.argtypes = [vp, i32p, i32p]
@@ -129,7 +130,7 @@ def load_library():
     lib.mcf_last_error.restype = ctypes.c_char_p
     lib.mcf_destroy.argtypes = [vp]
     lib.mcf_destroy.restype = None
-    for name in ("mcf_create", "mcf_solve", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_enqueue_price",
+    for name in ("mcf_create", "mcf_solve", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs", "mcf_enqueue_price",
                  "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing", "mcf_time_copy",
                  "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load"):
         getattr(lib, name).restype = ctypes.c_int
@@ -168,6 +169,7 @@ class McfEngine:
                  vkey_half_log2: int = 0, climb_depth: int = 0, overlap_update: int = 0, key_mode: int = 0, arc_priority=None,
                  tree_blocks: int = 0, tree_pool: int = 0, rc_drop: int = 0, pivot_run: int = 0):
         self._h = None
+        self._cost_private = False
         lib = load_library()
         if lib.mcf_device_count() <= 0:
             raise EngineUnavailableError("no HIP device visible; the network-simplex engine has no CPU fallback")
@@ -313,6 +315,21 @@ class McfEngine:
             return False
         self._check(rc)
         return True
+
+    def update_costs(self, arcs, costs) -> None:
+        """New integer costs for the arcs ``arcs`` (this engine's arc order; of duplicates the last entry wins).  The
+        device-resident basis stays: potentials, reduced costs and key codes follow the new costs on the device, and the next
+        ``solve()`` goes on pivoting from it (``mcf_update_costs``)."""
+        a = np.ascontiguousarray(arcs, dtype=np.int64).reshape(-1)
+        c = np.ascontiguousarray(costs, dtype=np.int64).reshape(-1)
+        if a.shape[0] != c.shape[0]:
+            raise ValueError("arcs and costs differ in length")
+        self._check(self._lib.mcf_update_costs(self._h, int(a.shape[0]), _p(a, ctypes.c_int64), _p(c, ctypes.c_int64)))
+        if a.shape[0]:
+            if not self._cost_private:     # the array may be the caller's own: copied once, on the first change
+                self.cost = self.cost.copy()
+                self._cost_private = True
+            self.cost[a] = c               # (numpy assigns in order: the last entry wins here too)
 
     def last_error(self) -> str:
         return (self._lib.mcf_last_error(self._h) or b"").decode()

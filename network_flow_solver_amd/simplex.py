@@ -20,10 +20,11 @@ There is no CPU fallback here: without the HIP library or a GPU,
 
 from __future__ import annotations
 
+import copy
 import logging
 import math
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 
@@ -183,6 +184,69 @@ def flatten_problem(problem: NetworkProblem, tolerance: float | None = None) -> 
                        cost, flow_scale, cost_scale)
 
 
+def map_cost_changes(flat: FlatProblem, changes, tolerance: float) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Cost changes in the caller's terms -> ``(arc indices, integer engine costs, costs in caller units)`` in ``flat``'s arc
+    order, one entry per changed arc.  Pure: neither ``flat`` nor ``changes`` is modified.
+
+    * object-model problems: ``changes`` maps ``(tail id, head id)`` to the new cost.  Of parallel arcs with one key the
+      LAST index takes it, like the key -> index map of a warm start (``_apply_warm_start_basis``); a key the problem does
+      not have is an ``InvalidProblemError``.
+    * ``SoAProblem``: ``changes`` is a pair ``(indices, costs)`` of arrays in the problem's arc order; of duplicate indices
+      the last entry wins.
+
+    Every new cost has to be an integer at ``flat.cost_scale`` (the decimal scaling chosen when the problem was flattened)
+    to within ``tolerance`` in the caller's units -- the engine is integer and the scale of the resident instance is fixed --
+    and fit int32 after scaling; otherwise ``InvalidProblemError`` / ``SolverConfigurationError``, and nothing is returned."""
+    m = len(flat.keys)
+    if flat.soa:
+        try:
+            if hasattr(changes, "items"):
+                raise TypeError
+            idx_in, cost_in = changes
+        except (TypeError, ValueError):
+            raise InvalidProblemError("cost changes of an SoAProblem are a pair (indices, costs) of arrays") from None
+        idx = np.asarray(idx_in).reshape(-1)
+        values = np.asarray(cost_in, dtype=np.float64).reshape(-1)
+        if idx.shape[0] != values.shape[0]:
+            raise InvalidProblemError("cost changes: indices and costs differ in length")
+        if idx.size and not np.issubdtype(idx.dtype, np.integer):
+            raise InvalidProblemError("cost changes: arc indices must be integers")
+        idx = idx.astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= m):
+            raise InvalidProblemError(f"cost changes: arc index outside [0, {m})")
+        # the last entry of every index wins
+        _, first_rev = np.unique(idx[::-1], return_index=True)
+        keep = np.sort(idx.shape[0] - 1 - first_rev)
+        idx, values = idx[keep], values[keep]
+    else:
+        if not hasattr(changes, "items"):
+            raise InvalidProblemError("cost changes are a mapping {(tail, head): cost}")
+        last: dict[tuple[str, str], int] = {}
+        for i, key in enumerate(flat.keys):
+            last[key] = i
+        picked: dict[int, float] = {}
+        for key, value in changes.items():
+            i = last.get(tuple(key))
+            if i is None:
+                raise InvalidProblemError(f"cost change names arc {tuple(key)} which is not in the problem")
+            picked[i] = float(value)
+        idx = np.fromiter(picked.keys(), dtype=np.int64, count=len(picked))
+        values = np.fromiter(picked.values(), dtype=np.float64, count=len(picked))
+    if values.size and not np.all(np.isfinite(values)):
+        raise InvalidProblemError("costs must be finite numbers")
+    scaled = values * float(flat.cost_scale)
+    rounded = np.round(scaled)
+    off = np.abs(scaled - rounded) > tolerance * flat.cost_scale
+    if off.any():
+        i = int(np.nonzero(off)[0][0])
+        raise InvalidProblemError(
+            f"new cost {values[i]} of arc {flat.keys[int(idx[i])]} is not a multiple of 1/{flat.cost_scale}, the cost "
+            f"resolution this solver was built with; build a new solver for finer costs")
+    if rounded.size and np.abs(rounded).max() >= 2 ** 31:
+        raise SolverConfigurationError("scaled costs must fit int32")
+    return idx, rounded.astype(np.int64), values
+
+
 class NetworkSimplex:
     """Network simplex solver for minimum-cost flow, pivoting on an MI355X.
 
@@ -231,6 +295,7 @@ class NetworkSimplex:
             self.flat.supply, rule=self.pricing_rule, block_size=block_size, batch_pivots=batch_pivots,
             use_graph=use_graph, device=device, **(special or {}), **(engine_options or {}))
         self.stats: dict = {}
+        self._pivots_seen = 0   # the engine's cumulative pivot count when the last solve() returned
 
     # simplex.py:314-374: the reference's grid-on-torus heuristic switches to Dantzig unless the
     # caller pinned a strategy
@@ -267,6 +332,7 @@ class NetworkSimplex:
             if not basis.in_tree.any():
                 self.logger.warning("Warm-start basis is empty. Falling back to cold start.")
                 return False
+            self._pivots_seen = 0                                  # (mcf_set_basis resets the engine's counters either way)
             if self.engine.set_basis(basis.in_tree, basis.at_upper):
                 self.logger.info(f"Successfully applied warm-start basis with {int(basis.in_tree.sum())} basis arcs")
                 return True
@@ -294,11 +360,42 @@ class NetworkSimplex:
             i = idxs[-1]
             if f.cap[i] > 0 and round(float(value) * f.flow_scale) >= f.cap[i]:
                 at_upper[i] = 1
+        self._pivots_seen = 0
         if self.engine.set_basis(in_tree, at_upper):
             self.logger.info(f"Successfully applied warm-start basis with {int(in_tree.sum())} basis arcs")
             return True
         self.logger.warning(f"{self.engine.last_error()}. Falling back to cold start.")
         return False
+
+    def update_costs(self, changes) -> int:
+        """Change arc costs and keep the solved state: the basis that is resident on the device stays, its potentials and
+        reduced costs are brought in line with the new costs there (``mcf_update_costs``), and the next ``solve()`` goes on
+        pivoting from it -- no new solver, no upload, no warm-start hand-over.  ``changes``: ``{(tail, head): cost}`` for
+        an object-model problem, ``(indices, costs)`` for an ``SoAProblem`` (see ``map_cost_changes``; on an invalid
+        change nothing is changed).  The caller's problem object is left alone: ``self.problem`` becomes an updated copy.
+        Returns the number of arcs whose cost was set."""
+        f = self.flat
+        idx, cost_i, cost_f = map_cost_changes(f, changes, self.tolerance)
+        self.engine.update_costs(idx, cost_i)
+        new_cost = f.cost.copy()
+        new_cost[idx] = cost_i
+        if f.soa:
+            problem = copy.copy(self.problem)
+            problem.cost = new_cost
+            problem._arcs = None
+            self.problem = problem
+            self.flat = replace(f, cost=new_cost, orig_cost=new_cost.astype(np.float64))
+        else:
+            orig_cost = f.orig_cost.copy()
+            orig_cost[idx] = cost_f
+            arcs = list(self.problem.arcs)
+            # flat arc j is arc order[j] of the problem (flatten_problem: a stable sort by key)
+            order = sorted(range(len(arcs)), key=lambda i: (arcs[i].tail, arcs[i].head))
+            for j, c in zip(idx.tolist(), cost_f.tolist()):
+                arcs[order[j]] = replace(arcs[order[j]], cost=c)
+            self.problem = replace(self.problem, nodes=dict(self.problem.nodes), arcs=arcs)
+            self.flat = replace(f, cost=new_cost, orig_cost=orig_cost)
+        return int(idx.shape[0])
 
     def _objective_estimate(self, flow: np.ndarray) -> float:
         f = self.flat
@@ -349,7 +446,9 @@ class NetworkSimplex:
         m = self.actual_arc_count
         res = self.engine.result()
         self.stats = res.stats
-        iterations = int(res.stats["pivots"])
+        # the engine counts pivots cumulatively over successive solves of one handle: report this call's
+        iterations = int(res.stats["pivots"]) - self._pivots_seen
+        self._pivots_seen = int(res.stats["pivots"])
         self.degenerate_pivots = int(res.stats["degenerate"])
 
         if res.status == "unbounded":                             # simplex.py:1231-1246
