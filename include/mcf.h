@@ -127,7 +127,7 @@ typedef struct mcf_options {
                                 3 = capacity x violation (max flow, :284-335).  Not with MCF_RULE_DEVEX_BLOCK. */
     const int8_t* arc_priority; /* key_mode 2: one byte per arc, caller's order; bit 0 = preferred as a forward candidate (flow rises
                                 from the lower bound), bit 1 = preferred as a backward candidate.  Read during mcf_create only. */
-    int32_t tree_blocks;     /* layout of the spanning tree's preorder: 0 = auto (blocked preorder list from 32 768 nodes on), -1 = dense
+    int32_t tree_blocks;     /* layout of the spanning tree's preorder: 0 = auto (blocked preorder list from 200 000 nodes on), -1 = dense
                                 array, k in 2..10 = blocked list with blocks of 2^k slots.  The blocked list re-hangs a subtree in
                                 O(subtree + block) element moves instead of shifting every position between its old and its new
                                 place (replaces the per-pivot BFS rebuild basis.py:82-125 and _update_tree_sets simplex.py:1103-1107);
@@ -227,7 +227,10 @@ int mcf_create(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, c
                const int64_t* cap, const int64_t* supply, const mcf_options* opt, mcf_handle** out);
 
 /* Pivot until optimal / unbounded / max_pivots more pivots were made (max_pivots < 0:
- * the reference's default budget max(100, 20 * (m + n)), simplex.py:1470). */
+ * the reference's default budget max(100, 20 * (m + n)), simplex.py:1470).
+ * A verdict is final: on a handle whose status is already optimal, infeasible or unbounded the call is a no-op that makes no
+ * pivot and leaves status, counters (mcf_stats.pivots, unbounded_arc, ...) and every array as they are; only an iteration
+ * limit is resumed.  mcf_reset, mcf_set_basis and mcf_update_costs are what put such a handle back to "running". */
 int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user, int64_t cb_interval);
 
 /* Solve `count` INDEPENDENT instances side by side: one persistent workgroup (one CU) per handle, each running its whole

@@ -217,7 +217,7 @@ class McfEngine:
             opt.arc_priority = _p(self._arc_priority, ctypes.c_int8)
         opt.overlap_update = int(overlap_update)     # 1 = pricing of pivot t+1 beside the permutation of pivot t (A/B switch: measured slower)
         opt.climb_depth = int(climb_depth)           # 0 auto, -1 never, k: end points of depth <= k are climbed outright
-        # layout of the tree's preorder: 0 auto (blocked list from 32 768 nodes on), -1 dense array, k = blocks of 2^k slots;
+        # layout of the tree's preorder: 0 auto (blocked list from 200 000 nodes on), -1 dense array, k = blocks of 2^k slots;
         # MCF_TREE_BLOCKS / MCF_TREE_POOL override the default (A/B runs of whole scripts)
         opt.tree_blocks = int(tree_blocks) if tree_blocks else int(os.environ.get("MCF_TREE_BLOCKS", "0"))
         opt.tree_pool = int(tree_pool) if tree_pool else int(os.environ.get("MCF_TREE_POOL", "0"))
