@@ -21,6 +21,8 @@
  *   solving again after arc costs changed: the reference builds a new NetworkSimplex
  *       from the edited problem and passes solve(warm_start_basis=...)
  *       simplex.py:99-265, 1491-1532 .........................................  mcf_update_costs (the resident basis stays)
+ *   validate_flow / compute_bottleneck_arcs  utils.py:169-312 (conservation, bounds, arcs
+ *       near capacity of a solution; the reference checks nothing on the dual side) ......  mcf_certify / mcf_bottlenecks
  *   AdaptiveTuner.adapt_block_size  simplex_adaptive.py:98-151 and the
  *       periodic Devex reset  simplex.py:1370-1400 ..........................  inside mcf_solve (MCF_RULE_DEVEX_BLOCK)
  *   specialised pivot strategies  specialized_pivots.py:69-424, 452-527 .....  mcf_options.key_mode (+ arc_priority): row scan,
@@ -293,6 +295,86 @@ int mcf_set_basis(mcf_handle* h, const int8_t* in_tree, const int8_t* at_upper);
  *              block cursor and the block-size tuner are at their start values.  A later mcf_reset / mcf_set_basis and
  *              the objective of mcf_get_result use the new costs. */
 int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int64_t* new_cost);
+
+/* ---- certificate on the device (the reference's validate_flow / compute_bottleneck_arcs, utils.py:169-312, plus the dual
+ * half the reference never checks).  Conservation, bounds, complementary slackness, the exact objectives and the
+ * consistency of the resident basis are evaluated where the data is: one streaming pass over the arcs, one pass over the
+ * nodes (conservation is a gather over the node -> arc adjacency), a final reduction; a few hundred bytes come back.
+ *
+ *   flow, potential   NULL = the handle's resident arrays (nothing is downloaded).  Non-NULL = the caller's arrays --
+ *                     flow[m] in the caller's arc order, potential[n] with the root excluded, the layout of mcf_get_result
+ *                     -- certified against the handle's instance (costs, capacities, supplies, topology).  They are
+ *                     uploaded to scratch buffers; the handle's own state is not touched.  A caller's flow says nothing
+ *                     about artificial arcs: node balances are then reported as they stand (validate_flow's meaning) and
+ *                     artificial_flow is 0.  Caller's potentials must satisfy |potential| <= 2^61 (MCF_E_RANGE).
+ *   checks            MCF_CERT_* groups, 0 = all.  BASIS and PRICING describe the resident state and are evaluated only
+ *                     when flow and potential are both NULL; `checks` in the result names the groups that were evaluated.
+ *   read-only         nothing the solver reads is written: status, counters, candidate lists, dirty marks, Devex weights
+ *                     and tuner stay bit-identical and a later mcf_solve makes the same pivots.  Valid between solves in
+ *                     any state of the handle, on every engine path, tree layout, rule and key_mode, on handles that
+ *                     dropped their resident reduced costs, and on handles with shard_count > 1 (every arc is checked from
+ *                     the replicated state; resident reduced costs / key codes only where the shard keeps them).
+ *   arithmetic        exact integers.  rc = cost + pi[tail] - pi[head].  Sums are 128-bit (two 64-bit halves, high first,
+ *                     like mcf_get_result's objective).  Every "worst" is a magnitude > 0 with the caller's index of the
+ *                     FIRST arc / node attaining it (ties: lowest index; -1: none), so results compare with numpy.
+ *   dual objective    of the big-M problem  min c x + bigM a  s.t.  outflow - inflow = supply, 0 <= x <= cap.  With the
+ *                     sign convention of rc above, c x = -sum_v pi[v] supply[v] + sum_e rc[e] x[e], hence
+ *                         dual = -sum_v pi[v] * supply[v] + sum over capped arcs with rc < 0 of rc * cap
+ *                     (an uncapacitated arc with rc < 0 makes the dual infeasible: it is counted in dual_lower_count and
+ *                     contributes nothing).  gap = primal + bigm_term - dual; 0 at an optimal basis.
+ *   verdict           what the evidence proves, all groups 1..8 evaluated: MCF_CERT_OPTIMAL = every primal and dual count
+ *                     is 0, gap is 0, no artificial flow; MCF_CERT_INFEASIBLE = the same with artificial flow > 0 (the
+ *                     flow is optimal for the big-M problem over the arcs the basis still holds); else MCF_CERT_NOT_PROVEN.
+ *                     An unbounded status needs a ray, which is outside this call: always MCF_CERT_NOT_PROVEN.
+ *                     proves_status = 1 when the handle's status is optimal / infeasible and the verdict says the same.
+ *   errors            MCF_E_BAD_ARG: null handle, null out, unknown bits in checks.  MCF_E_NO_DEVICE as elsewhere.
+ * Scratch (partials, uploads, supplies: 8 B per node, an adjacency where the handle holds none or a shard's only) is
+ * allocated on first use and freed by mcf_destroy; mcf_create costs what it did. */
+#define MCF_CERT_BOUNDS 1u
+#define MCF_CERT_CONSERVATION 2u
+#define MCF_CERT_DUAL 4u
+#define MCF_CERT_OBJECTIVES 8u
+#define MCF_CERT_BASIS 16u
+#define MCF_CERT_PRICING 32u
+#define MCF_CERT_NOT_PROVEN 0
+#define MCF_CERT_OPTIMAL 1
+#define MCF_CERT_INFEASIBLE 2
+
+typedef struct mcf_certificate {
+    int64_t checks;                /* groups evaluated */
+    int64_t status;                /* MCF_ST_* as mcf_get_result would report it, -1 while the handle is "running" */
+    int64_t verdict;               /* MCF_CERT_* */
+    int64_t proves_status;
+    /* primal: bounds */
+    int64_t negative_flow_count, over_capacity_count, bounds_worst, bounds_worst_arc;
+    /* primal: conservation (|balance| saturates at INT64_MAX) */
+    int64_t imbalance_count, imbalance_worst, imbalance_worst_node;
+    /* dual feasibility / complementary slackness */
+    int64_t dual_lower_count, dual_lower_worst, dual_lower_arc;   /* rc < 0, flow below capacity or uncapacitated */
+    int64_t dual_upper_count, dual_upper_worst, dual_upper_arc;   /* rc > 0, flow > 0 */
+    /* objectives, {high, low} */
+    int64_t primal[2], bigm_term[2], dual[2], gap[2];
+    int64_t artificial_flow, big_m;
+    /* basis consistency (resident state) */
+    int64_t basic_arcs;            /* arcs marked basic + artificial tree arcs; must be n */
+    int64_t basic_count_mismatch;  /* basic_arcs != n */
+    int64_t tree_rc_count;         /* tree arcs with rc != 0 */
+    int64_t state_flow_count;      /* state +1 with flow != 0, state -1 with flow != cap */
+    int64_t tree_shape_count;      /* nodes whose parent / pos / size / depth / psize / pred-arc records disagree */
+    int64_t strong_count;          /* basic arcs on a bound pointing the wrong way (what mcf_set_basis repairs) */
+    /* resident pricing data */
+    int64_t rc_compared, rc_mismatch_count, key_compared, key_mismatch_count;
+    int64_t saturated_arcs;        /* capped arcs with flow == cap > 0 (mcf_bottlenecks at 1/1) */
+    double arc_pass_ms, node_pass_ms;   /* kernel durations by HIP events */
+} mcf_certificate;
+
+int mcf_certify(mcf_handle* h, const int64_t* flow, const int64_t* potential, uint32_t checks, mcf_certificate* out);
+
+/* compute_bottleneck_arcs (utils.py:250-312) as an exact test: the capped arcs that carry flow with
+ * flow * den >= cap * num (128-bit products; num >= 0, den > 0), flow = the caller's (caller's order) or NULL = resident.
+ * *count <- how many there are; idx_out[0 .. min(count, idx_cap)) <- their caller's indices in ascending order, compacted
+ * on the device (idx_out may be NULL with idx_cap 0).  Read-only like mcf_certify. */
+int mcf_bottlenecks(mcf_handle* h, const int64_t* flow, int64_t num, int64_t den, int64_t* idx_out, int64_t idx_cap, int64_t* count);
 
 /* ---- arc-sharded multi-GPU pivoting: one handle per rank, every rank holds the full
  * replicated state and prices only its shard (options.shard_rank / shard_count).  Per pivot:

@@ -1859,3 +1859,122 @@ MCF_HD void mcf_reach_reindex_block(const McfView& v, const int32_t* zs, int32_t
     }
     v.reach[b] = m;
 }
+
+// ====================================================================== certificate (mcf_certify, include/mcf.h)
+// Per-arc and per-node logic of the device certificate, shared by the kernels (k_cert_arcs / k_cert_nodes) and by the
+// host restatement the CPU tests call (csrc/mcf_certify_host.cpp).  Every partial result combines by an integer sum, a max
+// or a (max, lowest index) pair -- all associative and commutative -- so the order in which lanes, waves and workgroups
+// are merged cannot change a single bit of the result.  Sums that can pass 64 bits are kept as unsigned 128-bit
+// integers (two's complement, modulo 2^128).
+typedef unsigned __int128 mcf_u128;
+
+#define MCF_CERT_BOUNDS 1u        // flow < 0, flow > cap
+#define MCF_CERT_CONSERVATION 2u  // supply + inflow - outflow per node
+#define MCF_CERT_DUAL 4u          // sign of the reduced costs against the flows
+#define MCF_CERT_OBJECTIVES 8u    // primal, big-M term, dual, gap
+#define MCF_CERT_BASIS 16u        // resident only: tree, states, strong feasibility
+#define MCF_CERT_PRICING 32u      // resident only: reduced-cost and key-code copies
+#define MCF_CERT_ALL 63u
+#define MCF_CERT_NONE INT64_MAX   // "no index yet" inside an accumulator (becomes -1 in the result)
+
+struct McfCertArcAcc {
+    int64_t neg_n, over_n, bnd_w, bnd_i;          // bounds: counts, worst excess, its arc
+    int64_t dlo_n, dlo_w, dlo_i;                  // rc < 0 on an arc that could take more flow
+    int64_t dup_n, dup_w, dup_i;                  // rc > 0 on an arc that carries flow
+    int64_t basic_n, stf_n;                       // real arcs marked basic; state / flow disagreements
+    int64_t rc_n, rc_bad, key_n, key_bad;         // resident copies compared / found different
+    int64_t sat_n;                                // capped arcs carrying flow == cap
+    uint64_t primal_lo, primal_hi;                // sum flow * cost
+    uint64_t dcap_lo, dcap_hi;                    // sum over capped arcs with rc < 0 of rc * cap (<= 0)
+};
+struct McfCertNodeAcc {
+    int64_t imb_n, imb_w, imb_i;                  // non-zero balances, largest |balance| (saturating at INT64_MAX), its node
+    int64_t art_basic, tree_rc_bad, shape_bad, strong_bad;
+    uint64_t art_lo, art_hi;                      // sum of the artificial flows
+    uint64_t dnode_lo, dnode_hi;                  // - sum pi[v] * supply[v]
+};
+#define MCF_CERT_ARC_WORDS ((int)(sizeof(McfCertArcAcc) / 8))
+#define MCF_CERT_NODE_WORDS ((int)(sizeof(McfCertNodeAcc) / 8))
+
+MCF_HD void mcf_cert_arc_init(McfCertArcAcc* a) {
+    uint64_t* p = reinterpret_cast<uint64_t*>(a);
+    for (int k = 0; k < MCF_CERT_ARC_WORDS; ++k) p[k] = 0;
+    a->bnd_i = a->dlo_i = a->dup_i = MCF_CERT_NONE;
+}
+MCF_HD void mcf_cert_node_init(McfCertNodeAcc* a) {
+    uint64_t* p = reinterpret_cast<uint64_t*>(a);
+    for (int k = 0; k < MCF_CERT_NODE_WORDS; ++k) p[k] = 0;
+    a->imb_i = MCF_CERT_NONE;
+}
+MCF_HD void mcf_cert_worst(int64_t* w, int64_t* wi, int64_t mag, int64_t idx) {
+    if (mag > *w || (mag == *w && idx < *wi)) { *w = mag; *wi = idx; }
+}
+MCF_HD void mcf_cert_add128(uint64_t* lo, uint64_t* hi, mcf_u128 x) {
+    const mcf_u128 s = (((mcf_u128)*hi << 64) | *lo) + x;
+    *lo = (uint64_t)s; *hi = (uint64_t)(s >> 64);
+}
+MCF_HD void mcf_cert_arc_merge(McfCertArcAcc* a, const McfCertArcAcc& b) {
+    a->neg_n += b.neg_n; a->over_n += b.over_n; mcf_cert_worst(&a->bnd_w, &a->bnd_i, b.bnd_w, b.bnd_i);
+    a->dlo_n += b.dlo_n; mcf_cert_worst(&a->dlo_w, &a->dlo_i, b.dlo_w, b.dlo_i);
+    a->dup_n += b.dup_n; mcf_cert_worst(&a->dup_w, &a->dup_i, b.dup_w, b.dup_i);
+    a->basic_n += b.basic_n; a->stf_n += b.stf_n;
+    a->rc_n += b.rc_n; a->rc_bad += b.rc_bad; a->key_n += b.key_n; a->key_bad += b.key_bad; a->sat_n += b.sat_n;
+    mcf_cert_add128(&a->primal_lo, &a->primal_hi, ((mcf_u128)b.primal_hi << 64) | b.primal_lo);
+    mcf_cert_add128(&a->dcap_lo, &a->dcap_hi, ((mcf_u128)b.dcap_hi << 64) | b.dcap_lo);
+}
+MCF_HD void mcf_cert_node_merge(McfCertNodeAcc* a, const McfCertNodeAcc& b) {
+    a->imb_n += b.imb_n; mcf_cert_worst(&a->imb_w, &a->imb_i, b.imb_w, b.imb_i);
+    a->art_basic += b.art_basic; a->tree_rc_bad += b.tree_rc_bad; a->shape_bad += b.shape_bad; a->strong_bad += b.strong_bad;
+    mcf_cert_add128(&a->art_lo, &a->art_hi, ((mcf_u128)b.art_hi << 64) | b.art_lo);
+    mcf_cert_add128(&a->dnode_lo, &a->dnode_hi, ((mcf_u128)b.dnode_hi << 64) | b.dnode_lo);
+}
+
+// |x| of a 128-bit two's complement value, saturating at INT64_MAX
+MCF_HD int64_t mcf_cert_mag128(__int128 x) {
+    if (x < 0) x = -x;
+    return x > (__int128)INT64_MAX ? INT64_MAX : (int64_t)x;
+}
+
+// flow * den >= cap * num on a capped arc that carries flow: exact, the products are formed in 128 bits (cap < 2^60)
+MCF_HD bool mcf_cert_bottleneck(int64_t cap, int64_t flow, int64_t num, int64_t den) {
+    return cap < MCF_INF && flow > 0 && (__int128)flow * den >= (__int128)cap * num;
+}
+
+// One arc of the primal / dual / objective groups.  idx: the caller's arc index; cap: MCF_INF when uncapacitated;
+// rc = cost + pi[tail] - pi[head].  The two dual classes are those of an optimality proof:
+//   lower:  rc < 0 although the arc could take more flow (uncapacitated, or flow < cap);
+//   upper:  rc > 0 although the arc carries flow (flow > 0).
+MCF_HD void mcf_cert_arc(McfCertArcAcc* a, uint32_t checks, int64_t idx, int64_t cost, int64_t cap, int64_t flow, int64_t rc) {
+    if (checks & MCF_CERT_BOUNDS) {
+        if (flow < 0) { ++a->neg_n; mcf_cert_worst(&a->bnd_w, &a->bnd_i, flow == INT64_MIN ? INT64_MAX : -flow, idx); }
+        else if (cap < MCF_INF && flow > cap) { ++a->over_n; mcf_cert_worst(&a->bnd_w, &a->bnd_i, flow - cap, idx); }
+        if (cap < MCF_INF && flow == cap && flow > 0) ++a->sat_n;
+    }
+    if (checks & MCF_CERT_DUAL) {
+        if (rc < 0 && (cap >= MCF_INF || flow < cap)) { ++a->dlo_n; mcf_cert_worst(&a->dlo_w, &a->dlo_i, -rc, idx); }
+        if (rc > 0 && flow > 0) { ++a->dup_n; mcf_cert_worst(&a->dup_w, &a->dup_i, rc, idx); }
+    }
+    if (checks & MCF_CERT_OBJECTIVES) {
+        mcf_cert_add128(&a->primal_lo, &a->primal_hi, (mcf_u128)((__int128)flow * cost));
+        if (rc < 0 && cap < MCF_INF) mcf_cert_add128(&a->dcap_lo, &a->dcap_hi, (mcf_u128)((__int128)rc * cap));
+    }
+}
+
+// ... and of the resident groups: the arc's state against its flow, the resident reduced cost and key code against
+// what the potentials say (rc_res / key_res: null when the handle keeps none, or not for this arc).
+MCF_HD void mcf_cert_arc_resident(McfCertArcAcc* a, uint32_t checks, int64_t cap, int64_t flow, int64_t rc, int32_t state,
+                                  const int64_t* rc_res, const int32_t* key_res, int64_t bigm, int32_t half) {
+    if (checks & MCF_CERT_BASIS) {
+        if (state == 0) ++a->basic_n;
+        else if (state > 0 ? flow != 0 : (cap >= MCF_INF || flow != cap)) ++a->stf_n;
+    }
+    if (checks & MCF_CERT_PRICING) {
+        if (rc_res) { ++a->rc_n; if (*rc_res != rc) ++a->rc_bad; }
+        if (key_res) { ++a->key_n; if (*key_res != mcf_vkey(-(int64_t)state * rc, bigm, half)) ++a->key_bad; }
+    }
+}
+
+// One node of the conservation group: bal = supply + inflow - outflow (artificial arc included by the caller).
+MCF_HD void mcf_cert_node_balance(McfCertNodeAcc* a, int64_t node, __int128 bal) {
+    if (bal != 0) { ++a->imb_n; mcf_cert_worst(&a->imb_w, &a->imb_i, mcf_cert_mag128(bal), node); }
+}

@@ -2038,6 +2038,269 @@ __global__ __launch_bounds__(kUcThreads) void k_uc_ones(float4* __restrict__ w4,
     for (int64_t i = (int64_t)blockIdx.x * kUcThreads + threadIdx.x; i < n4; i += stride) w4[i] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
 }
 
+// ------------------------------------------------------------------ certificate (mcf_certify / mcf_bottlenecks)
+// k_cert_arcs    ONE streaming pass over the arcs in engine order, workgroup b on head bucket b % 8 like the pricing sweeps
+//                (the two potential gathers of an arc then stay inside one XCD's L2 share): tail, head, cost, orig (4 B
+//                each), the walk record (cap, flow: 16 B), and for the resident groups state (1 B), reduced cost (8 B) and
+//                key code (4 B) -- 32 B per arc for the primal / dual / objective groups, 45 B with everything.  Read once
+//                per call: non-temporal loads from kIncrementalMinArcs arcs on, as for the key-code sweep.
+// k_cert_child   size[v] added to csum[parent[v]] (integer atomics: the sum does not depend on their order).
+// k_cert_nodes   one lane per node: conservation as a gather over the node's adjacency list (128-bit balance), the dual
+//                objective's node term, the artificial arc, and the tree records (mcf_get_tree's view of them).
+// k_cert_final   one workgroup merges the per-workgroup partials.
+// Every partial combines by integer +, max or (max, lowest index) (mcf_core.h), so no merge order can change the result.
+constexpr int kCertThreads = 256;
+constexpr int kCertMaxBlocks = 2048;
+
+struct CertArgs {
+    const int64_t* cflow;     // caller's flows in the caller's order; nullptr = resident
+    const int64_t* pi;        // [n_nodes] potentials, root included (resident, or the caller's with root = 0)
+    const int64_t* supply;    // [n]
+    const int64_t* adj_off;   // full node -> arc adjacency (the handle's, or the certificate's own)
+    const int64_t* adj;
+    const int64_t* rcache;    // resident copies to compare, nullptr = none
+    const int32_t* vkey;
+    int32_t* csum;            // [n_nodes] scratch: sum of the children's sizes
+    uint32_t checks;
+    int32_t resident_flow;
+    int32_t cur, arena;       // which copies of the preorder arrays are current (mcf_get_tree)
+    int32_t partial;          // resident reduced costs / key codes are exact on this rank's shard only
+    int64_t shard, shards;
+    int64_t bigm;
+};
+
+template <bool NT, typename T>
+__device__ __forceinline__ T cert_ld(const T* p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+
+template <typename Acc, int WORDS, typename Merge>
+__device__ __forceinline__ void cert_block_reduce(Acc& acc, Acc* s_wave, Merge merge) {
+    for (int off = 32; off > 0; off >>= 1) {
+        Acc o;
+        unsigned long long* po = reinterpret_cast<unsigned long long*>(&o);
+        const unsigned long long* pa = reinterpret_cast<const unsigned long long*>(&acc);
+#pragma unroll
+        for (int k = 0; k < WORDS; ++k) po[k] = __shfl_down(pa[k], off, 64);
+        if ((int)(threadIdx.x & 63) + off < 64) merge(&acc, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) s_wave[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < kCertThreads / 64; ++w) merge(&acc, s_wave[w]);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kCertThreads) void k_cert_arcs(McfView v, CertArgs a, McfCertArcAcc* __restrict__ part) {
+    __shared__ McfCertArcAcc s_wave[kCertThreads / 64];
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+    int64_t own_lo = lo, own_hi = hi;
+    if (a.partial) mcf_bucket_slice(v.bucket_off, x, a.shard, a.shards, 0, 1, &own_lo, &own_hi);
+    const bool resident = (a.checks & (MCF_CERT_BASIS | MCF_CERT_PRICING)) != 0;
+    McfCertArcAcc acc;
+    mcf_cert_arc_init(&acc);
+    for (int64_t e = lo + lb * kCertThreads + threadIdx.x; e < hi; e += nlb * kCertThreads) {
+        const int32_t t = cert_ld<NT>(v.tail + e), hd = cert_ld<NT>(v.head + e);
+        const int64_t cost = cert_ld<NT>(v.cost + e);
+        const int64_t o = cert_ld<NT>(v.orig + e);
+        const int64_t* aw = reinterpret_cast<const int64_t*>(v.arcw + e);
+        const int64_t cap = cert_ld<NT>(aw);
+        const int64_t flow = a.cflow ? a.cflow[o] : cert_ld<NT>(aw + 1);
+        const int64_t rc = cost + a.pi[t] - a.pi[hd];
+        mcf_cert_arc(&acc, a.checks, o, cost, cap, flow, rc);
+        if (resident) {
+            const int32_t st = cert_ld<NT>(v.state + e);
+            const bool own = e >= own_lo && e < own_hi;
+            int64_t rres = 0;
+            int32_t kres = 0;
+            if (a.rcache && own) rres = cert_ld<NT>(a.rcache + e);
+            if (a.vkey && own) kres = cert_ld<NT>(a.vkey + e);
+            mcf_cert_arc_resident(&acc, a.checks, cap, flow, rc, st, a.rcache && own ? &rres : nullptr, a.vkey && own ? &kres : nullptr,
+                                  v.vk_bigm, v.vk_half);
+        }
+    }
+    cert_block_reduce<McfCertArcAcc, MCF_CERT_ARC_WORDS>(acc, s_wave, [](McfCertArcAcc* p, const McfCertArcAcc& q) { mcf_cert_arc_merge(p, q); });
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_cert_child(McfView v, int32_t* __restrict__ csum) {
+    const int32_t N = v.n_nodes;
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N - 1; u += gridDim.x * kCertThreads) {
+        const McfNode nd = v.node[u];
+        if (nd.parent >= 0 && nd.parent < N) atomicAdd(&csum[nd.parent], nd.size);
+    }
+}
+
+// Preorder position of `node` and the slot that holds it, in the view mcf_get_tree reports (a.cur / a.arena already
+// account for a flip the last update left pending); -1 when a record points outside its array.
+__device__ __forceinline__ int32_t cert_pos(const McfView& v, const CertArgs& a, int32_t node, int32_t* slot) {
+    if (MCF_HAS_BPL(v)) {
+        const int32_t s = v.posbuf[0][node] & MCF_LOC_SLOT;
+        const int32_t b = s >> v.blk_shift;
+        *slot = s;
+        if (b < 0 || b >= v.blk_cap) return -1;
+        const int32_t base = (a.cur ? v.bmeta[1] : v.bmeta[0])[b].base;
+        if (base == MCF_BLK_FREE) return -1;
+        return base + (s & ((1 << v.blk_shift) - 1));
+    }
+    const int32_t p = (a.cur ? v.posbuf[1] : v.posbuf[0])[node];
+    *slot = p;
+    return (p < 0 || p >= v.n_nodes) ? -1 : p;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_cert_nodes(McfView v, CertArgs a, McfCertNodeAcc* __restrict__ part) {
+    __shared__ McfCertNodeAcc s_wave[kCertThreads / 64];
+    const int32_t N = v.n_nodes, root = N - 1;
+    const int64_t m = v.m;
+    const int32_t sel = MCF_HAS_BPL(v) ? a.arena : a.cur;
+    const int32_t* ord = sel ? v.order[1] : v.order[0];
+    const int32_t* psz = sel ? v.psz[1] : v.psz[0];
+    const int64_t pi_root = a.pi[root];
+    McfCertNodeAcc acc;
+    mcf_cert_node_init(&acc);
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
+        const McfNode nd = v.node[u];
+        if (u < root) {
+            const int64_t af = v.arcw[m + u].flow;
+            mcf_cert_add128(&acc.art_lo, &acc.art_hi, (mcf_u128)(__int128)af);
+            if (a.checks & MCF_CERT_CONSERVATION) {
+                // 128 bits: a node may have 2^30 arcs of up to 2^63 each
+                __int128 bal = a.supply[u];
+                for (int64_t k = a.adj_off[u]; k < a.adj_off[u + 1]; ++k) {
+                    const int64_t w = a.adj[k];
+                    const int64_t e = (w & 0xffffffff) >> 1;
+                    const int64_t f = a.cflow ? a.cflow[v.orig[e]] : v.arcw[e].flow;
+                    bal += (w & 1) ? -(__int128)f : (__int128)f;
+                }
+                if (a.resident_flow) {   // the node's artificial arc: node -> root when "up" (a non-basic one carries nothing)
+                    const bool up = (int64_t)(nd.pred >> 1) == m + u ? (nd.pred & 1) != 0 : true;
+                    bal += up ? -(__int128)af : (__int128)af;
+                }
+                mcf_cert_node_balance(&acc, u, bal);
+            }
+            if (a.checks & MCF_CERT_OBJECTIVES)
+                mcf_cert_add128(&acc.dnode_lo, &acc.dnode_hi, (mcf_u128)(-(__int128)(a.pi[u] - pi_root) * a.supply[u]));
+        }
+        if (!(a.checks & MCF_CERT_BASIS)) continue;
+        bool bad = false;
+        int32_t slot = 0;
+        const int32_t pos = cert_pos(v, a, u, &slot);
+        if (pos < 0) bad = true;
+        else {
+            if (ord[slot] != u) bad = true;
+            if (psz && psz[slot] != nd.size) bad = true;
+        }
+        if (nd.size != 1 + a.csum[u]) bad = true;
+        if (u == root) {
+            if (nd.parent != -1 || pos != 0 || nd.size != N || nd.depth != 0) bad = true;
+        } else if (nd.parent < 0 || nd.parent >= N || nd.pred < 0) {
+            bad = true;
+        } else {
+            const int32_t p = nd.parent;
+            const McfNode pn = v.node[p];
+            int32_t pslot = 0;
+            const int32_t ppos = cert_pos(v, a, p, &pslot);
+            if (ppos < 0 || pos < 0 || !(ppos < pos && (int64_t)pos + nd.size <= (int64_t)ppos + pn.size)) bad = true;
+            if (nd.depth != pn.depth + 1) bad = true;
+            const int64_t arc = nd.pred >> 1;
+            const bool up = (nd.pred & 1) != 0;
+            if (arc < m) {
+                const int32_t t = v.tail[arc], hd = v.head[arc];
+                if (up ? (t != u || hd != p) : (hd != u || t != p)) bad = true;
+                if (v.state[arc] != 0) bad = true;
+                if ((int64_t)v.cost[arc] + a.pi[t] - a.pi[hd] != 0) ++acc.tree_rc_bad;
+                const McfArcW w = v.arcw[arc];
+                if ((up && w.cap < MCF_INF && w.flow == w.cap) || (!up && w.flow == 0)) ++acc.strong_bad;
+            } else {
+                if (arc != m + u || p != root) bad = true;
+                if (a.bigm + (up ? a.pi[u] - pi_root : pi_root - a.pi[u]) != 0) ++acc.tree_rc_bad;
+                if (!up && v.arcw[m + u].flow == 0) ++acc.strong_bad;
+                ++acc.art_basic;
+            }
+        }
+        if (bad) ++acc.shape_bad;
+    }
+    cert_block_reduce<McfCertNodeAcc, MCF_CERT_NODE_WORDS>(acc, s_wave, [](McfCertNodeAcc* p, const McfCertNodeAcc& q) { mcf_cert_node_merge(p, q); });
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// part[0 .. n) -> part[n] (arcs and nodes alike)
+__global__ __launch_bounds__(kCertThreads) void k_cert_final(McfCertArcAcc* __restrict__ ap, int na, McfCertNodeAcc* __restrict__ np, int nn) {
+    __shared__ McfCertArcAcc s_a[kCertThreads / 64];
+    __shared__ McfCertNodeAcc s_n[kCertThreads / 64];
+    McfCertArcAcc a;
+    McfCertNodeAcc n;
+    mcf_cert_arc_init(&a);
+    mcf_cert_node_init(&n);
+    for (int i = threadIdx.x; i < na; i += kCertThreads) mcf_cert_arc_merge(&a, ap[i]);
+    for (int i = threadIdx.x; i < nn; i += kCertThreads) mcf_cert_node_merge(&n, np[i]);
+    cert_block_reduce<McfCertArcAcc, MCF_CERT_ARC_WORDS>(a, s_a, [](McfCertArcAcc* p, const McfCertArcAcc& q) { mcf_cert_arc_merge(p, q); });
+    cert_block_reduce<McfCertNodeAcc, MCF_CERT_NODE_WORDS>(n, s_n, [](McfCertNodeAcc* p, const McfCertNodeAcc& q) { mcf_cert_node_merge(p, q); });
+    if (threadIdx.x == 0) { ap[na] = a; np[nn] = n; }
+}
+
+// ---- bottleneck arcs, compacted in ascending caller's index: flag per caller's index (scatter from the engine-order
+// stream), count per chunk, exclusive scan of the chunk counts by one workgroup, write.
+constexpr int kBnChunk = 4096;   // caller's indices per workgroup: 16 rounds of 256
+__global__ __launch_bounds__(kCertThreads) void k_bn_flag(McfView v, const int64_t* __restrict__ cflow, int64_t num, int64_t den,
+                                                          uint8_t* __restrict__ flag) {
+    for (int64_t e = (int64_t)blockIdx.x * kCertThreads + threadIdx.x; e < v.m; e += (int64_t)gridDim.x * kCertThreads) {
+        const McfArcW w = v.arcw[e];
+        const int32_t o = v.orig[e];
+        flag[o] = mcf_cert_bottleneck(w.cap, cflow ? cflow[o] : w.flow, num, den) ? 1 : 0;
+    }
+}
+__global__ __launch_bounds__(kCertThreads) void k_bn_count(const uint8_t* __restrict__ flag, int64_t m, int32_t* __restrict__ cnt) {
+    __shared__ int32_t s[kCertThreads / 64];
+    const int64_t base = (int64_t)blockIdx.x * kBnChunk;
+    int32_t c = 0;
+    for (int r = 0; r < kBnChunk / kCertThreads; ++r) {
+        const int64_t i = base + r * kCertThreads + threadIdx.x;
+        if (i < m && flag[i]) ++c;
+    }
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+}
+__global__ __launch_bounds__(1024) void k_bn_scan(const int32_t* __restrict__ cnt, int64_t nb, int64_t* __restrict__ off) {
+    __shared__ int64_t s[1024];
+    const int64_t per = (nb + 1023) / 1024, lo = threadIdx.x * per < nb ? threadIdx.x * per : nb, hi = lo + per < nb ? lo + per : nb;
+    int64_t sum = 0;
+    for (int64_t b = lo; b < hi; ++b) sum += cnt[b];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t run = 0;
+        for (int k = 0; k < 1024; ++k) { const int64_t x = s[k]; s[k] = run; run += x; }
+        off[nb] = run;   // the total
+    }
+    __syncthreads();
+    int64_t run = s[threadIdx.x];
+    for (int64_t b = lo; b < hi; ++b) { off[b] = run; run += cnt[b]; }
+}
+__global__ __launch_bounds__(kCertThreads) void k_bn_write(const uint8_t* __restrict__ flag, int64_t m, const int64_t* __restrict__ off,
+                                                           int64_t* __restrict__ idx, int64_t idx_cap) {
+    __shared__ int32_t s[kCertThreads / 64];
+    const int64_t base = (int64_t)blockIdx.x * kBnChunk;
+    int64_t run = off[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = 0; r < kBnChunk / kCertThreads; ++r) {
+        const int64_t i = base + r * kCertThreads + threadIdx.x;
+        const bool f = i < m && flag[i];
+        const uint64_t mask = __ballot(f);
+        if (lane == 0) s[wave] = __popcll(mask);
+        __syncthreads();
+        int64_t before = run;
+        for (int w = 0; w < wave; ++w) before += s[w];
+        const int64_t at = before + __popcll(mask & (((uint64_t)1 << lane) - 1));
+        if (f && at < idx_cap) idx[at] = i;
+        run += s[0] + s[1] + s[2] + s[3];
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 // ====================================================================== handle
@@ -2130,6 +2393,19 @@ struct mcf_handle {
     int64_t uc_cap = 0;              // entries the two arrays hold
     McfJump* d_uc_jump[2] = {nullptr, nullptr};          // pointer-jumping records, double buffered
     int32_t* d_uc_info = nullptr;    // [0] greatest depth of the tree, [1] basic arcs among the changes
+    // mcf_certify / mcf_bottlenecks: everything allocated on first use
+    int64_t* d_ct_supply = nullptr;                        // [n]
+    int64_t *d_ct_adj_off = nullptr, *d_ct_adj = nullptr;  // full adjacency, where the handle holds none or its shard's only
+    int64_t *d_ct_flow = nullptr, *d_ct_pi = nullptr;      // the caller's arrays
+    McfCertArcAcc* d_ct_arc = nullptr;                     // [kCertMaxBlocks + 1] per-workgroup partials, then the total
+    McfCertNodeAcc* d_ct_node = nullptr;
+    int32_t* d_ct_csum = nullptr;                          // [n_nodes]
+    hipEvent_t ct_ev[3] = {nullptr, nullptr, nullptr};
+    uint8_t* d_bn_flag = nullptr;                          // [m] bottleneck flag per caller's arc index
+    int32_t* d_bn_cnt = nullptr;                           // per chunk of caller's indices
+    int64_t* d_bn_off = nullptr;
+    int64_t* d_bn_idx = nullptr;
+    int64_t bn_idx_cap = 0;
 };
 
 namespace {
@@ -2558,10 +2834,71 @@ void free_all(mcf_handle* h) {
     (void)hipFree(h->d_pos0); (void)hipFree(h->d_pos1); (void)hipFree(h->d_psz0); (void)hipFree(h->d_psz1); (void)hipFree(h->d_reach); (void)hipFree(h->d_chg); (void)hipFree(h->d_dirty); (void)hipFree(h->d_swept); (void)hipFree(h->d_dx); (void)hipFree(h->d_full_tab);
     (void)hipFree(h->d_rcache); (void)hipFree(h->d_adj_off); (void)hipFree(h->d_adj); (void)hipFree(h->d_vkey); (void)hipFree(h->d_candx);
     for (int a = 0; a < 2; ++a) { (void)hipFree(h->d_bmeta[a]); (void)hipFree(h->d_bext[a]); }
+    (void)hipFree(h->d_ct_supply); (void)hipFree(h->d_ct_adj_off); (void)hipFree(h->d_ct_adj); (void)hipFree(h->d_ct_flow); (void)hipFree(h->d_ct_pi);
+    (void)hipFree(h->d_ct_arc); (void)hipFree(h->d_ct_node); (void)hipFree(h->d_ct_csum);
+    (void)hipFree(h->d_bn_flag); (void)hipFree(h->d_bn_cnt); (void)hipFree(h->d_bn_off); (void)hipFree(h->d_bn_idx);
+    for (hipEvent_t e : h->ct_ev) if (e) (void)hipEventDestroy(e);
     (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost); (void)hipFree(h->d_uc_jump[0]); (void)hipFree(h->d_uc_jump[1]); (void)hipFree(h->d_uc_info);
     if (h->h_ctx) pinned_give(reinterpret_cast<char*>(h->h_ctx));   // (h_one lives in the same slot)
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
 }
+
+// ---- certificate on the device: host helpers
+// the caller's flows (caller's order, as they are) into the scratch buffer; nullptr stays nullptr
+int cert_upload_flow(mcf_handle* h, const int64_t* flow, const int64_t** dev) {
+    *dev = nullptr;
+    if (!flow || h->im.m == 0) return MCF_OK;
+    if (!h->d_ct_flow && dalloc(&h->d_ct_flow, (size_t)h->im.m) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc certificate flows"; return MCF_E_ALLOC; }
+    HIP_TRY(h, hipMemcpyAsync(h->d_ct_flow, flow, (size_t)h->im.m * 8, hipMemcpyHostToDevice, h->stream));
+    *dev = h->d_ct_flow;
+    return MCF_OK;
+}
+
+// (lazy scratch is allocated in groups; a group that could not be completed is given back whole)
+template <typename T> void cert_free(T** p) { (void)hipFree(*p); *p = nullptr; }
+
+// what the certificate needs beyond the solver's arrays: supplies, a FULL adjacency, partial buffers, events
+int cert_prepare(mcf_handle* h) {
+    const McfHostImage& im = h->im;
+    if (!h->d_ct_supply) {
+        if (dalloc(&h->d_ct_supply, (size_t)im.n) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc supplies"; return MCF_E_ALLOC; }
+        if (hipMemcpy(h->d_ct_supply, im.supply.data(), (size_t)im.n * 8, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError(); cert_free(&h->d_ct_supply); h->err = "hipMemcpy supplies"; return MCF_E_HIP;
+        }
+    }
+    const bool own_adj = h->d_adj && !h->view.rc_partial;   // (h->view.adj goes away with dropped reduced costs; the arrays stay)
+    if (!own_adj && !h->d_ct_adj_off) {
+        std::vector<int64_t> off((size_t)im.n + 1, 0), adj((size_t)(2 * im.m));
+        for (int64_t e = 0; e < im.m; ++e) { off[(size_t)im.tail[e] + 1]++; off[(size_t)im.head[e] + 1]++; }
+        for (int32_t u = 0; u < im.n; ++u) off[(size_t)u + 1] += off[u];
+        std::vector<int64_t> fill(off.begin(), off.end() - 1);
+        for (int64_t e = 0; e < im.m; ++e) {
+            const int64_t t = im.tail[e], hd = im.head[e];
+            adj[(size_t)fill[t]++] = (hd << 32) | (e << 1) | 1;
+            adj[(size_t)fill[hd]++] = (t << 32) | (e << 1);
+        }
+        // a group is complete or absent: the guard above looks at its first pointer only
+        if (dalloc(&h->d_ct_adj_off, off.size()) != hipSuccess || dalloc(&h->d_ct_adj, adj.size()) != hipSuccess) {
+            (void)hipGetLastError(); cert_free(&h->d_ct_adj_off); cert_free(&h->d_ct_adj);
+            h->err = "hipMalloc certificate adjacency"; return MCF_E_ALLOC;
+        }
+        if (hipMemcpy(h->d_ct_adj_off, off.data(), off.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            (!adj.empty() && hipMemcpy(h->d_ct_adj, adj.data(), adj.size() * 8, hipMemcpyHostToDevice) != hipSuccess)) {
+            (void)hipGetLastError(); cert_free(&h->d_ct_adj_off); cert_free(&h->d_ct_adj);
+            h->err = "hipMemcpy certificate adjacency"; return MCF_E_HIP;
+        }
+    }
+    if (!h->d_ct_arc) {
+        if (dalloc(&h->d_ct_arc, kCertMaxBlocks + 1) != hipSuccess || dalloc(&h->d_ct_node, kCertMaxBlocks + 1) != hipSuccess ||
+            dalloc(&h->d_ct_csum, (size_t)im.n_nodes) != hipSuccess) {
+            (void)hipGetLastError(); cert_free(&h->d_ct_arc); cert_free(&h->d_ct_node); cert_free(&h->d_ct_csum);
+            h->err = "hipMalloc certificate partials"; return MCF_E_ALLOC;
+        }
+    }
+    for (hipEvent_t& e : h->ct_ev) if (!e) HIP_TRY(h, hipEventCreate(&e));
+    return MCF_OK;
+}
+
 
 }  // namespace
 
@@ -3750,6 +4087,146 @@ int mcf_get_weights(mcf_handle* h, float* weight_out) {
     std::vector<float> w(im.m_pad);
     HIP_TRY(h, hipMemcpy(w.data(), h->d_weight, w.size() * 4, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < im.m; ++i) weight_out[im.orig[i]] = w[i];
+    return MCF_OK;
+}
+
+// ---- certificate on the device (include/mcf.h)
+int mcf_certify(mcf_handle* h, const int64_t* flow, const int64_t* potential, uint32_t checks, mcf_certificate* out) {
+    if (!h || !out || (checks & ~MCF_CERT_ALL)) return MCF_E_BAD_ARG;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    const McfHostImage& im = h->im;
+    if (!checks) checks = MCF_CERT_ALL;
+    if (flow || potential) checks &= ~(MCF_CERT_BASIS | MCF_CERT_PRICING);
+    std::vector<int64_t> pi_host;   // (outlives the asynchronous copy: the call ends with a synchronisation)
+    if (potential) {
+        pi_host.assign((size_t)im.n_nodes, 0);
+        for (int32_t v = 0; v < im.n; ++v) {
+            if (potential[v] > ((int64_t)1 << 61) || potential[v] < -((int64_t)1 << 61)) { h->err = "mcf_certify: |potential| must not exceed 2^61"; return MCF_E_RANGE; }
+            pi_host[(size_t)v] = potential[v];
+        }
+    }
+    if ((rc = cert_prepare(h)) != MCF_OK) return rc;
+    CertArgs a;
+    std::memset(&a, 0, sizeof a);
+    if ((rc = cert_upload_flow(h, flow, &a.cflow)) != MCF_OK) return rc;
+    a.pi = h->d_pi;
+    if (potential) {
+        if (!h->d_ct_pi && dalloc(&h->d_ct_pi, (size_t)im.n_nodes) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc certificate potentials"; return MCF_E_ALLOC; }
+        HIP_TRY(h, hipMemcpyAsync(h->d_ct_pi, pi_host.data(), pi_host.size() * 8, hipMemcpyHostToDevice, h->stream));
+        a.pi = h->d_ct_pi;
+    }
+    const bool own_adj = h->d_adj && !h->view.rc_partial;
+    a.supply = h->d_ct_supply;
+    a.adj_off = own_adj ? h->d_adj_off : h->d_ct_adj_off;
+    a.adj = own_adj ? h->d_adj : h->d_ct_adj;
+    a.rcache = (checks & MCF_CERT_PRICING) && h->rcached ? h->d_rcache : nullptr;
+    a.vkey = (checks & MCF_CERT_PRICING) && h->rcached ? h->view.vkey : nullptr;
+    a.csum = h->d_ct_csum;
+    a.checks = checks;
+    a.resident_flow = flow ? 0 : 1;
+    a.cur = h->h_ctx->cur ^ (h->h_ctx->pending_flip ? 1 : 0);                                   // as mcf_get_tree reads the arrays
+    a.arena = h->h_ctx->arena ^ ((h->h_ctx->pending_flip && h->h_ctx->rebuild) ? 1 : 0);
+    a.partial = h->view.rc_partial;
+    a.shard = h->shard; a.shards = h->shards;
+    a.bigm = im.big_m;
+    const int ab = mcf_price_blocks(im.m, 1, 0);
+    int64_t nb64 = ((int64_t)im.n_nodes + kCertThreads - 1) / kCertThreads;
+    const int nb = (int)(nb64 < kCertMaxBlocks ? nb64 : kCertMaxBlocks);
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
+    if (im.m >= kIncrementalMinArcs) hipLaunchKernelGGL(k_cert_arcs<true>, dim3(ab), dim3(kCertThreads), 0, s, h->view, a, h->d_ct_arc);
+    else hipLaunchKernelGGL(k_cert_arcs<false>, dim3(ab), dim3(kCertThreads), 0, s, h->view, a, h->d_ct_arc);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+    if (checks & MCF_CERT_BASIS) {
+        HIP_TRY(h, hipMemsetAsync(h->d_ct_csum, 0, (size_t)im.n_nodes * 4, s));
+        hipLaunchKernelGGL(k_cert_child, dim3(nb), dim3(kCertThreads), 0, s, h->view, h->d_ct_csum);
+    }
+    hipLaunchKernelGGL(k_cert_nodes, dim3(nb), dim3(kCertThreads), 0, s, h->view, a, h->d_ct_node);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[2], s));
+    hipLaunchKernelGGL(k_cert_final, dim3(1), dim3(kCertThreads), 0, s, h->d_ct_arc, ab, h->d_ct_node, nb);
+    HIP_TRY(h, hipGetLastError());
+    McfCertArcAcc A;
+    McfCertNodeAcc N;
+    HIP_TRY(h, hipMemcpyAsync(&A, h->d_ct_arc + ab, sizeof A, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(&N, h->d_ct_node + nb, sizeof N, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    float ms_a = 0, ms_n = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms_a, h->ct_ev[0], h->ct_ev[1]));
+    HIP_TRY(h, hipEventElapsedTime(&ms_n, h->ct_ev[1], h->ct_ev[2]));
+
+    mcf_certificate c;
+    std::memset(&c, 0, sizeof c);
+    auto idx = [](int64_t i) { return i == MCF_CERT_NONE ? (int64_t)-1 : i; };
+    auto put = [](int64_t* hi_lo, __int128 x) { hi_lo[0] = (int64_t)(x >> 64); hi_lo[1] = (int64_t)(uint64_t)x; };
+    c.checks = checks;
+    c.negative_flow_count = A.neg_n; c.over_capacity_count = A.over_n; c.bounds_worst = A.bnd_w; c.bounds_worst_arc = idx(A.bnd_i);
+    c.imbalance_count = N.imb_n; c.imbalance_worst = N.imb_w; c.imbalance_worst_node = idx(N.imb_i);
+    c.dual_lower_count = A.dlo_n; c.dual_lower_worst = A.dlo_w; c.dual_lower_arc = idx(A.dlo_i);
+    c.dual_upper_count = A.dup_n; c.dual_upper_worst = A.dup_w; c.dual_upper_arc = idx(A.dup_i);
+    const int64_t art_resident = (int64_t)N.art_lo;   // (below 2^60: "Numeric domain")
+    c.artificial_flow = flow ? 0 : art_resident;
+    c.big_m = im.big_m;
+    const __int128 primal = (__int128)(((mcf_u128)A.primal_hi << 64) | A.primal_lo);
+    const __int128 bigm_term = (__int128)c.big_m * c.artificial_flow;
+    const __int128 dual = (__int128)((((mcf_u128)N.dnode_hi << 64) | N.dnode_lo) + (((mcf_u128)A.dcap_hi << 64) | A.dcap_lo));
+    const __int128 gap = primal + bigm_term - dual;
+    if (checks & MCF_CERT_OBJECTIVES) { put(c.primal, primal); put(c.bigm_term, bigm_term); put(c.dual, dual); put(c.gap, gap); }
+    c.basic_arcs = A.basic_n + N.art_basic;
+    c.basic_count_mismatch = (checks & MCF_CERT_BASIS) && c.basic_arcs != im.n ? 1 : 0;
+    c.tree_rc_count = N.tree_rc_bad; c.state_flow_count = A.stf_n; c.tree_shape_count = N.shape_bad; c.strong_count = N.strong_bad;
+    c.rc_compared = A.rc_n; c.rc_mismatch_count = A.rc_bad; c.key_compared = A.key_n; c.key_mismatch_count = A.key_bad;
+    c.saturated_arcs = A.sat_n;
+    c.arc_pass_ms = ms_a; c.node_pass_ms = ms_n;
+    const int32_t st = h->h_ctx->status;
+    c.status = st == MCF_RUNNING ? -1 : st == MCF_UNBOUNDED ? MCF_ST_UNBOUNDED
+               : st == MCF_OPTIMAL ? (art_resident > 0 ? MCF_ST_INFEASIBLE : MCF_ST_OPTIMAL) : MCF_ST_ITERATION_LIMIT;
+    const uint32_t need = MCF_CERT_BOUNDS | MCF_CERT_CONSERVATION | MCF_CERT_DUAL | MCF_CERT_OBJECTIVES;
+    c.verdict = MCF_CERT_NOT_PROVEN;
+    if ((checks & need) == need && !A.neg_n && !A.over_n && !N.imb_n && !A.dlo_n && !A.dup_n && gap == 0)
+        c.verdict = c.artificial_flow > 0 ? MCF_CERT_INFEASIBLE : MCF_CERT_OPTIMAL;
+    c.proves_status = (c.status == MCF_ST_OPTIMAL && c.verdict == MCF_CERT_OPTIMAL) || (c.status == MCF_ST_INFEASIBLE && c.verdict == MCF_CERT_INFEASIBLE) ? 1 : 0;
+    *out = c;
+    return MCF_OK;
+}
+
+int mcf_bottlenecks(mcf_handle* h, const int64_t* flow, int64_t num, int64_t den, int64_t* idx_out, int64_t idx_cap, int64_t* count) {
+    if (!h || !count || num < 0 || den <= 0 || idx_cap < 0 || (idx_cap > 0 && !idx_out)) return MCF_E_BAD_ARG;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const McfHostImage& im = h->im;
+    *count = 0;
+    if (im.m == 0) return MCF_OK;
+    const int64_t nb = (im.m + kBnChunk - 1) / kBnChunk;
+    if (!h->d_bn_flag) {
+        if (dalloc(&h->d_bn_flag, (size_t)im.m) != hipSuccess || dalloc(&h->d_bn_cnt, (size_t)nb) != hipSuccess || dalloc(&h->d_bn_off, (size_t)nb + 1) != hipSuccess) {
+            (void)hipGetLastError(); cert_free(&h->d_bn_flag); cert_free(&h->d_bn_cnt); cert_free(&h->d_bn_off);
+            h->err = "hipMalloc bottleneck scratch"; return MCF_E_ALLOC;
+        }
+    }
+    const int64_t want = idx_cap < im.m ? idx_cap : im.m;
+    if (want > h->bn_idx_cap) {
+        (void)hipFree(h->d_bn_idx); h->d_bn_idx = nullptr; h->bn_idx_cap = 0;
+        if (dalloc(&h->d_bn_idx, (size_t)want) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc bottleneck indices"; return MCF_E_ALLOC; }
+        h->bn_idx_cap = want;
+    }
+    const int64_t* cflow = nullptr;
+    int rc = cert_upload_flow(h, flow, &cflow);
+    if (rc) return rc;
+    hipStream_t s = h->stream;
+    int64_t fb = (im.m + kCertThreads - 1) / kCertThreads;
+    if (fb > kCertMaxBlocks) fb = kCertMaxBlocks;
+    hipLaunchKernelGGL(k_bn_flag, dim3((unsigned)fb), dim3(kCertThreads), 0, s, h->view, cflow, num, den, h->d_bn_flag);
+    hipLaunchKernelGGL(k_bn_count, dim3((unsigned)nb), dim3(kCertThreads), 0, s, h->d_bn_flag, im.m, h->d_bn_cnt);
+    hipLaunchKernelGGL(k_bn_scan, dim3(1), dim3(1024), 0, s, h->d_bn_cnt, nb, h->d_bn_off);
+    if (want > 0) hipLaunchKernelGGL(k_bn_write, dim3((unsigned)nb), dim3(kCertThreads), 0, s, h->d_bn_flag, im.m, h->d_bn_off, h->d_bn_idx, want);
+    HIP_TRY(h, hipGetLastError());
+    int64_t total = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, h->d_bn_off + nb, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *count = total;
+    const int64_t got = total < want ? total : want;
+    if (got > 0) HIP_TRY(h, hipMemcpy(idx_out, h->d_bn_idx, (size_t)got * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 

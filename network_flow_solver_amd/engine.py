@@ -32,7 +32,11 @@ ABI_SYMBOLS = (
     "mcf_default_options", "mcf_create", "mcf_solve", "mcf_solve_batch", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs",
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
+    "mcf_certify", "mcf_bottlenecks",
 )
+# mcf_certify: check groups and verdicts (include/mcf.h)
+CERT_BOUNDS, CERT_CONSERVATION, CERT_DUAL, CERT_OBJECTIVES, CERT_BASIS, CERT_PRICING = 1, 2, 4, 8, 16, 32
+CERT_VERDICTS = {0: "not_proven", 1: "optimal", 2: "infeasible"}
 
 
 class EngineUnavailableError(NetworkSolverError):
@@ -80,6 +84,30 @@ class McfStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class McfCertificate(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "checks", "status", "verdict", "proves_status",
+        "negative_flow_count", "over_capacity_count", "bounds_worst", "bounds_worst_arc",
+        "imbalance_count", "imbalance_worst", "imbalance_worst_node",
+        "dual_lower_count", "dual_lower_worst", "dual_lower_arc", "dual_upper_count", "dual_upper_worst", "dual_upper_arc")] + [
+        ("primal", ctypes.c_int64 * 2), ("bigm_term", ctypes.c_int64 * 2), ("dual", ctypes.c_int64 * 2), ("gap", ctypes.c_int64 * 2)] + [
+        (name, ctypes.c_int64) for name in (
+        "artificial_flow", "big_m", "basic_arcs", "basic_count_mismatch", "tree_rc_count", "state_flow_count", "tree_shape_count",
+        "strong_count", "rc_compared", "rc_mismatch_count", "key_compared", "key_mismatch_count", "saturated_arcs")] + [
+        ("arc_pass_ms", ctypes.c_double), ("node_pass_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        """Plain values: 128-bit sums as Python ints, status / verdict as strings."""
+        d = {}
+        for name, t in self._fields_:
+            v = getattr(self, name)
+            d[name] = (int(v[0]) << 64) + (int(v[1]) & ((1 << 64) - 1)) if t is ctypes.c_int64 * 2 else v
+        d["status"] = "running" if self.status < 0 else STATUS_NAMES[int(self.status)]
+        d["verdict"] = CERT_VERDICTS[int(self.verdict)]
+        d["proves_status"] = bool(self.proves_status)
+        return d
+
+
 PROGRESS_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double)
 
 _lib = None
@@ -123,6 +151,8 @@ def load_library():
     lib.mcf_get_reduced_costs.argtypes = [vp, i64p, i32p]
     lib.mcf_get_weights.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     lib.mcf_get_pricing_keys.argtypes = [vp, i32p, i32p]
+    lib.mcf_certify.argtypes = [vp, i64p, i64p, ctypes.c_uint32, ctypes.POINTER(McfCertificate)]
+    lib.mcf_bottlenecks.argtypes = [vp, i64p, ctypes.c_int64, ctypes.c_int64, i64p, ctypes.c_int64, i64p]
     lib.mcf_dimacs_scan.argtypes = [ctypes.c_char_p, i64p, i64p, ctypes.c_char_p, ctypes.c_int32]
     lib.mcf_dimacs_load.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, i32p, i32p, i64p, i64p, i64p, i64p,
                                     ctypes.c_char_p, ctypes.c_int32]
@@ -132,7 +162,8 @@ def load_library():
     lib.mcf_destroy.restype = None
     for name in ("mcf_create", "mcf_solve", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs", "mcf_enqueue_price",
                  "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing", "mcf_time_copy",
-                 "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load"):
+                 "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load",
+                 "mcf_certify", "mcf_bottlenecks"):
         getattr(lib, name).restype = ctypes.c_int
     if lib.mcf_abi_version() != ABI_VERSION:
         raise EngineUnavailableError("libmcf_hip.so ABI version mismatch")
@@ -373,6 +404,36 @@ class McfEngine:
         w = np.ones(max(self.m, 1), dtype=np.float32)
         self._check(self._lib.mcf_get_weights(self._h, _p(w, ctypes.c_float)))
         return w[: self.m]
+
+    # -- certificate on the device
+    def certify(self, flow=None, potential=None, checks: int = 0) -> dict:
+        """Conservation, bounds, complementary slackness, exact objectives and -- for the resident state -- the consistency of
+        the basis and of the resident pricing data, evaluated on the device (``mcf_certify``).  ``flow`` (one per arc) and
+        ``potential`` (one per node) default to the handle's resident arrays; given, they are certified against this
+        instance.  Read-only.  Returns the fields of ``mcf_certificate`` with 128-bit sums as Python ints."""
+        f = None if flow is None else np.ascontiguousarray(flow, dtype=np.int64)
+        p = None if potential is None else np.ascontiguousarray(potential, dtype=np.int64)
+        if (f is not None and f.shape[0] != self.m) or (p is not None and p.shape[0] != self.n):
+            raise ValueError("flow needs one entry per arc, potential one per node")
+        if f is not None and self.m == 0:
+            f = np.zeros(1, dtype=np.int64)
+        cert = McfCertificate()
+        self._check(self._lib.mcf_certify(self._h, None if f is None else _p(f, ctypes.c_int64),
+                                          None if p is None else _p(p, ctypes.c_int64), int(checks), ctypes.byref(cert)))
+        return cert.as_dict()
+
+    def bottlenecks(self, num: int = 1, den: int = 1, flow=None, limit: int | None = None):
+        """(indices, count): the capped arcs carrying flow with ``flow * den >= cap * num``, exact, compacted on the device in
+        ascending arc index (``mcf_bottlenecks``); at most ``limit`` indices (default: all)."""
+        f = None if flow is None else np.ascontiguousarray(flow, dtype=np.int64)
+        if f is not None and f.shape[0] != self.m:
+            raise ValueError("flow needs one entry per arc")
+        cap = self.m if limit is None else max(0, min(int(limit), self.m))
+        idx = np.zeros(max(cap, 1), dtype=np.int64)
+        count = ctypes.c_int64(0)
+        self._check(self._lib.mcf_bottlenecks(self._h, None if f is None or self.m == 0 else _p(f, ctypes.c_int64), int(num), int(den),
+                                              _p(idx, ctypes.c_int64), cap, ctypes.byref(count)))
+        return idx[: min(cap, int(count.value))], int(count.value)
 
     # -- measurement
     def time_pricing(self, reps: int = 20, rule: int | None = None) -> float:

@@ -247,6 +247,30 @@ def map_cost_changes(flat: FlatProblem, changes, tolerance: float) -> tuple[np.n
     return idx, rounded.astype(np.int64), values
 
 
+@dataclass
+class Certificate:
+    """What ``NetworkSimplex.certify()`` returns; ``raw`` holds every field of ``mcf_certificate``."""
+
+    verdict: str                     # "optimal" / "infeasible" / "not_proven": what the evidence proves (see certify() on "infeasible")
+    status: str                      # the handle's solve status ("running" before a solve)
+    proves_status: bool
+    primal_objective: int            # exact, in flow_scale x cost_scale units
+    big_m_term: int
+    dual_objective: int
+    gap: int
+    artificial_flow: int
+    flow_scale: int
+    cost_scale: int
+    bound_violations: int
+    worst_bound_arc: tuple[str, str] | None
+    imbalanced_nodes: int
+    worst_imbalance_node: str | None
+    dual_violations: int
+    worst_dual_arc: tuple[str, str] | None
+    basis_inconsistencies: int
+    raw: dict
+
+
 class NetworkSimplex:
     """Network simplex solver for minimum-cost flow, pivoting on an MI355X.
 
@@ -396,6 +420,31 @@ class NetworkSimplex:
             self.problem = replace(self.problem, nodes=dict(self.problem.nodes), arcs=arcs)
             self.flat = replace(f, cost=new_cost, orig_cost=orig_cost)
         return int(idx.shape[0])
+
+    def certify(self) -> "Certificate":
+        """Certify the state resident on the device -- conservation, bounds, complementary slackness, exact objectives,
+        consistency of the basis -- without downloading it (``mcf_certify``).  Objectives are exact Python ints in the
+        engine's integer units (flow scale x cost scale, lower bounds shifted out); offenders are mapped back to
+        ``(tail, head)`` keys and node ids.
+
+        The verdict "infeasible" is weaker than "optimal": the dual groups cover the real arcs only, so it says that the
+        state is optimal for the big-M problem restricted to the artificial arcs still in the basis (those carrying the
+        remaining flow); the reduced costs of artificial arcs that have left the basis are not examined."""
+        f = self.flat
+        c = self.engine.certify()
+        arc = lambda i: f.keys[i] if 0 <= i < len(f.keys) else None
+        return Certificate(
+            verdict=c["verdict"], status=c["status"], proves_status=c["proves_status"],
+            primal_objective=c["primal"], big_m_term=c["bigm_term"], dual_objective=c["dual"], gap=c["gap"],
+            artificial_flow=c["artificial_flow"], flow_scale=f.flow_scale, cost_scale=f.cost_scale,
+            bound_violations=c["negative_flow_count"] + c["over_capacity_count"], worst_bound_arc=arc(c["bounds_worst_arc"]),
+            imbalanced_nodes=c["imbalance_count"],
+            worst_imbalance_node=f.node_ids[c["imbalance_worst_node"]] if 0 <= c["imbalance_worst_node"] < len(f.node_ids) else None,
+            dual_violations=c["dual_lower_count"] + c["dual_upper_count"],
+            worst_dual_arc=arc(c["dual_lower_arc"] if c["dual_lower_worst"] >= c["dual_upper_worst"] else c["dual_upper_arc"]),
+            basis_inconsistencies=sum(c[k] for k in ("basic_count_mismatch", "tree_rc_count", "state_flow_count", "tree_shape_count",
+                                                     "strong_count", "rc_mismatch_count", "key_mismatch_count")),
+            raw=c)
 
     def _objective_estimate(self, flow: np.ndarray) -> float:
         f = self.flat

@@ -41,6 +41,10 @@ dt = time.time() - t0
 print(f"status={res.status} pivots={res.stats['pivots']} seconds={dt:.1f} pivots/s={res.stats['pivots'] / dt:.0f} objective={res.objective} "
       f"artificial_flow={res.stats['artificial_flow']} degenerate={res.stats['degenerate']} tree_blocks={res.stats['tree_blocks']} "
       f"rebuilds={res.stats['tree_rebuilds']} rc_dropped_at={res.stats['rc_dropped_at']} moved/subtree={res.stats['nodes_moved'] / max(res.stats['subtree_nodes'], 1):.2f}", flush=True)
+t0 = time.time()
+cert = eng.certify()
+print(f"device certificate: verdict={cert['verdict']} proves_status={cert['proves_status']} primal={cert['primal']} gap={cert['gap']} "
+      f"in {(time.time() - t0) * 1e3:.1f} ms (arc pass {cert['arc_pass_ms'] * 1e3:.0f} us, node pass {cert['node_pass_ms'] * 1e3:.0f} us)", flush=True)
 if res.status == "optimal":
     from conftest import check_optimality
     check_optimality(inst, res.flow, res.potential)
