@@ -21,6 +21,9 @@
  *   solving again after arc costs changed: the reference builds a new NetworkSimplex
  *       from the edited problem and passes solve(warm_start_basis=...)
  *       simplex.py:99-265, 1491-1532 .........................................  mcf_update_costs (the resident basis stays)
+ *   solving again after supplies / demands / capacities changed: the reference builds a new NetworkSimplex from the edited
+ *       problem and passes solve(warm_start_basis=...), which recomputes the tree flows and falls back to the cold start
+ *       when one of them leaves its bounds  simplex.py:99-265, 905-1010, 1491-1532 ...  mcf_update_rhs (the resident basis stays or is repaired)
  *   validate_flow / compute_bottleneck_arcs  utils.py:169-312 (conservation, bounds, arcs
  *       near capacity of a solution; the reference checks nothing on the dual side) ......  mcf_certify / mcf_bottlenecks
  *   AdaptiveTuner.adapt_block_size  simplex_adaptive.py:98-151 and the
@@ -232,7 +235,7 @@ int mcf_create(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, c
  * the reference's default budget max(100, 20 * (m + n)), simplex.py:1470).
  * A verdict is final: on a handle whose status is already optimal, infeasible or unbounded the call is a no-op that makes no
  * pivot and leaves status, counters (mcf_stats.pivots, unbounded_arc, ...) and every array as they are; only an iteration
- * limit is resumed.  mcf_reset, mcf_set_basis and mcf_update_costs are what put such a handle back to "running". */
+ * limit is resumed.  mcf_reset, mcf_set_basis, mcf_update_costs and mcf_update_rhs are what put such a handle back to "running". */
 int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user, int64_t cb_interval);
 
 /* Solve `count` INDEPENDENT instances side by side: one persistent workgroup (one CU) per handle, each running its whole
@@ -295,6 +298,58 @@ int mcf_set_basis(mcf_handle* h, const int8_t* in_tree, const int8_t* at_upper);
  *              block cursor and the block-size tuner are at their start values.  A later mcf_reset / mcf_set_basis and
  *              the objective of mcf_get_result use the new costs. */
 int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int64_t* new_cost);
+
+/* Re-optimise after supplies / demands and arc capacities changed: node[i] now supplies new_supply[i], arc[i] (caller's arc
+ * index) now has capacity new_cap[i] (mcf_create's convention: < 0 or >= 2^60 = uncapacitated); both kinds of change in one
+ * call, so that a combined edit is one pass.  It replaces the reference's only way to do this -- a new NetworkSimplex from
+ * the edited problem plus solve(warm_start_basis=...), simplex.py:99-265, 905-1010, 1491-1532, which uploads nothing because
+ * it has nothing resident, walks the tree on the host and drops the basis altogether ("basis incompatible with the current
+ * supplies / capacities", :1527-1531) as soon as ONE tree flow leaves its bounds.
+ *   what stays   flows and states of non-basic arcs do not depend on supplies; reduced costs depend on neither supplies nor
+ *                capacities.  A non-basic arc at capacity follows its new capacity (and goes back to its lower bound when
+ *                the new capacity is 0 or none: upper_moved counts both).  Tree flows are subtree sums of node balances
+ *                (supply minus outflow plus inflow of the non-basic arcs, 128-bit), and a subtree is a contiguous range of
+ *                the preorder: one gather over the node -> arc adjacency, one device-wide prefix sum over preorder positions
+ *                (dense preorder array and blocked preorder list alike), one pass that writes the tree flows and takes the
+ *                census.  flow[m] and the tree are never downloaded for this.
+ *   path 0       no tree arc is out of bounds (flow < 0, > capacity, or magnitude >= 2^60) and no basic arc sits on a bound
+ *                pointing the wrong way (zero flow away from the root, full flow towards it): the basis stays.  An
+ *                artificial tree arc whose flow changed sign turns round (art_flips); only then do potentials (below it, by
+ *                -+2 big-M), reduced costs and key codes change, rebuilt as mcf_update_costs rebuilds them.  A handle that
+ *                was optimal and takes path 0 without a flip is optimal again: the next mcf_solve makes 0 pivots.
+ *   path 1       otherwise the states and the node records (not the flows) come down and the basis is repaired on the
+ *                host at mcf_set_basis cost: every tree arc whose flow left its bounds becomes non-basic at the bound it
+ *                violated, every wrong-way arc at the bound it sits on; each such subtree hangs on the root by its
+ *                artificial arc, which carries what the cut arc no longer can (arcs_cut real arcs leave the basis, in
+ *                repair_rounds sweeps over the tree).  The result is a strongly feasible basis with a few subtrees on big-M
+ *                arcs, which the primal pivots of the next mcf_solve drive out.
+ *   path 2       the repair refuses (a flow of 2^60 or more on an uncapacitated or artificial arc): cold start with the new
+ *                data, as mcf_reset.
+ *   valid        between solves in any state of the handle (fresh, mid-solve after an iteration limit, optimal, infeasible,
+ *                unbounded), on every engine path, tree layout, rule and key_mode, and on handles that dropped their
+ *                resident reduced costs.  Duplicate indices: the LAST entry wins.  Handles with shard_count > 1: MCF_E_STATE.
+ *   errors       MCF_E_BAD_ARG: null handle, a negative count, null arrays with a positive count, an index outside [0, n)
+ *                / [0, m).  MCF_E_RANGE: the new supply vector does not sum to 0 (128-bit sum) or its positive part reaches
+ *                2^60.  Everything is checked before anything changes: after either error the handle is exactly as it was.
+ *   afterwards   all three paths return MCF_OK and *out (may be NULL) says which one ran.  The solve status is back to
+ *                "running"; mcf_stats.pivots and the other counters keep counting on every path.  Everything derived for
+ *                pricing starts over as after mcf_update_costs.  A later mcf_reset / mcf_set_basis, mcf_certify and the
+ *                objective of mcf_get_result use the new data. */
+typedef struct mcf_rhs_report {
+    int64_t path;             /* 0 = basis kept on the device, 1 = basis repaired (host), 2 = cold start */
+    int64_t tree_violations;  /* tree arcs out of bounds after the recomputation (census on the device) */
+    int64_t wrong_way;        /* basic arcs on a bound pointing the wrong way (strong feasibility) */
+    int64_t arcs_cut;         /* real arcs the repair took out of the basis (path 1) */
+    int64_t repair_rounds;    /* rounds of the repair loop (path 1) */
+    int64_t art_flips;        /* artificial tree arcs whose direction turned round */
+    int64_t upper_moved;      /* non-basic arcs at capacity that followed their new capacity */
+    double  device_ms;        /* HIP events round the device passes */
+} mcf_rhs_report;
+
+int mcf_update_rhs(mcf_handle* h,
+                   int64_t n_sup, const int64_t* node, const int64_t* new_supply,
+                   int64_t n_cap, const int64_t* arc,  const int64_t* new_cap,
+                   mcf_rhs_report* out /* may be NULL */);
 
 /* ---- certificate on the device (the reference's validate_flow / compute_bottleneck_arcs, utils.py:169-312, plus the dual
  * half the reference never checks).  Conservation, bounds, complementary slackness, the exact objectives and the

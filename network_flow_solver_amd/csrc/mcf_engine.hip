@@ -2301,6 +2301,183 @@ __global__ __launch_bounds__(kCertThreads) void k_bn_write(const uint8_t* __rest
     }
 }
 
+// ------------------------------------------------------------------ mcf_update_rhs: new supplies / capacities under a resident basis
+// Flows and states of non-basic arcs do not depend on supplies; tree flows are subtree sums of node balances, and a
+// subtree is a contiguous range of the preorder.  Bytes each pass moves (n nodes, m arcs, k changes):
+//   k_rhs_scatter  one lane per change: 12 B in; a capacity change reads and writes the arc's 16 B walk record (+ 1 B state,
+//                  and 8 B reduced cost -> 4 B key code when a non-basic arc at capacity falls back to its lower bound);
+//                  a supply change is one 8 B store.
+//   k_rhs_balance  one lane per node: supply (8 B), position (4 B dense; 4 + 8 B blocked: slot, block base), and per
+//                  adjacency entry (2 m of them) 8 B entry + 1 B state + 16 B walk record of the NON-BASIC arcs only;
+//                  16 B out (the 128-bit balance, at the node's preorder position).
+//   k_rhs_scan_*   inclusive prefix sum over the n + 1 positions in three launches (chunk totals, scan of the totals by one
+//                  workgroup, scan of every chunk): 16 B per position read twice and written once.
+//   k_rhs_flows    one lane per node: node record (16 B), position, two 16 B prefix sums, the tree arc's walk record read
+//                  and its flow written (16 + 8 B); an artificial arc that turns round rewrites 4 B of the node record and
+//                  seeds 16 B of a jump record.  Census by wave reduction, one atomic per wave and counter.
+// All sums are 128-bit: 2^30 arcs at capacities below 2^60 stay below 2^91, so no prefix can wrap.
+constexpr int kRhsThreads = 256;
+constexpr int kRhsPer = 8;                             // positions per lane in the scan
+constexpr int kRhsChunk = kRhsThreads * kRhsPer;       // positions per workgroup
+enum { RHS_VIOL = 0, RHS_WRONG = 1, RHS_FLIPS = 2, RHS_MOVED = 3, RHS_COUNTERS = 4 };
+
+// logical preorder position of `node` in the view mcf_get_tree reports (cur: the copy that is current); -1: record out of range
+__device__ __forceinline__ int32_t rhs_pos(const McfView& v, int32_t cur, int32_t node) {
+    if (MCF_HAS_BPL(v)) {
+        const int32_t s = v.posbuf[0][node] & MCF_LOC_SLOT;
+        const int32_t b = s >> v.blk_shift;
+        if (b < 0 || b >= v.blk_cap) return -1;
+        const int32_t base = (cur ? v.bmeta[1] : v.bmeta[0])[b].base;
+        if (base == MCF_BLK_FREE) return -1;
+        const int32_t p = base + (s & ((1 << v.blk_shift) - 1));
+        return p < v.n_nodes ? p : -1;
+    }
+    const int32_t p = (cur ? v.posbuf[1] : v.posbuf[0])[node];
+    return (p < 0 || p >= v.n_nodes) ? -1 : p;
+}
+
+__device__ __forceinline__ void rhs_count(unsigned long long* info, int which, int32_t mine) {
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&info[which], (unsigned long long)mine);
+}
+
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_scatter(McfView v, int64_t n_sup, const int32_t* __restrict__ snode, const int64_t* __restrict__ sval,
+                                                             int64_t* __restrict__ supply, int64_t n_cap, const int32_t* __restrict__ carc,
+                                                             const int64_t* __restrict__ cval, unsigned long long* __restrict__ info) {
+    const int64_t total = n_sup > n_cap ? n_sup : n_cap;
+    const int64_t stride = (int64_t)gridDim.x * kRhsThreads;
+    int32_t moved = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kRhsThreads + threadIdx.x; i < total; i += stride) {
+        if (i < n_sup) supply[snode[i]] = sval[i];
+        if (i >= n_cap) continue;
+        const int32_t e = carc[i];
+        const int64_t nc = cval[i];
+        McfArcW w = v.arcw[e];
+        if (w.cap == nc) continue;
+        w.cap = nc;
+        if (v.state[e] == -1) {   // non-basic at capacity: the flow follows the capacity
+            ++moved;
+            if (nc >= MCF_INF || nc == 0) {   // no capacity to sit at: back to the lower bound (mcf_apply_basis' state rule)
+                v.state[e] = 1;
+                w.flow = 0;
+                if (v.vkey) v.vkey[e] = mcf_vkey(-v.rcache[e], v.vk_bigm, v.vk_half);
+            } else {
+                w.flow = nc;
+            }
+        }
+        v.arcw[e] = w;
+    }
+    rhs_count(info, RHS_MOVED, moved);
+}
+
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_balance(McfView v, int32_t cur, const int64_t* __restrict__ supply, const int64_t* __restrict__ adj_off,
+                                                             const int64_t* __restrict__ adj, mcf_u128* __restrict__ bal) {
+    const int32_t n = v.n_nodes - 1;
+    for (int32_t u = blockIdx.x * kRhsThreads + threadIdx.x; u < n; u += gridDim.x * kRhsThreads) {
+        const int32_t p = rhs_pos(v, cur, u);
+        if (p < 0) continue;   // (a broken record: the flow pass counts it as a violation)
+        __int128 b = supply[u];
+        const int64_t lo = adj_off[u], hi = adj_off[u + 1];
+        for (int64_t k = lo; k < hi; ++k) {
+            const int64_t w = adj[k];
+            const int64_t e = (w & 0xffffffff) >> 1;
+            if (v.state[e] == 0) continue;   // basic arcs get their flow from the subtree sums
+            const int64_t f = v.arcw[e].flow;
+            b += (w & 1) ? -(__int128)f : (__int128)f;
+        }
+        bal[p] = (mcf_u128)b;
+    }
+}
+
+// thread t of a workgroup owns positions [chunk base + t * kRhsPer, + kRhsPer): 128 contiguous bytes, 16-byte accesses
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_scan_totals(const mcf_u128* __restrict__ bal, int32_t count, mcf_u128* __restrict__ part) {
+    __shared__ mcf_u128 s[kRhsThreads / 64];
+    const int64_t base = (int64_t)blockIdx.x * kRhsChunk + (int64_t)threadIdx.x * kRhsPer;
+    mcf_u128 sum = 0;
+#pragma unroll
+    for (int k = 0; k < kRhsPer; ++k) if (base + k < count) sum += bal[base + k];
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t lo = __shfl_down((unsigned long long)(uint64_t)sum, off, 64), hi = __shfl_down((unsigned long long)(uint64_t)(sum >> 64), off, 64);
+        sum += ((mcf_u128)hi << 64) | lo;   // (lanes past the end add what their neighbours hold: only lane 0's sum is used)
+    }
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+}
+
+// part[b] <- sum of part[0 .. b) (one workgroup, like k_bn_scan)
+__global__ __launch_bounds__(1024) void k_rhs_scan_parts(mcf_u128* __restrict__ part, int64_t nb) {
+    __shared__ mcf_u128 s[1024];
+    const int64_t per = (nb + 1023) / 1024, lo = threadIdx.x * per < nb ? threadIdx.x * per : nb, hi = lo + per < nb ? lo + per : nb;
+    mcf_u128 sum = 0;
+    for (int64_t b = lo; b < hi; ++b) sum += part[b];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mcf_u128 run = 0;
+        for (int k = 0; k < 1024; ++k) { const mcf_u128 x = s[k]; s[k] = run; run += x; }
+    }
+    __syncthreads();
+    mcf_u128 run = s[threadIdx.x];
+    for (int64_t b = lo; b < hi; ++b) { const mcf_u128 x = part[b]; part[b] = run; run += x; }
+}
+
+// bal[p] <- sum of bal[0 .. p] (inclusive, in place)
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_scan_apply(mcf_u128* __restrict__ bal, int32_t count, const mcf_u128* __restrict__ part) {
+    __shared__ mcf_u128 s[kRhsThreads];
+    const int64_t base = (int64_t)blockIdx.x * kRhsChunk + (int64_t)threadIdx.x * kRhsPer;
+    mcf_u128 x[kRhsPer];
+    mcf_u128 sum = 0;
+#pragma unroll
+    for (int k = 0; k < kRhsPer; ++k) { x[k] = base + k < count ? bal[base + k] : (mcf_u128)0; sum += x[k]; x[k] = sum; }
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int off = 1; off < kRhsThreads; off <<= 1) {   // Hillis-Steele over the lanes' totals
+        const mcf_u128 add = (int)threadIdx.x >= off ? s[threadIdx.x - off] : (mcf_u128)0;
+        __syncthreads();
+        s[threadIdx.x] += add;
+        __syncthreads();
+    }
+    const mcf_u128 before = part[blockIdx.x] + (threadIdx.x > 0 ? s[threadIdx.x - 1] : (mcf_u128)0);
+#pragma unroll
+    for (int k = 0; k < kRhsPer; ++k) if (base + k < count) bal[base + k] = x[k] + before;
+}
+
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_flows(McfView v, int32_t cur, const mcf_u128* __restrict__ pre, int64_t bigm, McfJump* __restrict__ jump,
+                                                           unsigned long long* __restrict__ info) {
+    const int32_t N = v.n_nodes, n = N - 1;
+    const int64_t m = v.m;
+    int32_t viol = 0, wrong = 0, flips = 0;
+    for (int32_t u = blockIdx.x * kRhsThreads + threadIdx.x; u < n; u += gridDim.x * kRhsThreads) {
+        const McfNode nd = v.node[u];
+        const int32_t p = rhs_pos(v, cur, u);
+        if (p < 1 || nd.size < 1 || (int64_t)p + nd.size > N || nd.pred < 0) { ++viol; continue; }
+        const __int128 x = (__int128)(pre[p + nd.size - 1] - pre[p - 1]);   // surplus the subtree of u sends up
+        const int64_t a = nd.pred >> 1;
+        const bool up = (nd.pred & 1) != 0;
+        if (a < m) {
+            const __int128 f = up ? x : -x;
+            const int64_t cap = v.arcw[a].cap;
+            if (f < 0 || f > cap || f >= MCF_INF) { ++viol; continue; }
+            v.arcw[a].flow = (int64_t)f;
+            if ((up && cap < MCF_INF && f == cap) || (!up && f == 0)) ++wrong;
+        } else {
+            const __int128 ax = x < 0 ? -x : x;
+            if (ax >= MCF_INF) { ++viol; continue; }
+            v.arcw[a].flow = (int64_t)ax;
+            const bool nup = x >= 0;
+            if (nup != up) {   // the arc turns round: pi[u] = pi[root] -+ big-M, and with it every potential below
+                ++flips;
+                v.node[u].pred = (int32_t)((a << 1) | (nup ? 1 : 0));
+                jump[u].val = nup ? -2 * bigm : 2 * bigm;
+            }
+        }
+    }
+    rhs_count(info, RHS_VIOL, viol);
+    rhs_count(info, RHS_WRONG, wrong);
+    rhs_count(info, RHS_FLIPS, flips);
+}
+
 }  // namespace
 
 // ====================================================================== handle
@@ -2406,6 +2583,14 @@ struct mcf_handle {
     int64_t* d_bn_off = nullptr;
     int64_t* d_bn_idx = nullptr;
     int64_t bn_idx_cap = 0;
+    // mcf_update_rhs: everything allocated on first use (supplies and adjacency are the certificate's, jump records mcf_update_costs')
+    std::vector<uint32_t> rhs_nstamp;                      // per node: the call that last named it
+    int32_t* d_rhs_idx = nullptr;                          // changed nodes, then changed arcs (engine indices)
+    int64_t* d_rhs_val = nullptr;                          // their new supplies / capacities
+    int64_t rhs_cap = 0;                                   // entries the two arrays hold
+    mcf_u128* d_rhs_bal = nullptr;                         // [n_nodes] balance per preorder position, then its prefix sums
+    mcf_u128* d_rhs_part = nullptr;                        // per chunk of positions
+    unsigned long long* d_rhs_info = nullptr;              // [RHS_COUNTERS]
 };
 
 namespace {
@@ -2839,6 +3024,7 @@ void free_all(mcf_handle* h) {
     (void)hipFree(h->d_bn_flag); (void)hipFree(h->d_bn_cnt); (void)hipFree(h->d_bn_off); (void)hipFree(h->d_bn_idx);
     for (hipEvent_t e : h->ct_ev) if (e) (void)hipEventDestroy(e);
     (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost); (void)hipFree(h->d_uc_jump[0]); (void)hipFree(h->d_uc_jump[1]); (void)hipFree(h->d_uc_info);
+    (void)hipFree(h->d_rhs_idx); (void)hipFree(h->d_rhs_val); (void)hipFree(h->d_rhs_bal); (void)hipFree(h->d_rhs_part); (void)hipFree(h->d_rhs_info);
     if (h->h_ctx) pinned_give(reinterpret_cast<char*>(h->h_ctx));   // (h_one lives in the same slot)
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
 }
@@ -2899,6 +3085,84 @@ int cert_prepare(mcf_handle* h) {
     return MCF_OK;
 }
 
+
+// ---- shared by mcf_update_costs and mcf_update_rhs
+unsigned uc_blocks_for(int64_t items) { const int64_t b = (items + kUcThreads - 1) / kUcThreads; return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
+
+// caller's arc index -> engine arc index, and the stamps that resolve duplicates (arcs and nodes)
+void uc_index(mcf_handle* h) {
+    const McfHostImage& im = h->im;
+    if (!h->uc_inv.empty() || im.m == 0) return;
+    h->uc_inv.assign((size_t)im.m, 0);
+    for (int64_t e = 0; e < im.m; ++e) h->uc_inv[(size_t)im.orig[(size_t)e]] = (int32_t)e;
+    h->uc_stamp.assign((size_t)im.m, 0);
+}
+void uc_next_gen(mcf_handle* h) {
+    if (h->rhs_nstamp.empty()) h->rhs_nstamp.assign((size_t)h->im.n, 0);
+    if (++h->uc_gen == 0) {
+        std::fill(h->uc_stamp.begin(), h->uc_stamp.end(), 0u);
+        std::fill(h->rhs_nstamp.begin(), h->rhs_nstamp.end(), 0u);
+        h->uc_gen = 1;
+    }
+}
+
+// jump records (double buffered) and the info words
+int uc_alloc(mcf_handle* h) {
+    if (h->d_uc_info) return MCF_OK;
+    for (int a = 0; a < 2; ++a)
+        if (dalloc(&h->d_uc_jump[a], (size_t)h->im.n_nodes) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc jump records"; return MCF_E_ALLOC; }
+    if (dalloc(&h->d_uc_info, 2) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc update info"; return MCF_E_ALLOC; }
+    return MCF_OK;
+}
+
+// potentials from the seeded records in d_uc_jump[0]: rounds = ceil(log2(greatest depth)), at least the final one
+void uc_jump_rounds(mcf_handle* h, int32_t depth) {
+    const int32_t N = h->im.n_nodes;
+    hipStream_t s = h->stream;
+    int rounds = 1;
+    while (((int64_t)1 << rounds) < (int64_t)depth) ++rounds;
+    int cur = 0;
+    for (int r = 0; r < rounds; ++r) {
+        if (r + 1 < rounds) hipLaunchKernelGGL(k_uc_jump<false>, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfJump*)h->d_uc_jump[cur], h->d_uc_jump[cur ^ 1], h->d_pi, N);
+        else hipLaunchKernelGGL(k_uc_jump<true>, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfJump*)h->d_uc_jump[cur], h->d_uc_jump[cur ^ 1], h->d_pi, N);
+        cur ^= 1;
+    }
+}
+
+// The tail of both calls: resident reduced costs / key codes from the potentials (`rebuild`; only where the handle keeps
+// them), everything derived for pricing starts over, the control block says "running" again with its counters kept.
+// *h_ctx must be current (sync_ctx, and nothing since has touched the device's copy).
+int uc_finish(mcf_handle* h, bool rebuild) {
+    const McfHostImage& im = h->im;
+    hipStream_t s = h->stream;
+    if (rebuild && h->rcached) {   // (a handle that dropped its reduced costs, or never kept any, prices from the potentials)
+        int64_t pb = (im.m_pad / 4 / MCF_NUM_BUCKETS + kUcThreads * kUcUnroll - 1) / (kUcThreads * kUcUnroll);
+        pb = pb < 1 ? 1 : (pb > 2048 / MCF_NUM_BUCKETS ? 2048 / MCF_NUM_BUCKETS : pb);
+        hipLaunchKernelGGL(k_uc_rebuild, dim3((unsigned)pb * MCF_NUM_BUCKETS), dim3(kUcThreads), 0, s, h->view, im.m_pad);
+    }
+    // derived pricing state: candidate list and cache, clean / dirty marks, Devex weights, block cursor, tuner
+    HIP_TRY(h, hipMemsetAsync(h->d_cand, 0xff, kMaxPriceBlocks * sizeof(McfCand), s));
+    if (h->d_candx) HIP_TRY(h, hipMemsetAsync(h->d_candx, 0xff, kMaxPriceBlocks * sizeof(McfCandX), s));
+    if (h->d_dirty) HIP_TRY(h, hipMemsetAsync(h->d_dirty->flag, 1, sizeof(h->d_dirty->flag), s));
+    if (h->opt.rule == MCF_RULE_DEVEX_BLOCK) hipLaunchKernelGGL(k_uc_ones, dim3(uc_blocks_for(im.m_pad / 4)), dim3(kUcThreads), 0, s, reinterpret_cast<float4*>(h->d_weight), im.m_pad / 4);
+    HIP_TRY(h, hipGetLastError());
+    {
+        McfCtx& c = *h->h_ctx;
+        c.status = MCF_RUNNING;
+        c.limit_checked = 0;
+        c.unbounded_arc = -1;
+        c.minor_left = 0;
+        mcf_init_block_state(&c, h->opt.rule, im.m, h->opt.block_size);
+        if (h->opt.rule == MCF_RULE_DEVEX_BLOCK) {
+            if (h->opt.devex_tuner > 0) c.auto_tune = 1; else if (h->opt.devex_tuner < 0) c.auto_tune = 0;
+            if (h->opt.devex_stay > 0) c.devex_cyclic = 0;
+        }
+        HIP_TRY(h, hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->ctx_current = false;
+    return MCF_OK;
+}
 
 }  // namespace
 
@@ -3293,13 +3557,8 @@ int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int
         if (arc[i] < 0 || arc[i] >= im.m) { h->err = "mcf_update_costs: arc index out of range"; return MCF_E_BAD_ARG; }
     for (int64_t i = 0; i < count; ++i)
         if (new_cost[i] > INT32_MAX || new_cost[i] < -(int64_t)INT32_MAX) { h->err = "mcf_update_costs: |cost| must fit int32"; return MCF_E_RANGE; }
-    if (count > 0 && h->uc_inv.empty()) {
-        h->uc_inv.assign((size_t)im.m, 0);
-        for (int64_t e = 0; e < im.m; ++e) h->uc_inv[(size_t)im.orig[(size_t)e]] = (int32_t)e;
-        h->uc_stamp.assign((size_t)im.m, 0);
-        h->uc_gen = 0;
-    }
-    if (++h->uc_gen == 0) { std::fill(h->uc_stamp.begin(), h->uc_stamp.end(), 0u); h->uc_gen = 1; }
+    uc_index(h);
+    uc_next_gen(h);
     // duplicates: the last entry wins (walk backwards, keep the first sighting of every arc)
     std::vector<int32_t> ue, uc;
     ue.reserve((size_t)count); uc.reserve((size_t)count);
@@ -3320,12 +3579,8 @@ int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int
     const int64_t nu = (int64_t)ue.size();
 
     HIP_TRY(h, hipSetDevice(h->device));
-    // temporaries
-    if (!h->d_uc_info) {
-        for (int a = 0; a < 2; ++a)
-            if (dalloc(&h->d_uc_jump[a], (size_t)im.n_nodes) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc jump records"; return MCF_E_ALLOC; }
-        if (dalloc(&h->d_uc_info, 2) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc update info"; return MCF_E_ALLOC; }
-    }
+    int rc = uc_alloc(h);   // temporaries
+    if (rc) return rc;
     if (nu > h->uc_cap) {
         (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost);
         h->d_uc_arc = nullptr; h->d_uc_cost = nullptr; h->uc_cap = 0;
@@ -3337,13 +3592,13 @@ int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int
         }
         h->uc_cap = cap;
     }
-    int rc = sync_ctx(h, h->stream);
+    rc = sync_ctx(h, h->stream);
     if (rc) return rc;
     if (h->h_ctx->status == MCF_INTERNAL_ERROR) { h->err = "mcf_update_costs: the handle's tree is not usable"; return MCF_E_STATE; }
 
     hipStream_t s = h->stream;
     const int32_t N = im.n_nodes;
-    auto blocks_for = [](int64_t items) { const int64_t b = (items + kUcThreads - 1) / kUcThreads; return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); };
+    auto blocks_for = uc_blocks_for;
     if (nu > 0) {
         HIP_TRY(h, hipMemcpyAsync(h->d_uc_arc, ue.data(), (size_t)nu * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(h->d_uc_cost, uc.data(), (size_t)nu * 4, hipMemcpyHostToDevice, s));
@@ -3358,17 +3613,8 @@ int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int
     int32_t info[2] = {0, 0};
     HIP_TRY(h, hipMemcpyAsync(info, h->d_uc_info, sizeof info, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));   // (also: the pageable sources above are free again)
-    // potentials: only when a tree arc changed (or big-M grew); rounds = ceil(log2(greatest depth)), at least the final one
-    if (info[1] > 0 || d_bigm != 0) {
-        int rounds = 1;
-        while (((int64_t)1 << rounds) < (int64_t)info[0]) ++rounds;
-        int cur = 0;
-        for (int r = 0; r < rounds; ++r) {
-            if (r + 1 < rounds) hipLaunchKernelGGL(k_uc_jump<false>, dim3(blocks_for(N)), dim3(kUcThreads), 0, s, (const McfJump*)h->d_uc_jump[cur], h->d_uc_jump[cur ^ 1], h->d_pi, N);
-            else hipLaunchKernelGGL(k_uc_jump<true>, dim3(blocks_for(N)), dim3(kUcThreads), 0, s, (const McfJump*)h->d_uc_jump[cur], h->d_uc_jump[cur ^ 1], h->d_pi, N);
-            cur ^= 1;
-        }
-    }
+    // potentials: only when a tree arc changed (or big-M grew)
+    if (info[1] > 0 || d_bigm != 0) uc_jump_rounds(h, info[0]);
     // the view's big-M first: the key codes below are formed with it, and captured graphs carry the view by value
     if (d_bigm != 0) {
         h->view.vk_bigm = big_m;
@@ -3376,36 +3622,180 @@ int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int
         if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
         h->graph_batch = 0;
     }
-    if (h->rcached) {   // (a handle that dropped its reduced costs, or never kept any, prices from the potentials)
-        int64_t pb = (im.m_pad / 4 / MCF_NUM_BUCKETS + kUcThreads * kUcUnroll - 1) / (kUcThreads * kUcUnroll);
-        pb = pb < 1 ? 1 : (pb > 2048 / MCF_NUM_BUCKETS ? 2048 / MCF_NUM_BUCKETS : pb);
-        hipLaunchKernelGGL(k_uc_rebuild, dim3((unsigned)pb * MCF_NUM_BUCKETS), dim3(kUcThreads), 0, s, h->view, im.m_pad);
-    }
-    // derived pricing state: candidate list and cache, clean / dirty marks, Devex weights, block cursor, tuner
-    HIP_TRY(h, hipMemsetAsync(h->d_cand, 0xff, kMaxPriceBlocks * sizeof(McfCand), s));
-    if (h->d_candx) HIP_TRY(h, hipMemsetAsync(h->d_candx, 0xff, kMaxPriceBlocks * sizeof(McfCandX), s));
-    if (h->d_dirty) HIP_TRY(h, hipMemsetAsync(h->d_dirty->flag, 1, sizeof(h->d_dirty->flag), s));
-    if (h->opt.rule == MCF_RULE_DEVEX_BLOCK) hipLaunchKernelGGL(k_uc_ones, dim3(blocks_for(im.m_pad / 4)), dim3(kUcThreads), 0, s, reinterpret_cast<float4*>(h->d_weight), im.m_pad / 4);
-    HIP_TRY(h, hipGetLastError());
-    {
-        McfCtx& c = *h->h_ctx;   // current (sync_ctx above; nothing since has touched the device's copy)
-        c.status = MCF_RUNNING;
-        c.limit_checked = 0;
-        c.unbounded_arc = -1;
-        c.minor_left = 0;
-        mcf_init_block_state(&c, h->opt.rule, im.m, h->opt.block_size);
-        if (h->opt.rule == MCF_RULE_DEVEX_BLOCK) {
-            if (h->opt.devex_tuner > 0) c.auto_tune = 1; else if (h->opt.devex_tuner < 0) c.auto_tune = 0;
-            if (h->opt.devex_stay > 0) c.devex_cyclic = 0;
-        }
-        HIP_TRY(h, hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    h->ctx_current = false;
+    rc = uc_finish(h, true);
+    if (rc) return rc;
     // host image: a later mcf_reset / mcf_set_basis (which rebuild its potentials and reduced costs from these) and the
     // objective of mcf_get_result use the new costs
     for (int64_t i = 0; i < nu; ++i) { im.cost[(size_t)ue[(size_t)i]] = uc[(size_t)i]; im.cost64[(size_t)ue[(size_t)i]] = uc[(size_t)i]; }
     im.big_m = big_m;
+    return MCF_OK;
+}
+
+// Re-optimise after supplies / capacities changed (kernels k_rhs_* above).  Non-basic flows follow their capacities, tree
+// flows are recomputed as subtree sums of the node balances, and a census decides: the basis stays (path 0), is repaired
+// on the host at mcf_set_basis cost (path 1, mcf_repair_basis), or the handle goes to the cold start (path 2).
+int mcf_update_rhs(mcf_handle* h, int64_t n_sup, const int64_t* node, const int64_t* new_supply, int64_t n_cap,
+                   const int64_t* arc, const int64_t* new_cap, mcf_rhs_report* out) {
+    if (!h) return MCF_E_BAD_ARG;
+    if (h->shards != 1) {
+        h->err = "mcf_update_rhs: handle was created with shard_count > 1; sharded handles cannot change their supplies / capacities";
+        return MCF_E_STATE;
+    }
+    if (n_sup < 0 || n_cap < 0 || (n_sup > 0 && (!node || !new_supply)) || (n_cap > 0 && (!arc || !new_cap))) {
+        h->err = "mcf_update_rhs: bad count / null array";
+        return MCF_E_BAD_ARG;
+    }
+    McfHostImage& im = h->im;
+    for (int64_t i = 0; i < n_sup; ++i)
+        if (node[i] < 0 || node[i] >= im.n) { h->err = "mcf_update_rhs: node index out of range"; return MCF_E_BAD_ARG; }
+    for (int64_t i = 0; i < n_cap; ++i)
+        if (arc[i] < 0 || arc[i] >= im.m) { h->err = "mcf_update_rhs: arc index out of range"; return MCF_E_BAD_ARG; }
+    uc_index(h);
+    uc_next_gen(h);
+    // duplicates: the last entry wins (walk backwards, keep the first sighting); nodes first, then arcs, in one pair of arrays
+    std::vector<int32_t> idx;
+    std::vector<int64_t> val;
+    idx.reserve((size_t)(n_sup + n_cap)); val.reserve((size_t)(n_sup + n_cap));
+    __int128 total = 0, positive = 0;
+    for (int32_t v = 0; v < im.n; ++v) if (im.supply[(size_t)v] > 0) positive += im.supply[(size_t)v];
+    for (int64_t i = n_sup - 1; i >= 0; --i) {
+        const int32_t v = (int32_t)node[i];
+        if (h->rhs_nstamp[(size_t)v] == h->uc_gen) continue;
+        h->rhs_nstamp[(size_t)v] = h->uc_gen;
+        idx.push_back(v); val.push_back(new_supply[i]);
+        const int64_t was = im.supply[(size_t)v];
+        total += (__int128)new_supply[i] - was;
+        positive += (__int128)(new_supply[i] > 0 ? new_supply[i] : 0) - (was > 0 ? was : 0);
+    }
+    if (total != 0) { h->err = "mcf_update_rhs: supplies do not balance"; return MCF_E_RANGE; }
+    if (positive >= (__int128)MCF_INF) { h->err = "mcf_update_rhs: the sum of the positive supplies must stay below 2^60"; return MCF_E_RANGE; }
+    const int64_t ns = (int64_t)idx.size();
+    for (int64_t i = n_cap - 1; i >= 0; --i) {
+        const int32_t e = h->uc_inv[(size_t)arc[i]];
+        if (h->uc_stamp[(size_t)e] == h->uc_gen) continue;
+        h->uc_stamp[(size_t)e] = h->uc_gen;
+        idx.push_back(e); val.push_back((new_cap[i] < 0 || new_cap[i] >= MCF_INF) ? MCF_INF : new_cap[i]);
+    }
+    const int64_t nc = (int64_t)idx.size() - ns;
+
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = uc_alloc(h);
+    if (rc) return rc;
+    if ((rc = cert_prepare(h)) != MCF_OK) return rc;   // device supplies, a full adjacency, two events
+    const int32_t N = im.n_nodes;
+    const int64_t chunks = ((int64_t)N + kRhsChunk - 1) / kRhsChunk;
+    if (!h->d_rhs_bal) {
+        if (dalloc(&h->d_rhs_bal, (size_t)N) != hipSuccess || dalloc(&h->d_rhs_part, (size_t)chunks) != hipSuccess ||
+            dalloc(&h->d_rhs_info, (size_t)RHS_COUNTERS) != hipSuccess) {
+            (void)hipGetLastError(); cert_free(&h->d_rhs_bal); cert_free(&h->d_rhs_part); cert_free(&h->d_rhs_info);
+            h->err = "hipMalloc balances"; return MCF_E_ALLOC;
+        }
+    }
+    if (ns + nc > h->rhs_cap) {
+        cert_free(&h->d_rhs_idx); cert_free(&h->d_rhs_val); h->rhs_cap = 0;
+        const int64_t cap = (ns + nc) + (ns + nc) / 2 + 1024;
+        if (dalloc(&h->d_rhs_idx, (size_t)cap) != hipSuccess || dalloc(&h->d_rhs_val, (size_t)cap) != hipSuccess) {
+            (void)hipGetLastError(); cert_free(&h->d_rhs_idx); cert_free(&h->d_rhs_val);
+            h->err = "hipMalloc supply / capacity changes"; return MCF_E_ALLOC;
+        }
+        h->rhs_cap = cap;
+    }
+    rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    if (h->h_ctx->status == MCF_INTERNAL_ERROR) { h->err = "mcf_update_rhs: the handle's tree is not usable"; return MCF_E_STATE; }
+
+    // ---- device passes
+    hipStream_t s = h->stream;
+    const int32_t cur = h->h_ctx->cur ^ (h->h_ctx->pending_flip ? 1 : 0);   // as mcf_get_tree reads the arrays
+    const bool own_adj = h->d_adj && !h->view.rc_partial;
+    McfView vw = h->view;
+    if (h->rcached) { vw.rcache = h->d_rcache; } else { vw.vkey = nullptr; }   // (key codes are patched only where they are kept)
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
+    if (ns + nc > 0) {
+        HIP_TRY(h, hipMemcpyAsync(h->d_rhs_idx, idx.data(), (size_t)(ns + nc) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(h->d_rhs_val, val.data(), (size_t)(ns + nc) * 8, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(h, hipMemsetAsync(h->d_rhs_info, 0, RHS_COUNTERS * sizeof(unsigned long long), s));
+    HIP_TRY(h, hipMemsetAsync(h->d_uc_info, 0, 2 * sizeof(int32_t), s));
+    HIP_TRY(h, hipMemsetAsync(h->d_rhs_bal, 0, (size_t)N * sizeof(mcf_u128), s));
+    if (ns + nc > 0)
+        hipLaunchKernelGGL(k_rhs_scatter, dim3(uc_blocks_for(ns > nc ? ns : nc)), dim3(kRhsThreads), 0, s, vw, ns, (const int32_t*)h->d_rhs_idx,
+                           (const int64_t*)h->d_rhs_val, h->d_ct_supply, nc, (const int32_t*)(h->d_rhs_idx + ns), (const int64_t*)(h->d_rhs_val + ns), h->d_rhs_info);
+    hipLaunchKernelGGL(k_rhs_balance, dim3(uc_blocks_for(N)), dim3(kRhsThreads), 0, s, vw, cur, (const int64_t*)h->d_ct_supply,
+                       (const int64_t*)(own_adj ? h->d_adj_off : h->d_ct_adj_off), (const int64_t*)(own_adj ? h->d_adj : h->d_ct_adj), h->d_rhs_bal);
+    hipLaunchKernelGGL(k_rhs_scan_totals, dim3((unsigned)chunks), dim3(kRhsThreads), 0, s, (const mcf_u128*)h->d_rhs_bal, N, h->d_rhs_part);
+    hipLaunchKernelGGL(k_rhs_scan_parts, dim3(1), dim3(1024), 0, s, h->d_rhs_part, chunks);
+    hipLaunchKernelGGL(k_rhs_scan_apply, dim3((unsigned)chunks), dim3(kRhsThreads), 0, s, h->d_rhs_bal, N, (const mcf_u128*)h->d_rhs_part);
+    // jump records for the potentials below an artificial arc that turns round (seeded with 0; the flow pass marks the turns)
+    hipLaunchKernelGGL(k_uc_seed, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfNode*)h->d_node, N, im.m, (int64_t)0, h->d_uc_jump[0], h->d_uc_info);
+    hipLaunchKernelGGL(k_rhs_flows, dim3(uc_blocks_for(N)), dim3(kRhsThreads), 0, s, vw, cur, (const mcf_u128*)h->d_rhs_bal, im.big_m, h->d_uc_jump[0], h->d_rhs_info);
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long info[RHS_COUNTERS] = {0, 0, 0, 0};
+    int32_t depth[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(info, h->d_rhs_info, sizeof info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(depth, h->d_uc_info, sizeof depth, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));   // (also: the pageable sources above are free again)
+
+    // host image: the objective, a later mcf_reset / mcf_set_basis and the repair below use the new data
+    for (int64_t i = 0; i < ns; ++i) im.supply[(size_t)idx[(size_t)i]] = val[(size_t)i];
+    for (int64_t i = ns; i < ns + nc; ++i) im.arcw[(size_t)idx[(size_t)i]].cap = val[(size_t)i];
+
+    mcf_rhs_report rep;
+    std::memset(&rep, 0, sizeof rep);
+    rep.tree_violations = (int64_t)info[RHS_VIOL];
+    rep.wrong_way = (int64_t)info[RHS_WRONG];
+    rep.art_flips = (int64_t)info[RHS_FLIPS];
+    rep.upper_moved = (int64_t)info[RHS_MOVED];
+    if (rep.tree_violations == 0 && rep.wrong_way == 0) {
+        // ---- path 0: the basis stays
+        if (rep.art_flips > 0) uc_jump_rounds(h, depth[0]);
+        if ((rc = uc_finish(h, rep.art_flips > 0)) != MCF_OK) return rc;
+        HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+        HIP_TRY(h, hipEventSynchronize(h->ct_ev[1]));
+    } else {
+        // ---- path 1: states and node records come down, the basis is repaired on the host and installed as mcf_set_basis
+        // does; path 2 (cold start) when the repair refuses
+        HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+        std::vector<int8_t> st((size_t)im.m_pad), in_tree((size_t)(im.m ? im.m : 1), 0), at_upper((size_t)(im.m ? im.m : 1), 0), hang((size_t)im.n, 0);
+        std::vector<McfNode> nodes((size_t)N);
+        HIP_TRY(h, hipMemcpy(st.data(), h->d_state, st.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(nodes.data(), h->d_node, nodes.size() * sizeof(McfNode), hipMemcpyDeviceToHost));
+        for (int64_t e = 0; e < im.m; ++e) {
+            in_tree[(size_t)im.orig[(size_t)e]] = st[(size_t)e] == 0;
+            at_upper[(size_t)im.orig[(size_t)e]] = st[(size_t)e] == -1;
+        }
+        for (int32_t v = 0; v < im.n; ++v) hang[(size_t)v] = nodes[(size_t)v].pred >= 0 && (int64_t)(nodes[(size_t)v].pred >> 1) >= im.m;
+        McfRepairReport rr;
+        const std::string msg = mcf_repair_basis(im, in_tree.data(), at_upper.data(), hang.data(), &rr);
+        rep.path = 1;
+        rep.arcs_cut = rr.arcs_cut;
+        rep.repair_rounds = rr.rounds;
+        if (!msg.empty()) { mcf_init_cold_basis(im); rep.path = 2; rep.arcs_cut = 0; }
+        mcf_refresh_rcache(im);
+        // the counters keep counting: upload_image starts them over, so they are carried across it
+        const McfCtx was = *h->h_ctx;
+        const mcf_stats stats_was = h->stats;
+        if ((rc = upload_image(h)) != MCF_OK) return rc;
+        McfCtx& c = *h->h_ctx;
+        c.pivots = was.pivots; c.degenerate = was.degenerate; c.bound_flips = was.bound_flips; c.arcs_priced = was.arcs_priced;
+        c.nodes_moved = was.nodes_moved; c.subtree_nodes = was.subtree_nodes; c.cycle_arcs = was.cycle_arcs;
+        c.scans = was.scans; c.scan_rounds = was.scan_rounds; c.minor_pivots = was.minor_pivots; c.major_sweeps = was.major_sweeps;
+        c.rebuilds = was.rebuilds;
+        const int64_t price_bytes = h->stats.price_bytes;
+        h->stats = stats_was;
+        h->stats.price_bytes = price_bytes;
+        h->stats.rc_dropped_at = 0; h->stats.run_left_at = 0;   // (a fresh image keeps its reduced costs and its run shape again)
+        h->sw_pivots = c.pivots; h->sw_subtree = c.subtree_nodes; h->run_seen = c.pivots;
+        HIP_TRY(h, hipMemsetAsync(h->d_cand, 0xff, kMaxPriceBlocks * sizeof(McfCand), s));
+        if (h->d_candx) HIP_TRY(h, hipMemsetAsync(h->d_candx, 0xff, kMaxPriceBlocks * sizeof(McfCandX), s));
+        HIP_TRY(h, hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        h->ctx_current = true;
+    }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, h->ct_ev[0], h->ct_ev[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
+    rep.device_ms = ms;
+    if (out) *out = rep;
     return MCF_OK;
 }
 

@@ -280,6 +280,175 @@ inline std::string mcf_apply_basis(McfHostImage& im, const int8_t* in_tree, cons
     return "";
 }
 
+// Repair of a basis after supplies / capacities changed (mcf_update_rhs, path 1).  Same input and same installation as
+// mcf_apply_basis, but where that one returns "basis incompatible with the current supplies / capacities" this one cuts:
+//   * a tree arc whose flow from conservation leaves its bounds becomes non-basic AT THE BOUND IT VIOLATED (0 or capacity),
+//     its subtree a component of its own that hangs on the root by its artificial arc; that arc carries what the clamped
+//     arc no longer can, and the clamped flow stays in the balance of the parent's side;
+//   * a basic arc left on a bound pointing the wrong way (zero flow away from the root, full flow towards it) is taken out
+//     at that bound in the same way, its artificial arc carrying nothing: the strong-feasibility repair of mcf_apply_basis.
+// The tree is walked ONCE, children before parents: when an arc is looked at, every cut below it has already been made and
+// its subtree's surplus is final, so one sweep reaches the fixed point a "cut every violator, recompute, repeat" loop
+// converges to -- and cuts no arc that only looked violated because of a surplus that a cut further down takes away.
+//   hang[n]  (may be null) nodes whose tree arc is their artificial arc in the basis the flows come from: every component keeps
+//            its hanging node, so the arcs of a strongly feasible tree keep their direction.  A component that names none (or
+//            a null array) hangs on its lowest node.
+// Balances are 128-bit: non-basic arcs at capacities near 2^60 add up past 64 bits.  Returns "" (applied) or an error
+// text: a cycle in the basis, or a flow of 2^60 or more on an uncapacitated or artificial arc (outside the engine's
+// numeric domain).  After an error the image may be half written: the caller goes to the cold start.
+struct McfRepairReport {
+    int64_t violations = 0;   // tree arcs found outside their bounds
+    int64_t wrong_way = 0;    // basic arcs found on a bound pointing the wrong way
+    int64_t arcs_cut = 0;     // real arcs taken out of the basis (= violations + wrong_way)
+    int64_t rounds = 0;       // sweeps over the tree
+};
+
+inline std::string mcf_repair_basis(McfHostImage& im, const int8_t* in_tree, const int8_t* at_upper, const int8_t* hang,
+                                    McfRepairReport* report) {
+    const int32_t n = im.n, root = im.n, N = im.n_nodes;
+    const int64_t m = im.m;
+    if (!in_tree) return "null basis";
+    McfRepairReport rr;
+    std::vector<int32_t> uf(N);
+    for (int32_t v = 0; v < N; ++v) uf[v] = v;
+    auto find = [&](int32_t x) { while (uf[x] != x) { uf[x] = uf[uf[x]]; x = uf[x]; } return x; };
+    std::vector<int8_t> basic(m, 0);
+    for (int64_t e = 0; e < m; ++e) {
+        if (!in_tree[im.orig[e]]) continue;
+        const int32_t a = find(im.tail[e]), b = find(im.head[e]);
+        if (a == b) return "basis arcs contain a cycle";
+        uf[a] = b;
+        basic[e] = 1;
+    }
+    // --- non-basic flows and node balances (an arc marked "at capacity" that has none, or capacity 0, sits at zero)
+    std::vector<int64_t> flow(m, 0);
+    std::vector<__int128> bal(N, 0);
+    for (int32_t v = 0; v < n; ++v) bal[v] = im.supply[v];
+    for (int64_t e = 0; e < m; ++e) {
+        if (basic[e] || !at_upper || !at_upper[im.orig[e]]) continue;
+        const int64_t cp = im.arcw[e].cap;
+        if (cp >= MCF_INF || cp == 0) continue;
+        flow[e] = cp;
+        bal[im.tail[e]] -= cp;
+        bal[im.head[e]] += cp;
+    }
+    // --- hanging nodes
+    std::vector<int8_t> rep(N, 0);
+    {
+        std::vector<int8_t> have(N, 0);
+        if (hang) for (int32_t v = 0; v < n; ++v) { if (!hang[v]) continue; const int32_t c = find(v); if (!have[c]) { have[c] = 1; rep[v] = 1; } }
+        for (int32_t v = 0; v < n; ++v) { const int32_t c = find(v); if (!have[c]) { have[c] = 1; rep[v] = 1; } }
+    }
+    // --- tree adjacency and preorder, as in mcf_apply_basis
+    std::vector<int64_t> off((size_t)N + 1, 0);
+    std::vector<int32_t> adj, order(N), parent(N), depth(N), stack;
+    std::vector<int64_t> parc(N);
+    auto build_adj = [&]() {
+        std::fill(off.begin(), off.end(), 0);
+        for (int64_t e = 0; e < m; ++e) if (basic[e]) { off[im.tail[e] + 1]++; off[im.head[e] + 1]++; }
+        for (int32_t v = 0; v < N; ++v) off[v + 1] += off[v];
+        adj.assign((size_t)off[N], 0);
+        std::vector<int64_t> fill(off.begin(), off.end() - 1);
+        for (int64_t e = 0; e < m; ++e) if (basic[e]) { adj[fill[im.tail[e]]++] = (int32_t)e; adj[fill[im.head[e]]++] = (int32_t)e; }
+    };
+    auto dfs = [&]() -> bool {
+        std::vector<int8_t> seen(N, 0);
+        int32_t cnt = 0;
+        order[cnt++] = root; seen[root] = 1; parent[root] = -1; parc[root] = -1; depth[root] = 0;
+        for (int32_t r = 0; r < n; ++r) {
+            if (!rep[r]) continue;
+            if (seen[r]) return false;
+            seen[r] = 1; parent[r] = root; parc[r] = m + r; depth[r] = 1;
+            stack.clear(); stack.push_back(r);
+            while (!stack.empty()) {
+                const int32_t u = stack.back(); stack.pop_back();
+                order[cnt++] = u;
+                for (int64_t p = off[u + 1] - 1; p >= off[u]; --p) {
+                    const int32_t e = adj[p];
+                    const int32_t w = im.tail[e] == u ? im.head[e] : im.tail[e];
+                    if (seen[w]) continue;
+                    seen[w] = 1; parent[w] = u; parc[w] = e; depth[w] = depth[u] + 1;
+                    stack.push_back(w);
+                }
+            }
+        }
+        return cnt == N;
+    };
+    build_adj();
+    if (!dfs()) return "internal: basis does not span the nodes";
+    // --- the sweep: tree flows from conservation, children before parents; cut where a flow leaves its bounds
+    std::vector<int64_t> art_flow(n, 0);
+    std::vector<int8_t> art_up(n, 1);
+    const __int128 inf = MCF_INF;
+    auto hang_on_root = [&](int32_t v, __int128 x) -> bool {   // v's artificial arc carries the surplus x of its component
+        const __int128 ax = x < 0 ? -x : x;
+        if (ax >= inf) return false;
+        art_up[v] = x >= 0 ? 1 : 0;   // zero flow points at the root: strongly feasible
+        art_flow[v] = (int64_t)ax;
+        return true;
+    };
+    rr.rounds = 1;
+    for (int32_t k = N - 1; k >= 1; --k) {
+        const int32_t v = order[k];
+        const int64_t a = parc[v];
+        const __int128 x = bal[v];   // final: every child has been added
+        if (a >= m) {
+            if (!hang_on_root(v, x)) return "an artificial arc would carry 2^60 or more";
+            continue;
+        }
+        const bool up = im.tail[a] == v;
+        const int64_t cp = im.arcw[a].cap;
+        const __int128 f = up ? x : -x;
+        __int128 fc = f;
+        bool cut = false;
+        if (f < 0) { fc = 0; cut = true; ++rr.violations; }
+        else if (cp < MCF_INF && f > cp) { fc = cp; cut = true; ++rr.violations; }
+        else if (f >= inf) return "the flow of an uncapacitated tree arc would reach 2^60";
+        else if ((up && cp < MCF_INF && f == cp) || (!up && f == 0)) { cut = true; ++rr.wrong_way; }
+        flow[a] = (int64_t)fc;
+        const __int128 xc = up ? fc : -fc;
+        bal[parent[v]] += xc;
+        if (cut) {
+            basic[a] = 0;
+            rep[v] = 1;
+            ++rr.arcs_cut;
+            if (!hang_on_root(v, x - xc)) return "an artificial arc would carry 2^60 or more";
+        }
+    }
+    if (rr.arcs_cut > 0) {   // the cut subtrees hang on the root now: a new preorder (parents below the cuts are unchanged)
+        build_adj();
+        if (!dfs()) return "internal: repaired basis does not span the nodes";
+    }
+    // --- install: states, flows, records, preorder arrays, potentials (as mcf_apply_basis does)
+    for (int64_t e = 0; e < m; ++e) {
+        im.arcw[e].flow = flow[e];
+        const int64_t cp = im.arcw[e].cap;
+        im.state[e] = basic[e] ? 0 : ((flow[e] != 0 && flow[e] == cp) ? -1 : 1);
+    }
+    std::fill(im.weight.begin(), im.weight.end(), 1.0f);
+    for (int32_t v = 0; v < n; ++v) im.arcw[m + v] = McfArcW{MCF_INF, 0};
+    std::vector<int32_t> size(N, 1);
+    for (int32_t k = N - 1; k >= 1; --k) size[parent[order[k]]] += size[order[k]];
+    im.pi[root] = 0;
+    im.node[root] = McfNode{-1, -1, N, 0};
+    for (int32_t k = 0; k < N; ++k) {
+        const int32_t v = order[k];
+        im.order[k] = v;
+        im.pos[v] = k;
+        im.psize[k] = size[v];
+        if (v == root) continue;
+        const int64_t a = parc[v];
+        int32_t up;
+        int64_t c;
+        if (a >= m) { up = art_up[v]; c = im.big_m; im.arcw[a].flow = art_flow[v]; }
+        else { up = im.tail[a] == v ? 1 : 0; c = im.cost[a]; }
+        im.node[v] = McfNode{parent[v], (int32_t)((a << 1) | up), size[v], depth[v]};
+        im.pi[v] = up ? im.pi[parent[v]] - c : im.pi[parent[v]] + c;
+    }
+    if (report) *report = rr;
+    return "";
+}
+
 // resident reduced costs of the current image (values only; the adjacency does not depend on the basis)
 inline void mcf_refresh_rcache(McfHostImage& im) {
     if (im.rcache.empty()) return;

@@ -32,7 +32,7 @@ ABI_SYMBOLS = (
     "mcf_default_options", "mcf_create", "mcf_solve", "mcf_solve_batch", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs",
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
-    "mcf_certify", "mcf_bottlenecks",
+    "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs",
 )
 # mcf_certify: check groups and verdicts (include/mcf.h)
 CERT_BOUNDS, CERT_CONSERVATION, CERT_DUAL, CERT_OBJECTIVES, CERT_BASIS, CERT_PRICING = 1, 2, 4, 8, 16, 32
@@ -108,6 +108,14 @@ class McfCertificate(ctypes.Structure):
         return d
 
 
+class McfRhsReport(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "path", "tree_violations", "wrong_way", "arcs_cut", "repair_rounds", "art_flips", "upper_moved")] + [("device_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 PROGRESS_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double)
 
 _lib = None
@@ -138,6 +146,7 @@ def load_library():
     lib.mcf_reset.argtypes = [vp]
     lib.mcf_set_basis.argtypes = [vp, i8p, i8p]
     lib.mcf_update_costs.argtypes = [vp, ctypes.c_int64, i64p, i64p]
+    lib.mcf_update_rhs.argtypes = [vp, ctypes.c_int64, i64p, i64p, ctypes.c_int64, i64p, i64p, ctypes.POINTER(McfRhsReport)]
     lib.mcf_enqueue_price.argtypes = [vp, vp, vp]
     lib.mcf_enqueue_pivot.argtypes = [vp, vp, vp, ctypes.c_int32]
     lib.mcf_shard_info.argtypes = [vp, i32p, i32p]
@@ -163,7 +172,7 @@ def load_library():
     for name in ("mcf_create", "mcf_solve", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs", "mcf_enqueue_price",
                  "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing", "mcf_time_copy",
                  "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load",
-                 "mcf_certify", "mcf_bottlenecks"):
+                 "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs"):
         getattr(lib, name).restype = ctypes.c_int
     if lib.mcf_abi_version() != ABI_VERSION:
         raise EngineUnavailableError("libmcf_hip.so ABI version mismatch")
@@ -201,6 +210,7 @@ class McfEngine:
                  tree_blocks: int = 0, tree_pool: int = 0, rc_drop: int = 0, pivot_run: int = 0):
         self._h = None
         self._cost_private = False
+        self._rhs_private = False
         lib = load_library()
         if lib.mcf_device_count() <= 0:
             raise EngineUnavailableError("no HIP device visible; the network-simplex engine has no CPU fallback")
@@ -361,6 +371,28 @@ class McfEngine:
                 self.cost = self.cost.copy()
                 self._cost_private = True
             self.cost[a] = c               # (numpy assigns in order: the last entry wins here too)
+
+    def update_rhs(self, nodes=(), supplies=(), arcs=(), caps=()) -> dict:
+        """New integer supplies for the nodes ``nodes`` and new capacities (negative: uncapacitated) for the arcs ``arcs``
+        (this engine's orders; of duplicates the last entry wins), in one call.  The device-resident basis stays where its
+        tree flows, recomputed on the device, respect the new data; otherwise it is repaired (``mcf_update_rhs``).  Returns
+        the fields of ``mcf_rhs_report``: ``path`` 0 = basis kept, 1 = repaired, 2 = cold start."""
+        nd = np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)
+        sv = np.ascontiguousarray(supplies, dtype=np.int64).reshape(-1)
+        ar = np.ascontiguousarray(arcs, dtype=np.int64).reshape(-1)
+        cv = np.ascontiguousarray(caps, dtype=np.int64).reshape(-1)
+        if nd.shape[0] != sv.shape[0] or ar.shape[0] != cv.shape[0]:
+            raise ValueError("indices and values differ in length")
+        rep = McfRhsReport()
+        self._check(self._lib.mcf_update_rhs(self._h, int(nd.shape[0]), _p(nd, ctypes.c_int64), _p(sv, ctypes.c_int64),
+                                             int(ar.shape[0]), _p(ar, ctypes.c_int64), _p(cv, ctypes.c_int64), ctypes.byref(rep)))
+        if nd.shape[0] or ar.shape[0]:
+            if not self._rhs_private:      # the arrays may be the caller's own: copied once, on the first change
+                self.supply, self.cap = self.supply.copy(), self.cap.copy()
+                self._rhs_private = True
+            self.supply[nd] = sv           # (numpy assigns in order: the last entry wins here too)
+            self.cap[ar] = cv
+        return rep.as_dict()
 
     def last_error(self) -> str:
         return (self._lib.mcf_last_error(self._h) or b"").decode()

@@ -247,6 +247,122 @@ def map_cost_changes(flat: FlatProblem, changes, tolerance: float) -> tuple[np.n
     return idx, rounded.astype(np.int64), values
 
 
+def map_rhs_changes(flat: FlatProblem, supplies, capacities, tolerance: float):
+    """Supply and capacity changes in the caller's terms -> ``(node indices, integer engine supplies, supplies in caller
+    units, arc indices, integer engine capacities (-1: none), capacities in caller units (nan: none))`` in ``flat``'s
+    orders.  Pure: neither ``flat`` nor the changes are modified.  Either argument may be ``None``.
+
+    * object-model problems: ``supplies`` maps node id to the new supply, ``capacities`` maps ``(tail id, head id)`` to the
+      new capacity or ``None`` (of parallel arcs the LAST index takes it, as in ``map_cost_changes``).
+    * ``SoAProblem``: pairs ``(indices, values)`` of arrays; a negative capacity means none; of duplicates the last wins.
+
+    The resident instance keeps its ``flow_scale`` and its lower-bound shift (simplex.py:403-428): the engine's supply of a
+    node is ``(supply + shift) * flow_scale`` with the node's shift unchanged, the engine's capacity ``(capacity - lower) *
+    flow_scale``.  A value that is not an integer at that scale (to within ``tolerance``), a capacity below the arc's lower
+    bound or a supply vector that no longer balances is an ``InvalidProblemError`` with the reference's wording, and nothing
+    is returned."""
+    n, m = len(flat.node_ids), len(flat.keys)
+    scale = float(flat.flow_scale)
+
+    def pairs(changes, what, count):
+        try:
+            if hasattr(changes, "items"):
+                raise TypeError
+            idx_in, val_in = changes
+        except (TypeError, ValueError):
+            raise InvalidProblemError(f"{what} changes of an SoAProblem are a pair (indices, values) of arrays") from None
+        idx = np.asarray(idx_in).reshape(-1)
+        values = np.asarray(val_in, dtype=np.float64).reshape(-1)
+        if idx.shape[0] != values.shape[0]:
+            raise InvalidProblemError(f"{what} changes: indices and values differ in length")
+        if idx.size and not np.issubdtype(idx.dtype, np.integer):
+            raise InvalidProblemError(f"{what} changes: indices must be integers")
+        idx = idx.astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= count):
+            raise InvalidProblemError(f"{what} changes: index outside [0, {count})")
+        _, first_rev = np.unique(idx[::-1], return_index=True)      # the last entry of every index wins
+        keep = np.sort(idx.shape[0] - 1 - first_rev)
+        return idx[keep], values[keep]
+
+    def to_int(values, what, names):
+        if values.size and not np.all(np.isfinite(values)):
+            raise InvalidProblemError(f"{what} must be finite numbers")
+        scaled = values * scale
+        rounded = np.round(scaled)
+        off = np.abs(scaled - rounded) > tolerance * scale
+        if off.any():
+            i = int(np.nonzero(off)[0][0])
+            raise InvalidProblemError(
+                f"new {what} of {names(i)} is not a multiple of 1/{flat.flow_scale}, the flow resolution this solver was "
+                f"built with; build a new solver for finer values")
+        if rounded.size and np.abs(rounded).max() >= 2 ** 60:
+            raise SolverConfigurationError("scaled supplies / capacities must stay below 2^60")
+        return rounded.astype(np.int64)
+
+    empty_i, empty_f = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64)
+    # ---- supplies
+    if supplies is None:
+        s_idx, s_val = empty_i, empty_f
+    elif flat.soa:
+        s_idx, s_val = pairs(supplies, "supply", n)
+    else:
+        if not hasattr(supplies, "items"):
+            raise InvalidProblemError("supply changes are a mapping {node id: supply}")
+        index = {nid: i for i, nid in enumerate(flat.node_ids)}
+        for nid in supplies:
+            if nid not in index:
+                raise InvalidProblemError(f"supply change names node {nid!r} which is not in the problem")
+        s_idx = np.fromiter((index[nid] for nid in supplies), dtype=np.int64, count=len(supplies))
+        s_val = np.fromiter((float(v) for v in supplies.values()), dtype=np.float64, count=len(supplies))
+    shift = np.zeros(n, dtype=np.float64)                           # simplex.py:413-415, per node
+    if m and flat.lower.any():
+        np.subtract.at(shift, flat.tail, flat.lower)
+        np.add.at(shift, flat.head, flat.lower)
+    s_int = to_int(s_val + shift[s_idx], "supply", lambda i: f"node {flat.node_ids[int(s_idx[i])]}")
+    if s_idx.size:
+        new_supply = flat.supply.copy()
+        new_supply[s_idx] = s_int
+        residual = sum(int(x) for x in new_supply.tolist())
+        if residual != 0:
+            raise InvalidProblemError(
+                f"Supplies do not balance after lower-bound adjustment: total supply {residual / flat.flow_scale:.6f} "
+                f"exceeds tolerance {tolerance}.")
+    # ---- capacities
+    if capacities is None:
+        c_idx, c_val = empty_i, empty_f
+    elif flat.soa:
+        c_idx, c_val = pairs(capacities, "capacity", m)
+        c_val = np.where(c_val < 0, np.nan, c_val)
+    else:
+        if not hasattr(capacities, "items"):
+            raise InvalidProblemError("capacity changes are a mapping {(tail, head): capacity or None}")
+        last: dict[tuple[str, str], int] = {}
+        for i, key in enumerate(flat.keys):
+            last[key] = i
+        picked: dict[int, float] = {}
+        for key, value in capacities.items():
+            i = last.get(tuple(key))
+            if i is None:
+                raise InvalidProblemError(f"capacity change names arc {tuple(key)} which is not in the problem")
+            picked[i] = math.nan if value is None else float(value)
+        c_idx = np.fromiter(picked.keys(), dtype=np.int64, count=len(picked))
+        c_val = np.fromiter(picked.values(), dtype=np.float64, count=len(picked))
+    none = np.isnan(c_val)
+    if np.isinf(c_val).any():
+        raise InvalidProblemError("capacities must be finite numbers or None")
+    width = np.where(none, 0.0, c_val - flat.lower[c_idx])
+    low = width < -tolerance
+    if low.any():
+        i = int(np.nonzero(low)[0][0])
+        t, h = flat.keys[int(c_idx[i])]
+        raise InvalidProblemError(
+            f"Arc capacity ({c_val[i]:g}) is less than lower bound ({flat.lower[int(c_idx[i])]:g}) for arc "
+            f"{t} -> {h}. Capacity must be >= lower bound.")
+    c_int = to_int(np.maximum(width, 0.0), "capacity", lambda i: f"arc {flat.keys[int(c_idx[i])]}")
+    c_int[none] = -1
+    return s_idx, s_int, s_val, c_idx, c_int, c_val
+
+
 @dataclass
 class Certificate:
     """What ``NetworkSimplex.certify()`` returns; ``raw`` holds every field of ``mcf_certificate``."""
@@ -420,6 +536,52 @@ class NetworkSimplex:
             self.problem = replace(self.problem, nodes=dict(self.problem.nodes), arcs=arcs)
             self.flat = replace(f, cost=new_cost, orig_cost=orig_cost)
         return int(idx.shape[0])
+
+    def _update_rhs(self, supplies, capacities) -> dict:
+        f = self.flat
+        s_idx, s_int, s_val, c_idx, c_int, c_val = map_rhs_changes(f, supplies, capacities, self.tolerance)
+        report = self.engine.update_rhs(s_idx, s_int, c_idx, c_int)
+        new_supply, new_cap = f.supply.copy(), f.cap.copy()
+        new_supply[s_idx] = s_int
+        new_cap[c_idx] = c_int
+        if f.soa:
+            problem = copy.copy(self.problem)
+            if s_idx.size:
+                problem.supply = self.problem.supply.copy()
+                problem.supply[s_idx] = s_val.astype(self.problem.supply.dtype)
+            if c_idx.size:
+                problem.capacity = self.problem.capacity.copy()
+                problem.capacity[c_idx] = np.where(np.isnan(c_val), -1, c_val).astype(self.problem.capacity.dtype)
+            problem._arcs = None
+            self.problem = problem
+        else:
+            nodes = dict(self.problem.nodes)
+            for i, v in zip(s_idx.tolist(), s_val.tolist()):
+                nid = f.node_ids[i]
+                nodes[nid] = replace(nodes[nid], supply=v)
+            arcs = list(self.problem.arcs)
+            if c_idx.size:
+                # flat arc j is arc order[j] of the problem (flatten_problem: a stable sort by key)
+                order = sorted(range(len(arcs)), key=lambda i: (arcs[i].tail, arcs[i].head))
+                for j, c in zip(c_idx.tolist(), c_val.tolist()):
+                    arcs[order[j]] = replace(arcs[order[j]], capacity=None if math.isnan(c) else c)
+            self.problem = replace(self.problem, nodes=nodes, arcs=arcs)
+        self.flat = replace(f, supply=new_supply, cap=new_cap)
+        return report
+
+    def update_supplies(self, changes) -> dict:
+        """Change supplies / demands and keep the solved state (``mcf_update_rhs``): the tree flows of the resident basis
+        are recomputed on the device; where they respect the bounds the basis stays (a solved instance is optimal again in
+        zero pivots), otherwise it is repaired and the next ``solve()`` pivots on from it.  ``changes``: ``{node id:
+        supply}`` for an object-model problem, ``(indices, supplies)`` for an ``SoAProblem`` (``map_rhs_changes``; on an
+        invalid change nothing is changed).  The caller's problem object is left alone: ``self.problem`` becomes an updated
+        copy.  Returns the engine's report (``path`` 0 = basis kept, 1 = repaired, 2 = cold start)."""
+        return self._update_rhs(changes, None)
+
+    def update_capacities(self, changes) -> dict:
+        """Change arc capacities and keep the solved state, as ``update_supplies`` does.  ``changes``: ``{(tail, head):
+        capacity or None}`` for an object-model problem, ``(indices, capacities)`` (negative: none) for an ``SoAProblem``."""
+        return self._update_rhs(None, changes)
 
     def certify(self) -> "Certificate":
         """Certify the state resident on the device -- conservation, bounds, complementary slackness, exact objectives,
