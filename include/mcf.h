@@ -26,6 +26,8 @@
  *       when one of them leaves its bounds  simplex.py:99-265, 905-1010, 1491-1532 ...  mcf_update_rhs (the resident basis stays or is repaired)
  *   validate_flow / compute_bottleneck_arcs  utils.py:169-312 (conservation, bounds, arcs
  *       near capacity of a solution; the reference checks nothing on the dual side) ......  mcf_certify / mcf_bottlenecks
+ *   UnboundedProblemError / status "infeasible" carry no witness in the reference (exceptions.py:65-93 names the entering
+ *       arc, simplex.py:1600-1624 returns an empty flow): the ray and the cut that prove them ...  mcf_certify_ray / mcf_certify_cut
  *   AdaptiveTuner.adapt_block_size  simplex_adaptive.py:98-151 and the
  *       periodic Devex reset  simplex.py:1370-1400 ..........................  inside mcf_solve (MCF_RULE_DEVEX_BLOCK)
  *   specialised pivot strategies  specialized_pivots.py:69-424, 452-527 .....  mcf_options.key_mode (+ arc_priority): row scan,
@@ -380,7 +382,8 @@ int mcf_update_rhs(mcf_handle* h,
  *   verdict           what the evidence proves, all groups 1..8 evaluated: MCF_CERT_OPTIMAL = every primal and dual count
  *                     is 0, gap is 0, no artificial flow; MCF_CERT_INFEASIBLE = the same with artificial flow > 0 (the
  *                     flow is optimal for the big-M problem over the arcs the basis still holds); else MCF_CERT_NOT_PROVEN.
- *                     An unbounded status needs a ray, which is outside this call: always MCF_CERT_NOT_PROVEN.
+ *                     An unbounded status is proven by its ray, mcf_certify_ray below (this call keeps answering
+ *                     MCF_CERT_NOT_PROVEN for it); an infeasible one is proven for the CALLER'S instance by mcf_certify_cut.
  *                     proves_status = 1 when the handle's status is optimal / infeasible and the verdict says the same.
  *   errors            MCF_E_BAD_ARG: null handle, null out, unknown bits in checks.  MCF_E_NO_DEVICE as elsewhere.
  * Scratch (partials, uploads, supplies: 8 B per node, an adjacency where the handle holds none or a shard's only) is
@@ -430,6 +433,101 @@ int mcf_certify(mcf_handle* h, const int64_t* flow, const int64_t* potential, ui
  * *count <- how many there are; idx_out[0 .. min(count, idx_cap)) <- their caller's indices in ascending order, compacted
  * on the device (idx_out may be NULL with idx_cap 0).  Read-only like mcf_certify. */
 int mcf_bottlenecks(mcf_handle* h, const int64_t* flow, int64_t num, int64_t den, int64_t* idx_out, int64_t idx_cap, int64_t* count);
+
+/* ---- witnesses of the other two verdicts, evaluated on the device.  Both calls are read-only exactly as mcf_certify is
+ * (nothing the solver reads is written; a later mcf_solve makes the same pivots) and valid where it is valid: between solves
+ * in any state of the handle, on every engine path (fused LDS loop, persistent mid loop, graphs, handles solved by
+ * mcf_solve_batch), both tree layouts, every rule and key_mode, handles that dropped their resident reduced costs, and
+ * handles with shard_count > 1 (the state is replicated).  Everything is checked before any device work is queued; after an
+ * error the handle is exactly as it was.  Scratch is allocated on first use and freed by mcf_destroy.
+ *
+ * mcf_certify_ray -- the cycle a NON-BASIC arc closes with the resident tree, classified for the push along it.
+ *   arc          caller's index, or -1 = the handle's unbounded arc (mcf_stats.unbounded_arc; MCF_E_STATE when the status is
+ *                not MCF_ST_UNBOUNDED).  A basic arc or an index outside [0, m): MCF_E_BAD_ARG, as are a null handle, a
+ *                null out, idx_cap < 0 and a null idx_out with idx_cap > 0.
+ *   direction    from the arc's state: at its lower bound it is pushed forward (tail -> head); at capacity it is pushed
+ *                backward, entering_backward = 1, and it can then never be a ray.  With t / hd the end point the push
+ *                leaves from / arrives at (tail / head forward, head / tail backward) the push runs
+ *                hd -> ... -> join -> ... -> t and closes through the arc.
+ *   membership   node u is an ancestor-or-self of x iff pos[u] <= pos[x] < pos[u] + size[u] (logical preorder positions,
+ *                dense array and blocked list alike), and u's tree arc is on the cycle iff that holds for exactly one of
+ *                t and hd: one lane per node, one pass over the node records, no pointer is chased.  The join is the
+ *                deepest node for which it holds for both.
+ *   per arc      sense of traversal against the arc's own direction, artificial or not, capped or not, its signed cost
+ *                (-cost against the direction; an artificial arc costs big-M) and its residual in the push direction
+ *                (cap - flow forward, flow backward, 2^60 when there is none).
+ *   idx_out      idx_out[0 .. min(length, idx_cap)) <- the cycle in push order: the arc itself, the tree arcs from hd up
+ *                to the join, those from the join down to t (caller's indices; m + v for the artificial arc of node v,
+ *                as in mcf_get_tree).  May be NULL with idx_cap 0. */
+typedef struct mcf_ray {
+    int64_t arc;               /* caller's index of the arc examined */
+    int64_t entering_backward; /* 1 = the arc sits at its capacity and is pushed against its direction */
+    int64_t length;            /* arcs on the cycle, `arc` included */
+    int64_t join;              /* the node where the two tree paths meet */
+    int64_t backward_count;    /* TREE arcs traversed against their direction */
+    int64_t capped_count;      /* arcs of the cycle (`arc` included) that have a capacity */
+    int64_t artificial_count;  /* artificial arcs on the cycle */
+    int64_t cost;              /* signed sum of the costs round the cycle: fewer than 2^30 arcs below 2^44 each */
+    int64_t reduced_cost;      /* cost[arc] + pi[tail] - pi[head] from the resident potentials, negated when entering_backward: the
+                                  reduced cost in the push direction (mcf_stats.unbounded_rc).  Equals `cost` whenever every tree arc
+                                  has reduced cost 0 (mcf_certificate.tree_rc_count == 0) */
+    int64_t theta;             /* smallest residual on the cycle, 2^60 = no bound */
+    int64_t theta_arc;         /* first arc attaining it (ties: lowest index, artificial arcs as m + v), -1 = none */
+    int64_t proven;            /* 1 iff entering_backward, backward_count, capped_count and artificial_count are all 0 and cost < 0:
+                                  a directed cycle of real, uncapacitated arcs of negative cost in the caller's instance, which any
+                                  feasible flow can be pushed along for ever */
+    double device_ms;          /* HIP events round the device passes */
+} mcf_ray;
+
+int mcf_certify_ray(mcf_handle* h, int64_t arc /* caller's index; -1 = the handle's unbounded arc */,
+                    int64_t* idx_out, int64_t idx_cap, mcf_ray* out);
+
+/* mcf_certify_cut -- a node set S whose net supply exceeds what the arcs leaving it can carry (Gale's condition): the
+ * textbook witness of infeasibility, checkable from tail / head / cap / supply alone, whatever the solver did.
+ *   in_S == NULL   S is computed from the resident flow: the real nodes reachable in the RESIDUAL GRAPH OF THE REAL ARCS
+ *                  from the seeds.  A seed is a node whose artificial arc v -> root carries flow; arc (a, b) extends S from
+ *                  a to b while flow < cap or it is uncapacitated, from b to a while flow > 0; artificial arcs are never
+ *                  traversed.  S is the least fixpoint and depends on no launch geometry or visiting order.  It is built
+ *                  level by level over the node -> arc adjacency (the handle's, or the certificate's own, built on first
+ *                  use): every adjacency list is expanded once, marks are idempotent stores, the rounds are queued on the
+ *                  engine's stream in batches of 32 with one look at the "deepest level" word per batch, and the loop is
+ *                  bounded by n rounds in code.
+ *   in_S != NULL   the caller's set (in_S[v] != 0: v is in S).  No search is run and no flow is read: valid in any state of
+ *                  the handle, a fresh one included -- a cut is a property of the instance alone.  seeds, rounds,
+ *                  deficit_in_S, leaving_unsaturated, entering_with_flow and artificial_out are then 0.
+ *   evaluation     one streaming pass over the arcs in engine order (bucketed by head, non-temporal loads from 4 M arcs
+ *                  on, as in mcf_certify), one pass over the nodes, 128-bit sums merged in any order.
+ *   S_out          S_out[v] <- 1 / 0 for every real node (may be NULL); one byte per node crosses the bus.
+ *   why it works   at an "infeasible" verdict that mcf_certify attests, the computed S holds no node whose artificial arc
+ *                  root -> v carries flow: a residual path from a seed to such a node would close, through the two artificial
+ *                  arcs -- both still basic, since they carry flow --, a cycle of cost (path) - 2 big-M < 0, which the
+ *                  optimality of the big-M problem excludes.  No leaving arc has room and no entering arc carries flow (S is
+ *                  closed), so conservation over S reads supply(S) - capacity(leaving) = artificial_out: excess ==
+ *                  artificial_out > 0, and the capacities are finite.  A handle without seeds (optimal, fresh) has an empty S
+ *                  and proven = 0: MCF_OK, not an error.  A mid-solve handle may show deficit_in_S > 0 or leaving arcs with
+ *                  room: what is there is reported.
+ *   errors         MCF_E_BAD_ARG: null handle, null out. */
+typedef struct mcf_cut {
+    int64_t seeds;                  /* nodes of S whose artificial arc v -> root carries flow */
+    int64_t nodes_in_S;
+    int64_t rounds;                 /* levels of the search (rounds that found a frontier to expand) */
+    int64_t deficit_in_S;           /* nodes of S whose artificial arc root -> v carries flow */
+    int64_t leaving_arcs;           /* arcs with their tail in S and their head outside */
+    int64_t leaving_uncapacitated;
+    int64_t leaving_unsaturated;    /* leaving arcs with room under the resident flow (uncapacitated, or flow < cap) */
+    int64_t entering_with_flow;     /* arcs into S that carry resident flow */
+    int64_t capacity[2];            /* {high, low}: sum of the capacities of the capped leaving arcs */
+    int64_t supply[2];              /* sum of the supplies over S */
+    int64_t excess[2];              /* supply - capacity */
+    int64_t artificial_out[2];      /* artificial flow S -> root minus root -> S (resident flow).  NOT mcf_stats.artificial_flow: that
+                                       adds up the artificial arcs of both senses, and what goes to the root equals what comes from
+                                       it, so at an attested "infeasible" verdict artificial_flow == 2 * artificial_out == 2 * excess */
+    int64_t proven;                 /* 1 iff leaving_uncapacitated == 0 and excess > 0 */
+    double device_ms;               /* HIP events round the device passes (search and evaluation) */
+} mcf_cut;
+
+int mcf_certify_cut(mcf_handle* h, const int8_t* in_S /* [n] caller's set, or NULL = compute from the resident flow */,
+                    int8_t* S_out /* [n] or NULL */, mcf_cut* out);
 
 /* ---- arc-sharded multi-GPU pivoting: one handle per rank, every rank holds the full
  * replicated state and prices only its shard (options.shard_rank / shard_count).  Per pivot:

@@ -33,7 +33,7 @@ from .exceptions import (
 )
 from .simplex import NetworkSimplex
 from .solver import load_problem, save_result, solve_many, solve_min_cost_flow
-from .utils import BottleneckArc, ValidationResult, compute_bottleneck_arcs, validate_flow
+from .utils import BottleneckArc, InfeasibleCut, UnboundedRay, ValidationResult, compute_bottleneck_arcs, validate_flow
 
 __all__ = [
     "Arc", "Basis", "FlowResult", "NetworkProblem", "Node", "ProgressCallback", "ProgressInfo", "SoAProblem", "SolverOptions",
@@ -42,7 +42,7 @@ __all__ = [
     "SolverConfigurationError", "UnboundedProblemError", "NetworkSimplex", "load_problem", "save_result",
     "solve_many",
     "solve_min_cost_flow",
-    "BottleneckArc", "ValidationResult", "compute_bottleneck_arcs", "validate_flow",
+    "BottleneckArc", "ValidationResult", "compute_bottleneck_arcs", "validate_flow", "InfeasibleCut", "UnboundedRay",
 ]
 
 __version__ = "0.1.0"

@@ -1978,3 +1978,114 @@ MCF_HD void mcf_cert_arc_resident(McfCertArcAcc* a, uint32_t checks, int64_t cap
 MCF_HD void mcf_cert_node_balance(McfCertNodeAcc* a, int64_t node, __int128 bal) {
     if (bal != 0) { ++a->imb_n; mcf_cert_worst(&a->imb_w, &a->imb_i, mcf_cert_mag128(bal), node); }
 }
+
+// ====================================================================== witnesses of the other two verdicts (include/mcf.h)
+// mcf_certify_ray: the cycle a non-basic arc closes with the resident tree, classified arc by arc for the push along it;
+// mcf_certify_cut: a node set S, its leaving capacity against its net supply.  As for the certificate above, the per-arc /
+// per-node logic lives here, shared by the kernels (mcf_engine.hip: k_ray_*, k_cut_*) and the host restatement of the CPU
+// tests (csrc/mcf_farkas_host.cpp), and every partial combines by an integer sum, a min / max with the lowest index, or a
+// 128-bit sum: no merge order can change a bit of the result.
+struct McfRayAcc {
+    int64_t tree_n;                  // tree arcs on the cycle (the cycle's length is tree_n + 1)
+    int64_t back_n, cap_n, art_n;    // tree arcs traversed against their direction; arcs with a capacity; artificial arcs
+    int64_t cost;                    // signed sum: -cost of an arc traversed backward (< 2^30 arcs of < 2^44 each)
+    int64_t rc;                      // the entering arc's reduced cost in the push direction (set by the one lane that has it)
+    int64_t theta, theta_i;          // smallest residual in the push direction (MCF_INF: none), first arc attaining it
+    int64_t join_d, join_i;          // depth + 1 of the deepest common ancestor of the two end points, and that node
+};
+#define MCF_RAY_WORDS ((int)(sizeof(McfRayAcc) / 8))
+
+MCF_HD void mcf_ray_init(McfRayAcc* a) {
+    a->tree_n = a->back_n = a->cap_n = a->art_n = a->cost = a->rc = 0;
+    a->theta = MCF_INF; a->theta_i = MCF_CERT_NONE;
+    a->join_d = 0; a->join_i = MCF_CERT_NONE;
+}
+MCF_HD void mcf_ray_min(int64_t* w, int64_t* wi, int64_t r, int64_t idx) {
+    if (r < MCF_INF && (r < *w || (r == *w && idx < *wi))) { *w = r; *wi = idx; }
+}
+MCF_HD void mcf_ray_merge(McfRayAcc* a, const McfRayAcc& b) {
+    a->tree_n += b.tree_n; a->back_n += b.back_n; a->cap_n += b.cap_n; a->art_n += b.art_n; a->cost += b.cost; a->rc += b.rc;
+    mcf_ray_min(&a->theta, &a->theta_i, b.theta, b.theta_i);
+    mcf_cert_worst(&a->join_d, &a->join_i, b.join_d, b.join_i);
+}
+
+// Where node u (preorder position pos_u, subtree size size_u) stands to the cycle of an arc whose push arrives at `first`
+// and leaves from `second`: u is an ancestor-or-self of x iff pos_u <= pos_x < pos_u + size_u.
+//   0 = of neither end point: off the cycle;   1 = of `first` only: u's tree arc is climbed, u -> parent;
+//   2 = of `second` only: u's tree arc is descended, parent -> u;   3 = of both: at or above the join, off the cycle.
+MCF_HD int mcf_ray_side(int32_t pos_u, int32_t size_u, int32_t pos_first, int32_t pos_second) {
+    const bool f = pos_u <= pos_first && (int64_t)pos_first < (int64_t)pos_u + size_u;
+    const bool s = pos_u <= pos_second && (int64_t)pos_second < (int64_t)pos_u + size_u;
+    return (f ? 1 : 0) | (s ? 2 : 0);
+}
+
+// One arc of the cycle.  idx: the caller's arc index, m + v for the artificial arc of node v; forward: the push follows the
+// arc's own direction; cap: MCF_INF when uncapacitated (every artificial arc).  Residual in the push direction: cap - flow
+// forward (none on an uncapacitated arc), flow backward.
+MCF_HD void mcf_ray_arc(McfRayAcc* a, int64_t idx, bool tree_arc, bool artificial, bool forward, int64_t cost, int64_t cap, int64_t flow) {
+    if (tree_arc) { ++a->tree_n; if (!forward) ++a->back_n; }
+    if (artificial) ++a->art_n;
+    if (cap < MCF_INF) ++a->cap_n;
+    a->cost += forward ? cost : -cost;
+    mcf_ray_min(&a->theta, &a->theta_i, forward ? (cap < MCF_INF ? cap - flow : MCF_INF) : flow, idx);
+}
+
+// The push along the cycle can go on for ever and lowers the objective all the way: every arc real, followed forward,
+// uncapacitated, and the cycle's cost negative (tests/verdict_instances.py: unbounded_certificate makes the same assertions).
+MCF_HD bool mcf_ray_proven(const McfRayAcc& a, bool entering_backward) {
+    return !entering_backward && a.back_n == 0 && a.cap_n == 0 && a.art_n == 0 && a.cost < 0;
+}
+
+struct McfCutAcc {
+    int64_t seeds, in_s, deficit;                          // nodes of S: sending artificial flow to the root, all, receiving it
+    int64_t leave_n, leave_uncap, leave_unsat, enter_flow; // arcs S -> rest: all, uncapacitated, with room left; arcs rest -> S carrying flow
+    uint64_t cap_lo, cap_hi;                               // sum of the capacities of the capped leaving arcs
+    uint64_t sup_lo, sup_hi;                               // sum of the supplies over S
+    uint64_t art_lo, art_hi;                               // artificial flow S -> root minus root -> S
+};
+#define MCF_CUT_WORDS ((int)(sizeof(McfCutAcc) / 8))
+
+MCF_HD void mcf_cut_init(McfCutAcc* a) {
+    uint64_t* p = reinterpret_cast<uint64_t*>(a);
+    for (int k = 0; k < MCF_CUT_WORDS; ++k) p[k] = 0;
+}
+MCF_HD void mcf_cut_merge(McfCutAcc* a, const McfCutAcc& b) {
+    a->seeds += b.seeds; a->in_s += b.in_s; a->deficit += b.deficit;
+    a->leave_n += b.leave_n; a->leave_uncap += b.leave_uncap; a->leave_unsat += b.leave_unsat; a->enter_flow += b.enter_flow;
+    mcf_cert_add128(&a->cap_lo, &a->cap_hi, ((mcf_u128)b.cap_hi << 64) | b.cap_lo);
+    mcf_cert_add128(&a->sup_lo, &a->sup_hi, ((mcf_u128)b.sup_hi << 64) | b.sup_lo);
+    mcf_cert_add128(&a->art_lo, &a->art_hi, ((mcf_u128)b.art_hi << 64) | b.art_lo);
+}
+
+// The relaxation step of the residual search: does the arc (cap, flow) carry the set on from the end point it was reached
+// at to its other end?  From its tail while it has room (uncapacitated, or flow < cap), from its head while it carries flow.
+MCF_HD bool mcf_cut_extends(bool from_tail, int64_t cap, int64_t flow) {
+    return from_tail ? (cap >= MCF_INF || flow < cap) : flow > 0;
+}
+
+// One arc against the set.  resident = 0: the caller's set on the instance alone, the flow plays no part.
+MCF_HD void mcf_cut_arc(McfCutAcc* a, bool tail_in, bool head_in, int64_t cap, int64_t flow, bool resident) {
+    if (tail_in && !head_in) {
+        ++a->leave_n;
+        if (cap >= MCF_INF) ++a->leave_uncap;
+        else mcf_cert_add128(&a->cap_lo, &a->cap_hi, (mcf_u128)(__int128)cap);
+        if (resident && mcf_cut_extends(true, cap, flow)) ++a->leave_unsat;
+    } else if (head_in && !tail_in) {
+        if (resident && mcf_cut_extends(false, cap, flow)) ++a->enter_flow;
+    }
+}
+
+// One node of the set.  art: the flow of the node's artificial arc, > 0 towards the root, < 0 from it (0: not resident).
+MCF_HD void mcf_cut_node(McfCutAcc* a, int64_t supply, int64_t art) {
+    ++a->in_s;
+    mcf_cert_add128(&a->sup_lo, &a->sup_hi, (mcf_u128)(__int128)supply);
+    if (art > 0) ++a->seeds;
+    if (art < 0) ++a->deficit;
+    mcf_cert_add128(&a->art_lo, &a->art_hi, (mcf_u128)(__int128)art);
+}
+
+// Gale's condition: no uncapacitated arc leaves S and S supplies more than the leaving arcs can carry.
+MCF_HD bool mcf_cut_proven(const McfCutAcc& a, __int128* excess) {
+    *excess = (__int128)(((mcf_u128)a.sup_hi << 64) | a.sup_lo) - (__int128)(((mcf_u128)a.cap_hi << 64) | a.cap_lo);
+    return a.leave_uncap == 0 && *excess > 0;
+}

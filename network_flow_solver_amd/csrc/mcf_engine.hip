@@ -2301,6 +2301,178 @@ __global__ __launch_bounds__(kCertThreads) void k_bn_write(const uint8_t* __rest
     }
 }
 
+// ------------------------------------------------------------------ witnesses (mcf_certify_ray / mcf_certify_cut)
+// k_ray_nodes   one lane per node record (16 B) + its preorder position (4 B dense; 4 + 8 B blocked: slot, block base): the
+//               interval test against the two end points says whether the node's tree arc is on the cycle and on which
+//               side; only the <= length lanes that are read the arc's walk record (16 B), cost and caller's index.
+// k_ray_final   one workgroup merges the per-workgroup partials.
+// k_ray_write   the same pass once more, now that the length is known: a node of the arriving side lands at
+//               1 + depth[first] - depth[u], one of the leaving side at length - 1 - (depth[second] - depth[u]).  8 B per cycle arc out.
+// k_cut_seed    one lane per node: node record + artificial walk record in, a 4 B level mark out (1 = seed, 0 = not reached).
+// k_cut_round   round r: one lane per node reads its mark (4 B); the lanes at level r walk their adjacency list (8 B per entry +
+//               the arc's 16 B walk record + the other end's mark) and mark what the residual arcs reach with r + 1.  Every list
+//               is expanded in exactly one round; all lanes that reach a node in a round store the same value.
+// k_cut_arcs    the streaming pass of k_cert_arcs: tail, head (4 B each), the walk record (16 B), two gathered marks.
+// k_cut_nodes   one lane per node: mark, supply (8 B), node record and artificial walk record of the nodes of S.
+constexpr int kCutBatch = 32;   // rounds queued between two looks at the level word
+
+__global__ __launch_bounds__(kCertThreads) void k_ray_nodes(McfView v, CertArgs a, int64_t e, int32_t backward, McfRayAcc* __restrict__ part) {
+    __shared__ McfRayAcc s_wave[kCertThreads / 64];
+    const int32_t N = v.n_nodes;
+    const int64_t m = v.m;
+    const int32_t t = v.tail[e], hd = v.head[e];
+    const int32_t first = backward ? t : hd, second = backward ? hd : t;
+    int32_t slot = 0;
+    const int32_t pf = cert_pos(v, a, first, &slot), ps = cert_pos(v, a, second, &slot);
+    McfRayAcc acc;
+    mcf_ray_init(&acc);
+    if (pf >= 0 && ps >= 0) {
+        for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
+            const McfNode nd = v.node[u];
+            const int32_t pu = cert_pos(v, a, u, &slot);
+            if (pu < 0) continue;
+            const int side = mcf_ray_side(pu, nd.size, pf, ps);
+            if (side == 3) mcf_cert_worst(&acc.join_d, &acc.join_i, (int64_t)nd.depth + 1, u);
+            else if (side && nd.pred >= 0) {
+                const int64_t arc = nd.pred >> 1;
+                const bool up = (nd.pred & 1) != 0;
+                const bool forward = side == 1 ? up : !up;
+                if (arc < m) {
+                    const McfArcW w = v.arcw[arc];
+                    mcf_ray_arc(&acc, v.orig[arc], true, false, forward, v.cost[arc], w.cap, w.flow);
+                } else if (arc < m + N - 1) {
+                    mcf_ray_arc(&acc, arc, true, true, forward, a.bigm, MCF_INF, v.arcw[arc].flow);
+                }
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const McfArcW w = v.arcw[e];
+        const int64_t cost = v.cost[e];
+        mcf_ray_arc(&acc, v.orig[e], false, false, !backward, cost, w.cap, w.flow);
+        const int64_t rc = cost + a.pi[t] - a.pi[hd];
+        acc.rc = backward ? -rc : rc;
+    }
+    cert_block_reduce<McfRayAcc, MCF_RAY_WORDS>(acc, s_wave, [](McfRayAcc* p, const McfRayAcc& q) { mcf_ray_merge(p, q); });
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// part[0 .. n) -> part[n]
+__global__ __launch_bounds__(kCertThreads) void k_ray_final(McfRayAcc* __restrict__ part, int n) {
+    __shared__ McfRayAcc s_wave[kCertThreads / 64];
+    McfRayAcc acc;
+    mcf_ray_init(&acc);
+    for (int i = threadIdx.x; i < n; i += kCertThreads) mcf_ray_merge(&acc, part[i]);
+    cert_block_reduce<McfRayAcc, MCF_RAY_WORDS>(acc, s_wave, [](McfRayAcc* p, const McfRayAcc& q) { mcf_ray_merge(p, q); });
+    if (threadIdx.x == 0) part[n] = acc;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_ray_write(McfView v, CertArgs a, int64_t e, int32_t backward, const McfRayAcc* __restrict__ total,
+                                                            int64_t* __restrict__ idx, int64_t idx_cap) {
+    const int32_t N = v.n_nodes;
+    const int64_t m = v.m;
+    const int32_t t = v.tail[e], hd = v.head[e];
+    const int32_t first = backward ? t : hd, second = backward ? hd : t;
+    int32_t slot = 0;
+    const int32_t pf = cert_pos(v, a, first, &slot), ps = cert_pos(v, a, second, &slot);
+    const int64_t length = total->tree_n + 1;
+    const int64_t df = v.node[first].depth, ds = v.node[second].depth;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && idx_cap > 0) idx[0] = v.orig[e];
+    if (pf < 0 || ps < 0) return;
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
+        const McfNode nd = v.node[u];
+        const int32_t pu = cert_pos(v, a, u, &slot);
+        if (pu < 0 || nd.pred < 0) continue;
+        const int side = mcf_ray_side(pu, nd.size, pf, ps);
+        if (side != 1 && side != 2) continue;
+        const int64_t arc = nd.pred >> 1;
+        const int64_t at = side == 1 ? 1 + df - nd.depth : length - 1 - (ds - nd.depth);
+        if (at >= 1 && at < idx_cap && at < length) idx[at] = arc < m ? (int64_t)v.orig[arc] : arc;
+    }
+}
+
+// the flow of node u's artificial arc, > 0 towards the root, < 0 from it (a non-basic one carries nothing and counts as "up")
+__device__ __forceinline__ int64_t cut_art(const McfView& v, int32_t u) {
+    const McfNode nd = v.node[u];
+    const int64_t af = v.arcw[v.m + u].flow;
+    const bool up = (int64_t)(nd.pred >> 1) == v.m + u ? (nd.pred & 1) != 0 : true;
+    return up ? af : -af;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_cut_seed(McfView v, int32_t* __restrict__ mark, int32_t* __restrict__ level) {
+    const int32_t n = v.n_nodes - 1;
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) {
+        const bool seed = cut_art(v, u) > 0;
+        mark[u] = seed ? 1 : 0;
+        if (seed) *level = 1;
+    }
+}
+
+// mark[] is read while other lanes store r + 1 into entries that hold 0: a lane sees 0 or r + 1 there, and either is right
+__global__ __launch_bounds__(kCertThreads) void k_cut_round(McfView v, const int64_t* __restrict__ adj_off, const int64_t* __restrict__ adj,
+                                                            int32_t* mark, int32_t* __restrict__ level, int32_t r) {
+    const int32_t n = v.n_nodes - 1;
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) {
+        if (mark[u] != r) continue;
+        for (int64_t k = adj_off[u]; k < adj_off[u + 1]; ++k) {
+            const int64_t w = adj[k];
+            const int32_t other = (int32_t)(w >> 32);
+            if (other < 0 || other >= n || mark[other] != 0) continue;
+            const McfArcW aw = v.arcw[(w & 0xffffffff) >> 1];
+            if (mcf_cut_extends((w & 1) != 0, aw.cap, aw.flow)) { mark[other] = r + 1; *level = r + 1; }
+        }
+    }
+}
+
+// the caller's set, one byte per node, into level marks (1 / 0) -- and the marks back into bytes for S_out
+__global__ __launch_bounds__(kCertThreads) void k_cut_widen(const int8_t* __restrict__ in, int32_t n, int32_t* __restrict__ mark) {
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) mark[u] = in[u] != 0 ? 1 : 0;
+}
+__global__ __launch_bounds__(kCertThreads) void k_cut_narrow(const int32_t* __restrict__ mark, int32_t n, int8_t* __restrict__ out) {
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) out[u] = mark[u] != 0 ? 1 : 0;
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kCertThreads) void k_cut_arcs(McfView v, const int32_t* __restrict__ mark, int32_t resident, McfCutAcc* __restrict__ part) {
+    __shared__ McfCutAcc s_wave[kCertThreads / 64];
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+    McfCutAcc acc;
+    mcf_cut_init(&acc);
+    for (int64_t e = lo + lb * kCertThreads + threadIdx.x; e < hi; e += nlb * kCertThreads) {
+        const int32_t t = cert_ld<NT>(v.tail + e), hd = cert_ld<NT>(v.head + e);
+        const bool tin = mark[t] != 0, hin = mark[hd] != 0;
+        if (tin == hin) continue;
+        const int64_t* aw = reinterpret_cast<const int64_t*>(v.arcw + e);
+        mcf_cut_arc(&acc, tin, hin, cert_ld<NT>(aw), cert_ld<NT>(aw + 1), resident != 0);
+    }
+    cert_block_reduce<McfCutAcc, MCF_CUT_WORDS>(acc, s_wave, [](McfCutAcc* p, const McfCutAcc& q) { mcf_cut_merge(p, q); });
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_cut_nodes(McfView v, const int32_t* __restrict__ mark, const int64_t* __restrict__ supply, int32_t resident,
+                                                            McfCutAcc* __restrict__ part) {
+    __shared__ McfCutAcc s_wave[kCertThreads / 64];
+    const int32_t n = v.n_nodes - 1;
+    McfCutAcc acc;
+    mcf_cut_init(&acc);
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads)
+        if (mark[u] != 0) mcf_cut_node(&acc, supply[u], resident ? cut_art(v, u) : 0);
+    cert_block_reduce<McfCutAcc, MCF_CUT_WORDS>(acc, s_wave, [](McfCutAcc* p, const McfCutAcc& q) { mcf_cut_merge(p, q); });
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// part[0 .. n) -> part[n]
+__global__ __launch_bounds__(kCertThreads) void k_cut_final(McfCutAcc* __restrict__ part, int n) {
+    __shared__ McfCutAcc s_wave[kCertThreads / 64];
+    McfCutAcc acc;
+    mcf_cut_init(&acc);
+    for (int i = threadIdx.x; i < n; i += kCertThreads) mcf_cut_merge(&acc, part[i]);
+    cert_block_reduce<McfCutAcc, MCF_CUT_WORDS>(acc, s_wave, [](McfCutAcc* p, const McfCutAcc& q) { mcf_cut_merge(p, q); });
+    if (threadIdx.x == 0) part[n] = acc;
+}
+
 // ------------------------------------------------------------------ mcf_update_rhs: new supplies / capacities under a resident basis
 // Flows and states of non-basic arcs do not depend on supplies; tree flows are subtree sums of node balances, and a
 // subtree is a contiguous range of the preorder.  Bytes each pass moves (n nodes, m arcs, k changes):
@@ -2583,6 +2755,13 @@ struct mcf_handle {
     int64_t* d_bn_off = nullptr;
     int64_t* d_bn_idx = nullptr;
     int64_t bn_idx_cap = 0;
+    // mcf_certify_ray / mcf_certify_cut: everything allocated on first use (events, supplies and adjacency are the certificate's)
+    McfRayAcc* d_ray_part = nullptr;                       // [kCertMaxBlocks + 1] per-workgroup partials, then the total
+    int64_t* d_ray_idx = nullptr;                          // [n_nodes] the cycle in push order
+    int32_t* d_cut_mark = nullptr;                         // [n] level at which the search reached the node, 0 = not in S
+    int32_t* d_cut_level = nullptr;                        // [1] deepest level so far
+    int8_t* d_cut_byte = nullptr;                          // [n] the caller's set going in, S_out coming back
+    McfCutAcc* d_cut_part = nullptr;                       // [2 * kCertMaxBlocks + 1] arc partials, node partials, the total
     // mcf_update_rhs: everything allocated on first use (supplies and adjacency are the certificate's, jump records mcf_update_costs')
     std::vector<uint32_t> rhs_nstamp;                      // per node: the call that last named it
     int32_t* d_rhs_idx = nullptr;                          // changed nodes, then changed arcs (engine indices)
@@ -3024,6 +3203,7 @@ void free_all(mcf_handle* h) {
     (void)hipFree(h->d_bn_flag); (void)hipFree(h->d_bn_cnt); (void)hipFree(h->d_bn_off); (void)hipFree(h->d_bn_idx);
     for (hipEvent_t e : h->ct_ev) if (e) (void)hipEventDestroy(e);
     (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost); (void)hipFree(h->d_uc_jump[0]); (void)hipFree(h->d_uc_jump[1]); (void)hipFree(h->d_uc_info);
+    (void)hipFree(h->d_ray_part); (void)hipFree(h->d_ray_idx); (void)hipFree(h->d_cut_mark); (void)hipFree(h->d_cut_level); (void)hipFree(h->d_cut_byte); (void)hipFree(h->d_cut_part);
     (void)hipFree(h->d_rhs_idx); (void)hipFree(h->d_rhs_val); (void)hipFree(h->d_rhs_bal); (void)hipFree(h->d_rhs_part); (void)hipFree(h->d_rhs_info);
     if (h->h_ctx) pinned_give(reinterpret_cast<char*>(h->h_ctx));   // (h_one lives in the same slot)
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
@@ -3043,8 +3223,8 @@ int cert_upload_flow(mcf_handle* h, const int64_t* flow, const int64_t** dev) {
 // (lazy scratch is allocated in groups; a group that could not be completed is given back whole)
 template <typename T> void cert_free(T** p) { (void)hipFree(*p); *p = nullptr; }
 
-// what the certificate needs beyond the solver's arrays: supplies, a FULL adjacency, partial buffers, events
-int cert_prepare(mcf_handle* h) {
+// what the certificate needs beyond the solver's arrays: supplies, a FULL adjacency (need_adj), partial buffers, events
+int cert_prepare(mcf_handle* h, bool need_adj = true) {
     const McfHostImage& im = h->im;
     if (!h->d_ct_supply) {
         if (dalloc(&h->d_ct_supply, (size_t)im.n) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc supplies"; return MCF_E_ALLOC; }
@@ -3053,7 +3233,7 @@ int cert_prepare(mcf_handle* h) {
         }
     }
     const bool own_adj = h->d_adj && !h->view.rc_partial;   // (h->view.adj goes away with dropped reduced costs; the arrays stay)
-    if (!own_adj && !h->d_ct_adj_off) {
+    if (need_adj && !own_adj && !h->d_ct_adj_off) {
         std::vector<int64_t> off((size_t)im.n + 1, 0), adj((size_t)(2 * im.m));
         for (int64_t e = 0; e < im.m; ++e) { off[(size_t)im.tail[e] + 1]++; off[(size_t)im.head[e] + 1]++; }
         for (int32_t u = 0; u < im.n; ++u) off[(size_t)u + 1] += off[u];
@@ -4617,6 +4797,149 @@ int mcf_bottlenecks(mcf_handle* h, const int64_t* flow, int64_t num, int64_t den
     *count = total;
     const int64_t got = total < want ? total : want;
     if (got > 0) HIP_TRY(h, hipMemcpy(idx_out, h->d_bn_idx, (size_t)got * 8, hipMemcpyDeviceToHost));
+    return MCF_OK;
+}
+
+// ---- witnesses of the unbounded and the infeasible verdict (include/mcf.h)
+int mcf_certify_ray(mcf_handle* h, int64_t arc, int64_t* idx_out, int64_t idx_cap, mcf_ray* out) {
+    if (!h || !out || idx_cap < 0 || (idx_cap > 0 && !idx_out)) return MCF_E_BAD_ARG;
+    const McfHostImage& im = h->im;
+    if (arc < -1 || arc >= im.m) { h->err = "mcf_certify_ray: arc index outside [0, m)"; return MCF_E_BAD_ARG; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    int64_t e;
+    if (arc < 0) {
+        if (h->h_ctx->status != MCF_UNBOUNDED || h->h_ctx->unbounded_arc < 0 || h->h_ctx->unbounded_arc >= im.m) {
+            h->err = "mcf_certify_ray: the handle's status is not unbounded"; return MCF_E_STATE;
+        }
+        e = h->h_ctx->unbounded_arc;
+    } else {
+        uc_index(h);
+        e = h->uc_inv[(size_t)arc];
+    }
+    int8_t st = 0;
+    HIP_TRY(h, hipMemcpy(&st, h->d_state + e, 1, hipMemcpyDeviceToHost));
+    if (st == 0) { h->err = "mcf_certify_ray: the arc is basic"; return MCF_E_BAD_ARG; }
+    const int32_t backward = st < 0 ? 1 : 0;
+    if (!h->d_ray_part) {
+        if (dalloc(&h->d_ray_part, kCertMaxBlocks + 1) != hipSuccess || dalloc(&h->d_ray_idx, (size_t)im.n_nodes) != hipSuccess) {
+            (void)hipGetLastError(); cert_free(&h->d_ray_part); cert_free(&h->d_ray_idx);
+            h->err = "hipMalloc ray scratch"; return MCF_E_ALLOC;
+        }
+    }
+    for (hipEvent_t& ev : h->ct_ev) if (!ev) HIP_TRY(h, hipEventCreate(&ev));
+    CertArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.pi = h->d_pi;
+    a.cur = h->h_ctx->cur ^ (h->h_ctx->pending_flip ? 1 : 0);                                   // as mcf_get_tree reads the arrays
+    a.arena = h->h_ctx->arena ^ ((h->h_ctx->pending_flip && h->h_ctx->rebuild) ? 1 : 0);
+    a.bigm = im.big_m;
+    int64_t nb64 = ((int64_t)im.n_nodes + kCertThreads - 1) / kCertThreads;
+    const int nb = (int)(nb64 < kCertMaxBlocks ? nb64 : kCertMaxBlocks);
+    const int64_t want = idx_cap < im.n_nodes ? idx_cap : im.n_nodes;   // a cycle has at most n + 1 = n_nodes arcs
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
+    hipLaunchKernelGGL(k_ray_nodes, dim3(nb), dim3(kCertThreads), 0, s, h->view, a, e, backward, h->d_ray_part);
+    hipLaunchKernelGGL(k_ray_final, dim3(1), dim3(kCertThreads), 0, s, h->d_ray_part, nb);
+    if (want > 0) hipLaunchKernelGGL(k_ray_write, dim3(nb), dim3(kCertThreads), 0, s, h->view, a, e, backward, h->d_ray_part + nb, h->d_ray_idx, want);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+    HIP_TRY(h, hipGetLastError());
+    McfRayAcc R;
+    HIP_TRY(h, hipMemcpyAsync(&R, h->d_ray_part + nb, sizeof R, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms, h->ct_ev[0], h->ct_ev[1]));
+    mcf_ray r;
+    std::memset(&r, 0, sizeof r);
+    r.arc = im.orig[e];
+    r.entering_backward = backward;
+    r.length = R.tree_n + 1;
+    r.join = R.join_i == MCF_CERT_NONE ? -1 : R.join_i;
+    r.backward_count = R.back_n; r.capped_count = R.cap_n; r.artificial_count = R.art_n;
+    r.cost = R.cost; r.reduced_cost = R.rc;
+    r.theta = R.theta; r.theta_arc = R.theta_i == MCF_CERT_NONE ? -1 : R.theta_i;
+    r.proven = mcf_ray_proven(R, backward != 0) ? 1 : 0;
+    r.device_ms = ms;
+    const int64_t got = r.length < want ? r.length : want;
+    if (got > 0) HIP_TRY(h, hipMemcpy(idx_out, h->d_ray_idx, (size_t)got * 8, hipMemcpyDeviceToHost));
+    *out = r;
+    return MCF_OK;
+}
+
+int mcf_certify_cut(mcf_handle* h, const int8_t* in_S, int8_t* S_out, mcf_cut* out) {
+    if (!h || !out) return MCF_E_BAD_ARG;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    const McfHostImage& im = h->im;
+    if ((rc = cert_prepare(h, in_S == nullptr)) != MCF_OK) return rc;   // device supplies, events; a full adjacency for the search only
+    if (!h->d_cut_mark) {
+        if (dalloc(&h->d_cut_mark, (size_t)im.n) != hipSuccess || dalloc(&h->d_cut_level, 1) != hipSuccess ||
+            dalloc(&h->d_cut_byte, (size_t)im.n) != hipSuccess || dalloc(&h->d_cut_part, 2 * kCertMaxBlocks + 1) != hipSuccess) {
+            (void)hipGetLastError(); cert_free(&h->d_cut_mark); cert_free(&h->d_cut_level); cert_free(&h->d_cut_byte); cert_free(&h->d_cut_part);
+            h->err = "hipMalloc cut scratch"; return MCF_E_ALLOC;
+        }
+    }
+    const bool own_adj = h->d_adj && !h->view.rc_partial;
+    const int64_t* adj_off = own_adj ? h->d_adj_off : h->d_ct_adj_off;
+    const int64_t* adj = own_adj ? h->d_adj : h->d_ct_adj;
+    int64_t nb64 = ((int64_t)im.n + kCertThreads - 1) / kCertThreads;
+    const int nb = (int)(nb64 < kCertMaxBlocks ? nb64 : kCertMaxBlocks);
+    const int ab = mcf_price_blocks(im.m, 1, 0);
+    hipStream_t s = h->stream;
+    int32_t level = 0;
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
+    if (in_S) {
+        HIP_TRY(h, hipMemcpyAsync(h->d_cut_byte, in_S, (size_t)im.n, hipMemcpyHostToDevice, s));   // (the call ends with a synchronisation)
+        hipLaunchKernelGGL(k_cut_widen, dim3(nb), dim3(kCertThreads), 0, s, h->d_cut_byte, im.n, h->d_cut_mark);
+    } else {
+        HIP_TRY(h, hipMemsetAsync(h->d_cut_level, 0, 4, s));
+        hipLaunchKernelGGL(k_cut_seed, dim3(nb), dim3(kCertThreads), 0, s, h->view, h->d_cut_mark, h->d_cut_level);
+        HIP_TRY(h, hipMemcpyAsync(&level, h->d_cut_level, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        // Round r expands level r and fills level r + 1; a level holds at least one new node, so there are at most n of them
+        // and round n finds nothing new: the loop ends at r > n whatever the device arrays hold.
+        int32_t r = 1;
+        while (level > 0 && r <= im.n) {
+            const int32_t stop = r + kCutBatch - 1 < im.n ? r + kCutBatch - 1 : im.n;
+            for (; r <= stop; ++r) hipLaunchKernelGGL(k_cut_round, dim3(nb), dim3(kCertThreads), 0, s, h->view, adj_off, adj, h->d_cut_mark, h->d_cut_level, r);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(&level, h->d_cut_level, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+            if (level < r) break;   // the last level was expanded (r is one past the rounds queued) and reached nothing new
+        }
+    }
+    const int32_t resident = in_S ? 0 : 1;
+    if (im.m >= kIncrementalMinArcs) hipLaunchKernelGGL(k_cut_arcs<true>, dim3(ab), dim3(kCertThreads), 0, s, h->view, h->d_cut_mark, resident, h->d_cut_part);
+    else hipLaunchKernelGGL(k_cut_arcs<false>, dim3(ab), dim3(kCertThreads), 0, s, h->view, h->d_cut_mark, resident, h->d_cut_part);
+    hipLaunchKernelGGL(k_cut_nodes, dim3(nb), dim3(kCertThreads), 0, s, h->view, h->d_cut_mark, h->d_ct_supply, resident, h->d_cut_part + ab);
+    hipLaunchKernelGGL(k_cut_final, dim3(1), dim3(kCertThreads), 0, s, h->d_cut_part, ab + nb);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+    HIP_TRY(h, hipGetLastError());
+    McfCutAcc C;
+    HIP_TRY(h, hipMemcpyAsync(&C, h->d_cut_part + ab + nb, sizeof C, hipMemcpyDeviceToHost, s));
+    if (S_out) {
+        hipLaunchKernelGGL(k_cut_narrow, dim3(nb), dim3(kCertThreads), 0, s, h->d_cut_mark, im.n, h->d_cut_byte);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(S_out, h->d_cut_byte, (size_t)im.n, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms, h->ct_ev[0], h->ct_ev[1]));
+    mcf_cut c;
+    std::memset(&c, 0, sizeof c);
+    auto put = [](int64_t* hi_lo, __int128 x) { hi_lo[0] = (int64_t)(x >> 64); hi_lo[1] = (int64_t)(uint64_t)x; };
+    c.seeds = C.seeds; c.nodes_in_S = C.in_s; c.rounds = level; c.deficit_in_S = C.deficit;
+    c.leaving_arcs = C.leave_n; c.leaving_uncapacitated = C.leave_uncap; c.leaving_unsaturated = C.leave_unsat; c.entering_with_flow = C.enter_flow;
+    __int128 excess = 0;
+    c.proven = mcf_cut_proven(C, &excess) ? 1 : 0;
+    put(c.capacity, (__int128)(((mcf_u128)C.cap_hi << 64) | C.cap_lo));
+    put(c.supply, (__int128)(((mcf_u128)C.sup_hi << 64) | C.sup_lo));
+    put(c.excess, excess);
+    put(c.artificial_out, (__int128)(((mcf_u128)C.art_hi << 64) | C.art_lo));
+    c.device_ms = ms;
+    *out = c;
     return MCF_OK;
 }
 

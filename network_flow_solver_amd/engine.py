@@ -32,7 +32,7 @@ ABI_SYMBOLS = (
     "mcf_default_options", "mcf_create", "mcf_solve", "mcf_solve_batch", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs",
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
-    "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs",
+    "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut",
 )
 # mcf_certify: check groups and verdicts (include/mcf.h)
 CERT_BOUNDS, CERT_CONSERVATION, CERT_DUAL, CERT_OBJECTIVES, CERT_BASIS, CERT_PRICING = 1, 2, 4, 8, 16, 32
@@ -116,6 +116,34 @@ class McfRhsReport(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+def _int128(v) -> int:
+    return (int(v[0]) << 64) + (int(v[1]) & ((1 << 64) - 1))
+
+
+class McfRay(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "arc", "entering_backward", "length", "join", "backward_count", "capped_count", "artificial_count", "cost", "reduced_cost",
+        "theta", "theta_arc", "proven")] + [("device_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["entering_backward"], d["proven"] = bool(self.entering_backward), bool(self.proven)
+        return d
+
+
+class McfCut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "seeds", "nodes_in_S", "rounds", "deficit_in_S", "leaving_arcs", "leaving_uncapacitated", "leaving_unsaturated",
+        "entering_with_flow")] + [(name, ctypes.c_int64 * 2) for name in ("capacity", "supply", "excess", "artificial_out")] + [
+        ("proven", ctypes.c_int64), ("device_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        """Plain values: 128-bit sums as Python ints."""
+        d = {name: _int128(getattr(self, name)) if t is ctypes.c_int64 * 2 else getattr(self, name) for name, t in self._fields_}
+        d["proven"] = bool(self.proven)
+        return d
+
+
 PROGRESS_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double)
 
 _lib = None
@@ -162,6 +190,8 @@ def load_library():
     lib.mcf_get_pricing_keys.argtypes = [vp, i32p, i32p]
     lib.mcf_certify.argtypes = [vp, i64p, i64p, ctypes.c_uint32, ctypes.POINTER(McfCertificate)]
     lib.mcf_bottlenecks.argtypes = [vp, i64p, ctypes.c_int64, ctypes.c_int64, i64p, ctypes.c_int64, i64p]
+    lib.mcf_certify_ray.argtypes = [vp, ctypes.c_int64, i64p, ctypes.c_int64, ctypes.POINTER(McfRay)]
+    lib.mcf_certify_cut.argtypes = [vp, i8p, i8p, ctypes.POINTER(McfCut)]
     lib.mcf_dimacs_scan.argtypes = [ctypes.c_char_p, i64p, i64p, ctypes.c_char_p, ctypes.c_int32]
     lib.mcf_dimacs_load.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, i32p, i32p, i64p, i64p, i64p, i64p,
                                     ctypes.c_char_p, ctypes.c_int32]
@@ -172,7 +202,7 @@ def load_library():
     for name in ("mcf_create", "mcf_solve", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs", "mcf_enqueue_price",
                  "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing", "mcf_time_copy",
                  "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load",
-                 "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs"):
+                 "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut"):
         getattr(lib, name).restype = ctypes.c_int
     if lib.mcf_abi_version() != ABI_VERSION:
         raise EngineUnavailableError("libmcf_hip.so ABI version mismatch")
@@ -466,6 +496,41 @@ class McfEngine:
         self._check(self._lib.mcf_bottlenecks(self._h, None if f is None or self.m == 0 else _p(f, ctypes.c_int64), int(num), int(den),
                                               _p(idx, ctypes.c_int64), cap, ctypes.byref(count)))
         return idx[: min(cap, int(count.value))], int(count.value)
+
+    # -- witnesses of the unbounded and the infeasible verdict
+    def certify_ray(self, arc: int = -1, want_arcs: bool = True) -> dict:
+        """The cycle the non-basic arc ``arc`` (default: the arc of an "unbounded" verdict) closes with the resident tree,
+        classified on the device for the push along it (``mcf_certify_ray``).  Read-only.  Returns the fields of ``mcf_ray``;
+        with ``want_arcs`` also ``"arcs"``: the cycle in push order (arc indices, ``m + v`` for the artificial arc of node
+        ``v``).  ``proven``: a directed cycle of real, uncapacitated arcs of negative cost."""
+        cap = self.n + 1 if want_arcs else 0
+        idx = np.zeros(max(cap, 1), dtype=np.int64)
+        ray = McfRay()
+        self._check(self._lib.mcf_certify_ray(self._h, int(arc), _p(idx, ctypes.c_int64) if cap else None, cap, ctypes.byref(ray)))
+        d = ray.as_dict()
+        if want_arcs:
+            d["arcs"] = idx[: min(cap, int(ray.length))]
+        return d
+
+    def certify_cut(self, in_S=None, want_set: bool = True) -> dict:
+        """A cut that proves infeasibility (``mcf_certify_cut``): the node set ``in_S`` (one truth value per node), or, by
+        default, the set reachable from the nodes with artificial outflow in the residual graph of the resident flow,
+        searched on the device.  Read-only.  Returns the fields of ``mcf_cut`` with 128-bit sums as Python ints; with
+        ``want_set`` also ``"S"`` (bool per node).  ``proven``: no uncapacitated arc leaves S and S supplies more than the
+        leaving arcs can carry -- a statement about the instance alone."""
+        s_in = None
+        if in_S is not None:
+            s_in = np.ascontiguousarray(np.asarray(in_S) != 0, dtype=np.int8)
+            if s_in.shape[0] != self.n:
+                raise ValueError("in_S needs one entry per node")
+        s_out = np.zeros(self.n, dtype=np.int8) if want_set else None
+        cut = McfCut()
+        self._check(self._lib.mcf_certify_cut(self._h, None if s_in is None else _p(s_in, ctypes.c_int8),
+                                              None if s_out is None else _p(s_out, ctypes.c_int8), ctypes.byref(cut)))
+        d = cut.as_dict()
+        if want_set:
+            d["S"] = s_out.astype(bool)
+        return d
 
     # -- measurement
     def time_pricing(self, reps: int = 20, rule: int | None = None) -> float:

@@ -608,6 +608,71 @@ class NetworkSimplex:
                                                      "strong_count", "rc_mismatch_count", "key_mismatch_count")),
             raw=c)
 
+    def unbounded_ray(self, arc=None):
+        """The witness of an unbounded problem, evaluated on the device (``mcf_certify_ray``): the cycle the entering arc
+        closes with the resident tree.  Usable after ``solve()`` raised ``UnboundedProblemError`` -- this object still holds
+        the handle.  ``arc``: ``None`` = the arc of that verdict, else a ``(tail, head)`` key (of parallel arcs the last; an
+        arc index for an ``SoAProblem``) of any non-basic arc.  Returns an ``UnboundedRay``."""
+        from .utils import UnboundedRay
+
+        f = self.flat
+        m = len(f.keys)
+        if arc is None:
+            index = -1
+        elif f.soa:
+            index = int(arc)
+        else:
+            hits = [i for i, key in enumerate(f.keys) if key == tuple(arc)]
+            if not hits:
+                raise InvalidProblemError(f"arc {tuple(arc)} is not in the problem")
+            index = hits[-1]
+        r = self.engine.certify_ray(index)
+        if f.soa:
+            arcs = [int(a) for a in r["arcs"]]
+        else:
+            arcs = [f.keys[a] if a < m else (f.node_ids[a - m], self.ROOT_NODE) for a in r["arcs"].tolist()]
+        raw = {k: v for k, v in r.items() if k != "arcs"}
+        return UnboundedRay(arcs=arcs, cost=r["cost"] / f.cost_scale, reduced_cost=r["reduced_cost"] / f.cost_scale,
+                            length=int(r["length"]), proven=bool(r["proven"]), raw=raw)
+
+    def infeasibility_cut(self, nodes=None):
+        """The witness of an infeasible problem (``mcf_certify_cut``): a node set S whose net supply exceeds what the arcs
+        leaving it can carry.  ``nodes=None``: S is searched on the device from the state the last ``solve()`` left (the
+        nodes the stranded supply can still reach); ``nodes`` = an iterable of node ids (node indices for an
+        ``SoAProblem``): that set is evaluated against the instance alone, solved or not.  Capacity and supply come back in
+        the caller's units with the lower-bound shift of the flattening undone.  Returns an ``InfeasibleCut``."""
+        from .utils import InfeasibleCut
+
+        f = self.flat
+        n = len(f.node_ids)
+        in_S = None
+        if nodes is not None:
+            in_S = np.zeros(n, dtype=bool)
+            if f.soa:
+                idx = np.fromiter((int(v) for v in nodes), dtype=np.int64)
+                if idx.size and (idx.min() < 0 or idx.max() >= n):
+                    raise InvalidProblemError(f"node index outside [0, {n})")
+            else:
+                index = {nid: i for i, nid in enumerate(f.node_ids)}
+                missing = [v for v in nodes if v not in index]
+                if missing:
+                    raise InvalidProblemError(f"node {missing[0]!r} is not in the problem")
+                idx = np.fromiter((index[v] for v in nodes), dtype=np.int64)
+            in_S[idx] = True
+        c = self.engine.certify_cut(in_S)
+        S = c.pop("S")
+        leaving = np.flatnonzero(S[f.tail] & ~S[f.head])
+        entering = S[f.head] & ~S[f.tail]
+        capped = leaving[(f.cap[leaving] >= 0) & (f.cap[leaving] < 2 ** 60)]   # the engine's predicate: the capacity sums the capped arcs only
+        lower_leaving, lower_entering = float(f.lower[leaving].sum()), float(f.lower[entering].sum())
+        scale = f.flow_scale
+        return InfeasibleCut(
+            nodes=np.flatnonzero(S).tolist() if f.soa else [f.node_ids[i] for i in np.flatnonzero(S)],
+            leaving_arcs=leaving.tolist() if f.soa else [f.keys[i] for i in leaving],
+            capacity=c["capacity"] / scale + float(f.lower[capped].sum()),
+            supply=c["supply"] / scale + lower_leaving - lower_entering,
+            entering_lower=lower_entering, excess=c["excess"] / scale, proven=bool(c["proven"]), raw=c)
+
     def _objective_estimate(self, flow: np.ndarray) -> float:
         f = self.flat
         return float(np.dot(flow / f.flow_scale + f.lower, f.orig_cost))

@@ -20,7 +20,7 @@ from .data import FlowResult, NetworkProblem
 from .exceptions import SolverConfigurationError
 from .simplex import _decimal_scale
 
-__all__ = ["ValidationResult", "BottleneckArc", "validate_flow", "compute_bottleneck_arcs"]
+__all__ = ["ValidationResult", "BottleneckArc", "UnboundedRay", "InfeasibleCut", "validate_flow", "compute_bottleneck_arcs"]
 
 
 @dataclass
@@ -45,6 +45,37 @@ class BottleneckArc:
     utilization: float | None
     cost: float
     slack: float
+
+
+@dataclass
+class UnboundedRay:
+    """What ``NetworkSimplex.unbounded_ray()`` returns: the cycle an entering arc closes with the resident tree, evaluated on
+    the device (``mcf_certify_ray``).  ``proven``: every arc is a real arc followed in its own direction and has no capacity,
+    and the cycle's cost is negative -- flow can be pushed round it for ever."""
+
+    arcs: list                       # push order: (tail id, head id) keys (arc indices for an SoAProblem); the artificial arc of a
+    #                                  node shows as (node id, NetworkSimplex.ROOT_NODE) (as m + node index for an SoAProblem)
+    cost: float                      # signed sum of the arcs' costs, in the caller's units
+    reduced_cost: float              # the entering arc's reduced cost in the push direction
+    length: int
+    proven: bool
+    raw: dict                        # every field of mcf_ray, integer units
+
+
+@dataclass
+class InfeasibleCut:
+    """What ``NetworkSimplex.infeasibility_cut()`` returns: a node set S and what leaves it (``mcf_certify_cut``), in the
+    caller's units with the lower-bound shift undone.  ``proven``: no uncapacitated arc leaves S and
+    ``excess = supply + entering_lower - capacity > 0``: S has to send out more than its leaving arcs can carry."""
+
+    nodes: list                      # node ids of S (node indices for an SoAProblem)
+    leaving_arcs: list               # (tail id, head id) keys of the arcs from S to the rest (arc indices for an SoAProblem)
+    capacity: float                  # sum of their capacities
+    supply: float                    # net supply of S
+    entering_lower: float            # sum of the lower bounds of the arcs into S: flow S cannot refuse
+    excess: float
+    proven: bool
+    raw: dict                        # every field of mcf_cut, integer units
 
 
 class _Image:
