@@ -1893,17 +1893,21 @@ struct McfCertNodeAcc {
     uint64_t art_lo, art_hi;                      // sum of the artificial flows
     uint64_t dnode_lo, dnode_hi;                  // - sum pi[v] * supply[v]
 };
-#define MCF_CERT_ARC_WORDS ((int)(sizeof(McfCertArcAcc) / 8))
-#define MCF_CERT_NODE_WORDS ((int)(sizeof(McfCertNodeAcc) / 8))
+// an accumulator is a row of 8-byte words (that is how the kernels hand one from lane to lane)
+template <typename Acc>
+constexpr int mcf_acc_words() {
+    static_assert(sizeof(Acc) % 8 == 0, "accumulators are whole 8-byte words");
+    return (int)(sizeof(Acc) / 8);
+}
 
 MCF_HD void mcf_cert_arc_init(McfCertArcAcc* a) {
     uint64_t* p = reinterpret_cast<uint64_t*>(a);
-    for (int k = 0; k < MCF_CERT_ARC_WORDS; ++k) p[k] = 0;
+    for (int k = 0; k < mcf_acc_words<McfCertArcAcc>(); ++k) p[k] = 0;
     a->bnd_i = a->dlo_i = a->dup_i = MCF_CERT_NONE;
 }
 MCF_HD void mcf_cert_node_init(McfCertNodeAcc* a) {
     uint64_t* p = reinterpret_cast<uint64_t*>(a);
-    for (int k = 0; k < MCF_CERT_NODE_WORDS; ++k) p[k] = 0;
+    for (int k = 0; k < mcf_acc_words<McfCertNodeAcc>(); ++k) p[k] = 0;
     a->imb_i = MCF_CERT_NONE;
 }
 MCF_HD void mcf_cert_worst(int64_t* w, int64_t* wi, int64_t mag, int64_t idx) {
@@ -1982,7 +1986,7 @@ MCF_HD void mcf_cert_node_balance(McfCertNodeAcc* a, int64_t node, __int128 bal)
 // ====================================================================== witnesses of the other two verdicts (include/mcf.h)
 // mcf_certify_ray: the cycle a non-basic arc closes with the resident tree, classified arc by arc for the push along it;
 // mcf_certify_cut: a node set S, its leaving capacity against its net supply.  As for the certificate above, the per-arc /
-// per-node logic lives here, shared by the kernels (mcf_engine.hip: k_ray_*, k_cut_*) and the host restatement of the CPU
+// per-node logic lives here, shared by the kernels (mcf_passes_dev.h: k_ray_*, k_cut_*) and the host restatement of the CPU
 // tests (csrc/mcf_farkas_host.cpp), and every partial combines by an integer sum, a min / max with the lowest index, or a
 // 128-bit sum: no merge order can change a bit of the result.
 struct McfRayAcc {
@@ -1993,7 +1997,6 @@ struct McfRayAcc {
     int64_t theta, theta_i;          // smallest residual in the push direction (MCF_INF: none), first arc attaining it
     int64_t join_d, join_i;          // depth + 1 of the deepest common ancestor of the two end points, and that node
 };
-#define MCF_RAY_WORDS ((int)(sizeof(McfRayAcc) / 8))
 
 MCF_HD void mcf_ray_init(McfRayAcc* a) {
     a->tree_n = a->back_n = a->cap_n = a->art_n = a->cost = a->rc = 0;
@@ -2043,11 +2046,10 @@ struct McfCutAcc {
     uint64_t sup_lo, sup_hi;                               // sum of the supplies over S
     uint64_t art_lo, art_hi;                               // artificial flow S -> root minus root -> S
 };
-#define MCF_CUT_WORDS ((int)(sizeof(McfCutAcc) / 8))
 
 MCF_HD void mcf_cut_init(McfCutAcc* a) {
     uint64_t* p = reinterpret_cast<uint64_t*>(a);
-    for (int k = 0; k < MCF_CUT_WORDS; ++k) p[k] = 0;
+    for (int k = 0; k < mcf_acc_words<McfCutAcc>(); ++k) p[k] = 0;
 }
 MCF_HD void mcf_cut_merge(McfCutAcc* a, const McfCutAcc& b) {
     a->seeds += b.seeds; a->in_s += b.in_s; a->deficit += b.deficit;
@@ -2056,6 +2058,16 @@ MCF_HD void mcf_cut_merge(McfCutAcc* a, const McfCutAcc& b) {
     mcf_cert_add128(&a->sup_lo, &a->sup_hi, ((mcf_u128)b.sup_hi << 64) | b.sup_lo);
     mcf_cert_add128(&a->art_lo, &a->art_hi, ((mcf_u128)b.art_hi << 64) | b.art_lo);
 }
+
+// one interface over the four accumulators, for the code that reduces any of them (mcf_passes_dev.h)
+MCF_HD void mcf_acc_init(McfCertArcAcc* a) { mcf_cert_arc_init(a); }
+MCF_HD void mcf_acc_init(McfCertNodeAcc* a) { mcf_cert_node_init(a); }
+MCF_HD void mcf_acc_init(McfRayAcc* a) { mcf_ray_init(a); }
+MCF_HD void mcf_acc_init(McfCutAcc* a) { mcf_cut_init(a); }
+MCF_HD void mcf_acc_merge(McfCertArcAcc* a, const McfCertArcAcc& b) { mcf_cert_arc_merge(a, b); }
+MCF_HD void mcf_acc_merge(McfCertNodeAcc* a, const McfCertNodeAcc& b) { mcf_cert_node_merge(a, b); }
+MCF_HD void mcf_acc_merge(McfRayAcc* a, const McfRayAcc& b) { mcf_ray_merge(a, b); }
+MCF_HD void mcf_acc_merge(McfCutAcc* a, const McfCutAcc& b) { mcf_cut_merge(a, b); }
 
 // The relaxation step of the residual search: does the arc (cap, flow) carry the set on from the end point it was reached
 // at to its other end?  From its tail while it has room (uncapacitated, or flow < cap), from its head while it carries flow.

@@ -1890,765 +1890,7 @@ __global__ void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
 }
 
-// ------------------------------------------------------------------ mcf_update_costs: re-price a resident basis
-// Flows, states and the tree do not depend on costs, so a cost change on a handle that holds a basis moves only the
-// potentials below a changed TREE arc and, after them, the reduced costs / key codes.  Four kinds of launches, none of
-// which depends on how many arcs changed or (beyond a logarithm) on the depth of the tree:
-//   k_uc_seed     one lane per node: jump record {val = 0 (root children on an artificial arc: +-(growth of big-M)),
-//                 anc = parent}, and the greatest depth of the tree (decides the number of jump rounds);
-//   k_uc_scatter  one lane per changed arc: store cost[e]; a basic arc adds +-delta to the record of the end point it is
-//                 the tree arc of (every node has its own tree arc: plain stores, nothing to resolve);
-//   k_uc_jump     pointer jumping, ceil(log2(max depth)) rounds over double buffers: val[v] += val[anc[v]],
-//                 anc[v] = anc[anc[v]] -- after the last round val[v] is the sum of the deltas on v's root path.  Reads
-//                 parent pointers only, so it serves the dense preorder array and the blocked preorder list alike;
-//                 the last round adds the sum to pi[v] itself;
-//   k_uc_rebuild  one streaming pass over all m_pad arcs in the shape of k_price's gather: rc = cost + pi[tail] - pi[head]
-//                 into rcache (and the key code into vkey), 16-byte accesses throughout.
-struct alignas(16) McfJump {
-    int64_t val;   // sum of the potential shifts of the tree arcs from this node up to (excluding) anc
-    int32_t anc;   // -1: the path has reached the root
-    int32_t pad;
-};
-
-constexpr int kUcThreads = 256;
-
-__global__ __launch_bounds__(kUcThreads) void k_uc_seed(const McfNode* __restrict__ node, int32_t n_nodes, int64_t m, int64_t d_bigm,
-                                                        McfJump* __restrict__ out, int32_t* __restrict__ info) {
-    __shared__ int32_t s_depth;
-    if (threadIdx.x == 0) s_depth = 0;
-    __syncthreads();
-    int32_t deepest = 0;
-    const int32_t stride = (int32_t)(gridDim.x * kUcThreads);
-    for (int32_t v = (int32_t)(blockIdx.x * kUcThreads + threadIdx.x); v < n_nodes; v += stride) {
-        const McfNode r = node[v];
-        McfJump j;
-        j.val = 0; j.anc = r.parent; j.pad = 0;
-        // an artificial arc costs big-M: a larger big-M is a cost change on the tree arc of every node that still hangs on one
-        if (r.pred >= 0 && (int64_t)(r.pred >> 1) >= m) j.val = (r.pred & 1) ? -d_bigm : d_bigm;
-        out[v] = j;
-        deepest = r.depth > deepest ? r.depth : deepest;
-    }
-    atomicMax(&s_depth, deepest);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_depth > 0) atomicMax(&info[0], s_depth);
-}
-
-__global__ __launch_bounds__(kUcThreads) void k_uc_scatter(int64_t count, const int32_t* __restrict__ arc, const int32_t* __restrict__ new_cost,
-                                                           int32_t* __restrict__ cost, const int8_t* __restrict__ state,
-                                                           const int32_t* __restrict__ tail, const int32_t* __restrict__ head,
-                                                           const McfNode* __restrict__ node, McfJump* __restrict__ jump, int32_t* __restrict__ info) {
-    const int64_t stride = (int64_t)gridDim.x * kUcThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kUcThreads + threadIdx.x; i < count; i += stride) {
-        const int32_t e = arc[i];
-        const int64_t delta = (int64_t)new_cost[i] - (int64_t)cost[e];
-        cost[e] = new_cost[i];
-        if (delta == 0 || state[e] != 0) continue;
-        // basic: the arc is the tree arc of exactly one of its end points; pi[x] = pi[parent] -+ cost (up / down)
-        const int32_t t = tail[e], hd = head[e];
-        const int32_t pt = node[t].pred, ph = node[hd].pred;
-        int32_t x = -1;
-        if (pt >= 0 && (pt >> 1) == e) x = t; else if (ph >= 0 && (ph >> 1) == e) x = hd;
-        if (x < 0) continue;
-        jump[x].val = x == t ? -delta : delta;
-        atomicAdd(&info[1], 1);
-    }
-}
-
-template <bool LAST>   // LAST: the sums are complete after this round and go straight into the potentials
-__global__ __launch_bounds__(kUcThreads) void k_uc_jump(const McfJump* __restrict__ in, McfJump* __restrict__ out, int64_t* __restrict__ pi, int32_t n_nodes) {
-    const int32_t stride = (int32_t)(gridDim.x * kUcThreads);
-    for (int32_t v = (int32_t)(blockIdx.x * kUcThreads + threadIdx.x); v < n_nodes; v += stride) {
-        McfJump a = in[v];
-        if (a.anc >= 0) {
-            const McfJump b = in[a.anc];
-            a.val += b.val;
-            a.anc = b.anc;
-        }
-        if (LAST) { if (a.val != 0) pi[v] += a.val; }
-        else out[v] = a;
-    }
-}
-
-// Bucket x's share of the 4-arc groups: a group that straddles a bucket boundary belongs to the lower bucket, the last
-// bucket takes the padding.  Workgroup b sweeps bucket b % 8 like k_price, so that the head gathers of an XCD's workgroups
-// stay inside one eighth of the potential array.
-__device__ __forceinline__ int64_t uc_group_lo(const McfView& v, int x, int64_t ngroups) {
-    if (x <= 0) return 0;
-    if (x >= MCF_NUM_BUCKETS) return ngroups;
-    return (v.bucket_off[x] + 3) >> 2;
-}
-
-constexpr int kUcUnroll = 2;   // 4-arc groups in flight per lane, as in k_price
-
-__global__ __launch_bounds__(kUcThreads) void k_uc_rebuild(McfView v, int64_t m_pad) {
-    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
-    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
-    const int64_t ngroups = m_pad >> 2;
-    const int64_t g_lo = uc_group_lo(v, x, ngroups), g_hi = uc_group_lo(v, x + 1, ngroups);
-    const int4* __restrict__ tail4 = reinterpret_cast<const int4*>(v.tail);
-    const int4* __restrict__ head4 = reinterpret_cast<const int4*>(v.head);
-    const int4* __restrict__ cost4 = reinterpret_cast<const int4*>(v.cost);
-    const int32_t* __restrict__ state4 = reinterpret_cast<const int32_t*>(v.state);
-    const int64_t* __restrict__ pi = v.pi;
-    longlong2* __restrict__ rc2 = reinterpret_cast<longlong2*>(v.rcache);
-    int4* __restrict__ vk4 = reinterpret_cast<int4*>(v.vkey);
-    const int64_t bigm = v.vk_bigm;
-    const int32_t half = v.vk_half;
-    const int64_t stride = nlb * kUcThreads;
-    for (int64_t g0 = g_lo + lb * kUcThreads + threadIdx.x; g0 < g_hi; g0 += stride * kUcUnroll) {
-        int4 t[kUcUnroll], h[kUcUnroll], cc[kUcUnroll];
-        int32_t st[kUcUnroll];
-#pragma unroll
-        for (int u = 0; u < kUcUnroll; ++u) {
-            const int64_t g = g0 + u * stride;
-            const int64_t gs = g < g_hi ? g : g_lo;   // clamp: the loads stay unconditional and in range
-            t[u] = tail4[gs]; h[u] = head4[gs]; cc[u] = cost4[gs]; st[u] = state4[gs];
-        }
-        int64_t pt[kUcUnroll][4], ph[kUcUnroll][4];
-#pragma unroll
-        for (int u = 0; u < kUcUnroll; ++u) {
-            pt[u][0] = pi[t[u].x]; pt[u][1] = pi[t[u].y]; pt[u][2] = pi[t[u].z]; pt[u][3] = pi[t[u].w];
-            ph[u][0] = pi[h[u].x]; ph[u][1] = pi[h[u].y]; ph[u][2] = pi[h[u].z]; ph[u][3] = pi[h[u].w];
-        }
-#pragma unroll
-        for (int u = 0; u < kUcUnroll; ++u) {
-            const int64_t g = g0 + u * stride;
-            if (g >= g_hi) continue;
-            const int64_t r0 = (int64_t)cc[u].x + pt[u][0] - ph[u][0], r1 = (int64_t)cc[u].y + pt[u][1] - ph[u][1];
-            const int64_t r2 = (int64_t)cc[u].z + pt[u][2] - ph[u][2], r3 = (int64_t)cc[u].w + pt[u][3] - ph[u][3];
-            longlong2 a, b;
-            a.x = r0; a.y = r1; b.x = r2; b.y = r3;
-            rc2[2 * g] = a;
-            rc2[2 * g + 1] = b;
-            if (vk4) {
-                const int32_t s = st[u];
-                int4 k;
-                k.x = mcf_vkey(-(int64_t)(int8_t)s * r0, bigm, half);
-                k.y = mcf_vkey(-(int64_t)(int8_t)(s >> 8) * r1, bigm, half);
-                k.z = mcf_vkey(-(int64_t)(int8_t)(s >> 16) * r2, bigm, half);
-                k.w = mcf_vkey(-(int64_t)(int8_t)(s >> 24) * r3, bigm, half);
-                vk4[g] = k;
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(kUcThreads) void k_uc_ones(float4* __restrict__ w4, int64_t n4) {
-    const int64_t stride = (int64_t)gridDim.x * kUcThreads;
-    for (int64_t i = (int64_t)blockIdx.x * kUcThreads + threadIdx.x; i < n4; i += stride) w4[i] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-}
-
-// ------------------------------------------------------------------ certificate (mcf_certify / mcf_bottlenecks)
-// k_cert_arcs    ONE streaming pass over the arcs in engine order, workgroup b on head bucket b % 8 like the pricing sweeps
-//                (the two potential gathers of an arc then stay inside one XCD's L2 share): tail, head, cost, orig (4 B
-//                each), the walk record (cap, flow: 16 B), and for the resident groups state (1 B), reduced cost (8 B) and
-//                key code (4 B) -- 32 B per arc for the primal / dual / objective groups, 45 B with everything.  Read once
-//                per call: non-temporal loads from kIncrementalMinArcs arcs on, as for the key-code sweep.
-// k_cert_child   size[v] added to csum[parent[v]] (integer atomics: the sum does not depend on their order).
-// k_cert_nodes   one lane per node: conservation as a gather over the node's adjacency list (128-bit balance), the dual
-//                objective's node term, the artificial arc, and the tree records (mcf_get_tree's view of them).
-// k_cert_final   one workgroup merges the per-workgroup partials.
-// Every partial combines by integer +, max or (max, lowest index) (mcf_core.h), so no merge order can change the result.
-constexpr int kCertThreads = 256;
-constexpr int kCertMaxBlocks = 2048;
-
-struct CertArgs {
-    const int64_t* cflow;     // caller's flows in the caller's order; nullptr = resident
-    const int64_t* pi;        // [n_nodes] potentials, root included (resident, or the caller's with root = 0)
-    const int64_t* supply;    // [n]
-    const int64_t* adj_off;   // full node -> arc adjacency (the handle's, or the certificate's own)
-    const int64_t* adj;
-    const int64_t* rcache;    // resident copies to compare, nullptr = none
-    const int32_t* vkey;
-    int32_t* csum;            // [n_nodes] scratch: sum of the children's sizes
-    uint32_t checks;
-    int32_t resident_flow;
-    int32_t cur, arena;       // which copies of the preorder arrays are current (mcf_get_tree)
-    int32_t partial;          // resident reduced costs / key codes are exact on this rank's shard only
-    int64_t shard, shards;
-    int64_t bigm;
-};
-
-template <bool NT, typename T>
-__device__ __forceinline__ T cert_ld(const T* p) { return NT ? __builtin_nontemporal_load(p) : *p; }
-
-template <typename Acc, int WORDS, typename Merge>
-__device__ __forceinline__ void cert_block_reduce(Acc& acc, Acc* s_wave, Merge merge) {
-    for (int off = 32; off > 0; off >>= 1) {
-        Acc o;
-        unsigned long long* po = reinterpret_cast<unsigned long long*>(&o);
-        const unsigned long long* pa = reinterpret_cast<const unsigned long long*>(&acc);
-#pragma unroll
-        for (int k = 0; k < WORDS; ++k) po[k] = __shfl_down(pa[k], off, 64);
-        if ((int)(threadIdx.x & 63) + off < 64) merge(&acc, o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_wave[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kCertThreads / 64; ++w) merge(&acc, s_wave[w]);
-}
-
-template <bool NT>
-__global__ __launch_bounds__(kCertThreads) void k_cert_arcs(McfView v, CertArgs a, McfCertArcAcc* __restrict__ part) {
-    __shared__ McfCertArcAcc s_wave[kCertThreads / 64];
-    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
-    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
-    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
-    int64_t own_lo = lo, own_hi = hi;
-    if (a.partial) mcf_bucket_slice(v.bucket_off, x, a.shard, a.shards, 0, 1, &own_lo, &own_hi);
-    const bool resident = (a.checks & (MCF_CERT_BASIS | MCF_CERT_PRICING)) != 0;
-    McfCertArcAcc acc;
-    mcf_cert_arc_init(&acc);
-    for (int64_t e = lo + lb * kCertThreads + threadIdx.x; e < hi; e += nlb * kCertThreads) {
-        const int32_t t = cert_ld<NT>(v.tail + e), hd = cert_ld<NT>(v.head + e);
-        const int64_t cost = cert_ld<NT>(v.cost + e);
-        const int64_t o = cert_ld<NT>(v.orig + e);
-        const int64_t* aw = reinterpret_cast<const int64_t*>(v.arcw + e);
-        const int64_t cap = cert_ld<NT>(aw);
-        const int64_t flow = a.cflow ? a.cflow[o] : cert_ld<NT>(aw + 1);
-        const int64_t rc = cost + a.pi[t] - a.pi[hd];
-        mcf_cert_arc(&acc, a.checks, o, cost, cap, flow, rc);
-        if (resident) {
-            const int32_t st = cert_ld<NT>(v.state + e);
-            const bool own = e >= own_lo && e < own_hi;
-            int64_t rres = 0;
-            int32_t kres = 0;
-            if (a.rcache && own) rres = cert_ld<NT>(a.rcache + e);
-            if (a.vkey && own) kres = cert_ld<NT>(a.vkey + e);
-            mcf_cert_arc_resident(&acc, a.checks, cap, flow, rc, st, a.rcache && own ? &rres : nullptr, a.vkey && own ? &kres : nullptr,
-                                  v.vk_bigm, v.vk_half);
-        }
-    }
-    cert_block_reduce<McfCertArcAcc, MCF_CERT_ARC_WORDS>(acc, s_wave, [](McfCertArcAcc* p, const McfCertArcAcc& q) { mcf_cert_arc_merge(p, q); });
-    if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-__global__ __launch_bounds__(kCertThreads) void k_cert_child(McfView v, int32_t* __restrict__ csum) {
-    const int32_t N = v.n_nodes;
-    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N - 1; u += gridDim.x * kCertThreads) {
-        const McfNode nd = v.node[u];
-        if (nd.parent >= 0 && nd.parent < N) atomicAdd(&csum[nd.parent], nd.size);
-    }
-}
-
-// Preorder position of `node` and the slot that holds it, in the view mcf_get_tree reports (a.cur / a.arena already
-// account for a flip the last update left pending); -1 when a record points outside its array.
-__device__ __forceinline__ int32_t cert_pos(const McfView& v, const CertArgs& a, int32_t node, int32_t* slot) {
-    if (MCF_HAS_BPL(v)) {
-        const int32_t s = v.posbuf[0][node] & MCF_LOC_SLOT;
-        const int32_t b = s >> v.blk_shift;
-        *slot = s;
-        if (b < 0 || b >= v.blk_cap) return -1;
-        const int32_t base = (a.cur ? v.bmeta[1] : v.bmeta[0])[b].base;
-        if (base == MCF_BLK_FREE) return -1;
-        return base + (s & ((1 << v.blk_shift) - 1));
-    }
-    const int32_t p = (a.cur ? v.posbuf[1] : v.posbuf[0])[node];
-    *slot = p;
-    return (p < 0 || p >= v.n_nodes) ? -1 : p;
-}
-
-__global__ __launch_bounds__(kCertThreads) void k_cert_nodes(McfView v, CertArgs a, McfCertNodeAcc* __restrict__ part) {
-    __shared__ McfCertNodeAcc s_wave[kCertThreads / 64];
-    const int32_t N = v.n_nodes, root = N - 1;
-    const int64_t m = v.m;
-    const int32_t sel = MCF_HAS_BPL(v) ? a.arena : a.cur;
-    const int32_t* ord = sel ? v.order[1] : v.order[0];
-    const int32_t* psz = sel ? v.psz[1] : v.psz[0];
-    const int64_t pi_root = a.pi[root];
-    McfCertNodeAcc acc;
-    mcf_cert_node_init(&acc);
-    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
-        const McfNode nd = v.node[u];
-        if (u < root) {
-            const int64_t af = v.arcw[m + u].flow;
-            mcf_cert_add128(&acc.art_lo, &acc.art_hi, (mcf_u128)(__int128)af);
-            if (a.checks & MCF_CERT_CONSERVATION) {
-                // 128 bits: a node may have 2^30 arcs of up to 2^63 each
-                __int128 bal = a.supply[u];
-                for (int64_t k = a.adj_off[u]; k < a.adj_off[u + 1]; ++k) {
-                    const int64_t w = a.adj[k];
-                    const int64_t e = (w & 0xffffffff) >> 1;
-                    const int64_t f = a.cflow ? a.cflow[v.orig[e]] : v.arcw[e].flow;
-                    bal += (w & 1) ? -(__int128)f : (__int128)f;
-                }
-                if (a.resident_flow) {   // the node's artificial arc: node -> root when "up" (a non-basic one carries nothing)
-                    const bool up = (int64_t)(nd.pred >> 1) == m + u ? (nd.pred & 1) != 0 : true;
-                    bal += up ? -(__int128)af : (__int128)af;
-                }
-                mcf_cert_node_balance(&acc, u, bal);
-            }
-            if (a.checks & MCF_CERT_OBJECTIVES)
-                mcf_cert_add128(&acc.dnode_lo, &acc.dnode_hi, (mcf_u128)(-(__int128)(a.pi[u] - pi_root) * a.supply[u]));
-        }
-        if (!(a.checks & MCF_CERT_BASIS)) continue;
-        bool bad = false;
-        int32_t slot = 0;
-        const int32_t pos = cert_pos(v, a, u, &slot);
-        if (pos < 0) bad = true;
-        else {
-            if (ord[slot] != u) bad = true;
-            if (psz && psz[slot] != nd.size) bad = true;
-        }
-        if (nd.size != 1 + a.csum[u]) bad = true;
-        if (u == root) {
-            if (nd.parent != -1 || pos != 0 || nd.size != N || nd.depth != 0) bad = true;
-        } else if (nd.parent < 0 || nd.parent >= N || nd.pred < 0) {
-            bad = true;
-        } else {
-            const int32_t p = nd.parent;
-            const McfNode pn = v.node[p];
-            int32_t pslot = 0;
-            const int32_t ppos = cert_pos(v, a, p, &pslot);
-            if (ppos < 0 || pos < 0 || !(ppos < pos && (int64_t)pos + nd.size <= (int64_t)ppos + pn.size)) bad = true;
-            if (nd.depth != pn.depth + 1) bad = true;
-            const int64_t arc = nd.pred >> 1;
-            const bool up = (nd.pred & 1) != 0;
-            if (arc < m) {
-                const int32_t t = v.tail[arc], hd = v.head[arc];
-                if (up ? (t != u || hd != p) : (hd != u || t != p)) bad = true;
-                if (v.state[arc] != 0) bad = true;
-                if ((int64_t)v.cost[arc] + a.pi[t] - a.pi[hd] != 0) ++acc.tree_rc_bad;
-                const McfArcW w = v.arcw[arc];
-                if ((up && w.cap < MCF_INF && w.flow == w.cap) || (!up && w.flow == 0)) ++acc.strong_bad;
-            } else {
-                if (arc != m + u || p != root) bad = true;
-                if (a.bigm + (up ? a.pi[u] - pi_root : pi_root - a.pi[u]) != 0) ++acc.tree_rc_bad;
-                if (!up && v.arcw[m + u].flow == 0) ++acc.strong_bad;
-                ++acc.art_basic;
-            }
-        }
-        if (bad) ++acc.shape_bad;
-    }
-    cert_block_reduce<McfCertNodeAcc, MCF_CERT_NODE_WORDS>(acc, s_wave, [](McfCertNodeAcc* p, const McfCertNodeAcc& q) { mcf_cert_node_merge(p, q); });
-    if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// part[0 .. n) -> part[n] (arcs and nodes alike)
-__global__ __launch_bounds__(kCertThreads) void k_cert_final(McfCertArcAcc* __restrict__ ap, int na, McfCertNodeAcc* __restrict__ np, int nn) {
-    __shared__ McfCertArcAcc s_a[kCertThreads / 64];
-    __shared__ McfCertNodeAcc s_n[kCertThreads / 64];
-    McfCertArcAcc a;
-    McfCertNodeAcc n;
-    mcf_cert_arc_init(&a);
-    mcf_cert_node_init(&n);
-    for (int i = threadIdx.x; i < na; i += kCertThreads) mcf_cert_arc_merge(&a, ap[i]);
-    for (int i = threadIdx.x; i < nn; i += kCertThreads) mcf_cert_node_merge(&n, np[i]);
-    cert_block_reduce<McfCertArcAcc, MCF_CERT_ARC_WORDS>(a, s_a, [](McfCertArcAcc* p, const McfCertArcAcc& q) { mcf_cert_arc_merge(p, q); });
-    cert_block_reduce<McfCertNodeAcc, MCF_CERT_NODE_WORDS>(n, s_n, [](McfCertNodeAcc* p, const McfCertNodeAcc& q) { mcf_cert_node_merge(p, q); });
-    if (threadIdx.x == 0) { ap[na] = a; np[nn] = n; }
-}
-
-// ---- bottleneck arcs, compacted in ascending caller's index: flag per caller's index (scatter from the engine-order
-// stream), count per chunk, exclusive scan of the chunk counts by one workgroup, write.
-constexpr int kBnChunk = 4096;   // caller's indices per workgroup: 16 rounds of 256
-__global__ __launch_bounds__(kCertThreads) void k_bn_flag(McfView v, const int64_t* __restrict__ cflow, int64_t num, int64_t den,
-                                                          uint8_t* __restrict__ flag) {
-    for (int64_t e = (int64_t)blockIdx.x * kCertThreads + threadIdx.x; e < v.m; e += (int64_t)gridDim.x * kCertThreads) {
-        const McfArcW w = v.arcw[e];
-        const int32_t o = v.orig[e];
-        flag[o] = mcf_cert_bottleneck(w.cap, cflow ? cflow[o] : w.flow, num, den) ? 1 : 0;
-    }
-}
-__global__ __launch_bounds__(kCertThreads) void k_bn_count(const uint8_t* __restrict__ flag, int64_t m, int32_t* __restrict__ cnt) {
-    __shared__ int32_t s[kCertThreads / 64];
-    const int64_t base = (int64_t)blockIdx.x * kBnChunk;
-    int32_t c = 0;
-    for (int r = 0; r < kBnChunk / kCertThreads; ++r) {
-        const int64_t i = base + r * kCertThreads + threadIdx.x;
-        if (i < m && flag[i]) ++c;
-    }
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
-}
-__global__ __launch_bounds__(1024) void k_bn_scan(const int32_t* __restrict__ cnt, int64_t nb, int64_t* __restrict__ off) {
-    __shared__ int64_t s[1024];
-    const int64_t per = (nb + 1023) / 1024, lo = threadIdx.x * per < nb ? threadIdx.x * per : nb, hi = lo + per < nb ? lo + per : nb;
-    int64_t sum = 0;
-    for (int64_t b = lo; b < hi; ++b) sum += cnt[b];
-    s[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int k = 0; k < 1024; ++k) { const int64_t x = s[k]; s[k] = run; run += x; }
-        off[nb] = run;   // the total
-    }
-    __syncthreads();
-    int64_t run = s[threadIdx.x];
-    for (int64_t b = lo; b < hi; ++b) { off[b] = run; run += cnt[b]; }
-}
-__global__ __launch_bounds__(kCertThreads) void k_bn_write(const uint8_t* __restrict__ flag, int64_t m, const int64_t* __restrict__ off,
-                                                           int64_t* __restrict__ idx, int64_t idx_cap) {
-    __shared__ int32_t s[kCertThreads / 64];
-    const int64_t base = (int64_t)blockIdx.x * kBnChunk;
-    int64_t run = off[blockIdx.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int r = 0; r < kBnChunk / kCertThreads; ++r) {
-        const int64_t i = base + r * kCertThreads + threadIdx.x;
-        const bool f = i < m && flag[i];
-        const uint64_t mask = __ballot(f);
-        if (lane == 0) s[wave] = __popcll(mask);
-        __syncthreads();
-        int64_t before = run;
-        for (int w = 0; w < wave; ++w) before += s[w];
-        const int64_t at = before + __popcll(mask & (((uint64_t)1 << lane) - 1));
-        if (f && at < idx_cap) idx[at] = i;
-        run += s[0] + s[1] + s[2] + s[3];
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------ witnesses (mcf_certify_ray / mcf_certify_cut)
-// k_ray_nodes   one lane per node record (16 B) + its preorder position (4 B dense; 4 + 8 B blocked: slot, block base): the
-//               interval test against the two end points says whether the node's tree arc is on the cycle and on which
-//               side; only the <= length lanes that are read the arc's walk record (16 B), cost and caller's index.
-// k_ray_final   one workgroup merges the per-workgroup partials.
-// k_ray_write   the same pass once more, now that the length is known: a node of the arriving side lands at
-//               1 + depth[first] - depth[u], one of the leaving side at length - 1 - (depth[second] - depth[u]).  8 B per cycle arc out.
-// k_cut_seed    one lane per node: node record + artificial walk record in, a 4 B level mark out (1 = seed, 0 = not reached).
-// k_cut_round   round r: one lane per node reads its mark (4 B); the lanes at level r walk their adjacency list (8 B per entry +
-//               the arc's 16 B walk record + the other end's mark) and mark what the residual arcs reach with r + 1.  Every list
-//               is expanded in exactly one round; all lanes that reach a node in a round store the same value.
-// k_cut_arcs    the streaming pass of k_cert_arcs: tail, head (4 B each), the walk record (16 B), two gathered marks.
-// k_cut_nodes   one lane per node: mark, supply (8 B), node record and artificial walk record of the nodes of S.
-constexpr int kCutBatch = 32;   // rounds queued between two looks at the level word
-
-__global__ __launch_bounds__(kCertThreads) void k_ray_nodes(McfView v, CertArgs a, int64_t e, int32_t backward, McfRayAcc* __restrict__ part) {
-    __shared__ McfRayAcc s_wave[kCertThreads / 64];
-    const int32_t N = v.n_nodes;
-    const int64_t m = v.m;
-    const int32_t t = v.tail[e], hd = v.head[e];
-    const int32_t first = backward ? t : hd, second = backward ? hd : t;
-    int32_t slot = 0;
-    const int32_t pf = cert_pos(v, a, first, &slot), ps = cert_pos(v, a, second, &slot);
-    McfRayAcc acc;
-    mcf_ray_init(&acc);
-    if (pf >= 0 && ps >= 0) {
-        for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
-            const McfNode nd = v.node[u];
-            const int32_t pu = cert_pos(v, a, u, &slot);
-            if (pu < 0) continue;
-            const int side = mcf_ray_side(pu, nd.size, pf, ps);
-            if (side == 3) mcf_cert_worst(&acc.join_d, &acc.join_i, (int64_t)nd.depth + 1, u);
-            else if (side && nd.pred >= 0) {
-                const int64_t arc = nd.pred >> 1;
-                const bool up = (nd.pred & 1) != 0;
-                const bool forward = side == 1 ? up : !up;
-                if (arc < m) {
-                    const McfArcW w = v.arcw[arc];
-                    mcf_ray_arc(&acc, v.orig[arc], true, false, forward, v.cost[arc], w.cap, w.flow);
-                } else if (arc < m + N - 1) {
-                    mcf_ray_arc(&acc, arc, true, true, forward, a.bigm, MCF_INF, v.arcw[arc].flow);
-                }
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const McfArcW w = v.arcw[e];
-        const int64_t cost = v.cost[e];
-        mcf_ray_arc(&acc, v.orig[e], false, false, !backward, cost, w.cap, w.flow);
-        const int64_t rc = cost + a.pi[t] - a.pi[hd];
-        acc.rc = backward ? -rc : rc;
-    }
-    cert_block_reduce<McfRayAcc, MCF_RAY_WORDS>(acc, s_wave, [](McfRayAcc* p, const McfRayAcc& q) { mcf_ray_merge(p, q); });
-    if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// part[0 .. n) -> part[n]
-__global__ __launch_bounds__(kCertThreads) void k_ray_final(McfRayAcc* __restrict__ part, int n) {
-    __shared__ McfRayAcc s_wave[kCertThreads / 64];
-    McfRayAcc acc;
-    mcf_ray_init(&acc);
-    for (int i = threadIdx.x; i < n; i += kCertThreads) mcf_ray_merge(&acc, part[i]);
-    cert_block_reduce<McfRayAcc, MCF_RAY_WORDS>(acc, s_wave, [](McfRayAcc* p, const McfRayAcc& q) { mcf_ray_merge(p, q); });
-    if (threadIdx.x == 0) part[n] = acc;
-}
-
-__global__ __launch_bounds__(kCertThreads) void k_ray_write(McfView v, CertArgs a, int64_t e, int32_t backward, const McfRayAcc* __restrict__ total,
-                                                            int64_t* __restrict__ idx, int64_t idx_cap) {
-    const int32_t N = v.n_nodes;
-    const int64_t m = v.m;
-    const int32_t t = v.tail[e], hd = v.head[e];
-    const int32_t first = backward ? t : hd, second = backward ? hd : t;
-    int32_t slot = 0;
-    const int32_t pf = cert_pos(v, a, first, &slot), ps = cert_pos(v, a, second, &slot);
-    const int64_t length = total->tree_n + 1;
-    const int64_t df = v.node[first].depth, ds = v.node[second].depth;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && idx_cap > 0) idx[0] = v.orig[e];
-    if (pf < 0 || ps < 0) return;
-    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
-        const McfNode nd = v.node[u];
-        const int32_t pu = cert_pos(v, a, u, &slot);
-        if (pu < 0 || nd.pred < 0) continue;
-        const int side = mcf_ray_side(pu, nd.size, pf, ps);
-        if (side != 1 && side != 2) continue;
-        const int64_t arc = nd.pred >> 1;
-        const int64_t at = side == 1 ? 1 + df - nd.depth : length - 1 - (ds - nd.depth);
-        if (at >= 1 && at < idx_cap && at < length) idx[at] = arc < m ? (int64_t)v.orig[arc] : arc;
-    }
-}
-
-// the flow of node u's artificial arc, > 0 towards the root, < 0 from it (a non-basic one carries nothing and counts as "up")
-__device__ __forceinline__ int64_t cut_art(const McfView& v, int32_t u) {
-    const McfNode nd = v.node[u];
-    const int64_t af = v.arcw[v.m + u].flow;
-    const bool up = (int64_t)(nd.pred >> 1) == v.m + u ? (nd.pred & 1) != 0 : true;
-    return up ? af : -af;
-}
-
-__global__ __launch_bounds__(kCertThreads) void k_cut_seed(McfView v, int32_t* __restrict__ mark, int32_t* __restrict__ level) {
-    const int32_t n = v.n_nodes - 1;
-    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) {
-        const bool seed = cut_art(v, u) > 0;
-        mark[u] = seed ? 1 : 0;
-        if (seed) *level = 1;
-    }
-}
-
-// mark[] is read while other lanes store r + 1 into entries that hold 0: a lane sees 0 or r + 1 there, and either is right
-__global__ __launch_bounds__(kCertThreads) void k_cut_round(McfView v, const int64_t* __restrict__ adj_off, const int64_t* __restrict__ adj,
-                                                            int32_t* mark, int32_t* __restrict__ level, int32_t r) {
-    const int32_t n = v.n_nodes - 1;
-    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) {
-        if (mark[u] != r) continue;
-        for (int64_t k = adj_off[u]; k < adj_off[u + 1]; ++k) {
-            const int64_t w = adj[k];
-            const int32_t other = (int32_t)(w >> 32);
-            if (other < 0 || other >= n || mark[other] != 0) continue;
-            const McfArcW aw = v.arcw[(w & 0xffffffff) >> 1];
-            if (mcf_cut_extends((w & 1) != 0, aw.cap, aw.flow)) { mark[other] = r + 1; *level = r + 1; }
-        }
-    }
-}
-
-// the caller's set, one byte per node, into level marks (1 / 0) -- and the marks back into bytes for S_out
-__global__ __launch_bounds__(kCertThreads) void k_cut_widen(const int8_t* __restrict__ in, int32_t n, int32_t* __restrict__ mark) {
-    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) mark[u] = in[u] != 0 ? 1 : 0;
-}
-__global__ __launch_bounds__(kCertThreads) void k_cut_narrow(const int32_t* __restrict__ mark, int32_t n, int8_t* __restrict__ out) {
-    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) out[u] = mark[u] != 0 ? 1 : 0;
-}
-
-template <bool NT>
-__global__ __launch_bounds__(kCertThreads) void k_cut_arcs(McfView v, const int32_t* __restrict__ mark, int32_t resident, McfCutAcc* __restrict__ part) {
-    __shared__ McfCutAcc s_wave[kCertThreads / 64];
-    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
-    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
-    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
-    McfCutAcc acc;
-    mcf_cut_init(&acc);
-    for (int64_t e = lo + lb * kCertThreads + threadIdx.x; e < hi; e += nlb * kCertThreads) {
-        const int32_t t = cert_ld<NT>(v.tail + e), hd = cert_ld<NT>(v.head + e);
-        const bool tin = mark[t] != 0, hin = mark[hd] != 0;
-        if (tin == hin) continue;
-        const int64_t* aw = reinterpret_cast<const int64_t*>(v.arcw + e);
-        mcf_cut_arc(&acc, tin, hin, cert_ld<NT>(aw), cert_ld<NT>(aw + 1), resident != 0);
-    }
-    cert_block_reduce<McfCutAcc, MCF_CUT_WORDS>(acc, s_wave, [](McfCutAcc* p, const McfCutAcc& q) { mcf_cut_merge(p, q); });
-    if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-__global__ __launch_bounds__(kCertThreads) void k_cut_nodes(McfView v, const int32_t* __restrict__ mark, const int64_t* __restrict__ supply, int32_t resident,
-                                                            McfCutAcc* __restrict__ part) {
-    __shared__ McfCutAcc s_wave[kCertThreads / 64];
-    const int32_t n = v.n_nodes - 1;
-    McfCutAcc acc;
-    mcf_cut_init(&acc);
-    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads)
-        if (mark[u] != 0) mcf_cut_node(&acc, supply[u], resident ? cut_art(v, u) : 0);
-    cert_block_reduce<McfCutAcc, MCF_CUT_WORDS>(acc, s_wave, [](McfCutAcc* p, const McfCutAcc& q) { mcf_cut_merge(p, q); });
-    if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// part[0 .. n) -> part[n]
-__global__ __launch_bounds__(kCertThreads) void k_cut_final(McfCutAcc* __restrict__ part, int n) {
-    __shared__ McfCutAcc s_wave[kCertThreads / 64];
-    McfCutAcc acc;
-    mcf_cut_init(&acc);
-    for (int i = threadIdx.x; i < n; i += kCertThreads) mcf_cut_merge(&acc, part[i]);
-    cert_block_reduce<McfCutAcc, MCF_CUT_WORDS>(acc, s_wave, [](McfCutAcc* p, const McfCutAcc& q) { mcf_cut_merge(p, q); });
-    if (threadIdx.x == 0) part[n] = acc;
-}
-
-// ------------------------------------------------------------------ mcf_update_rhs: new supplies / capacities under a resident basis
-// Flows and states of non-basic arcs do not depend on supplies; tree flows are subtree sums of node balances, and a
-// subtree is a contiguous range of the preorder.  Bytes each pass moves (n nodes, m arcs, k changes):
-//   k_rhs_scatter  one lane per change: 12 B in; a capacity change reads and writes the arc's 16 B walk record (+ 1 B state,
-//                  and 8 B reduced cost -> 4 B key code when a non-basic arc at capacity falls back to its lower bound);
-//                  a supply change is one 8 B store.
-//   k_rhs_balance  one lane per node: supply (8 B), position (4 B dense; 4 + 8 B blocked: slot, block base), and per
-//                  adjacency entry (2 m of them) 8 B entry + 1 B state + 16 B walk record of the NON-BASIC arcs only;
-//                  16 B out (the 128-bit balance, at the node's preorder position).
-//   k_rhs_scan_*   inclusive prefix sum over the n + 1 positions in three launches (chunk totals, scan of the totals by one
-//                  workgroup, scan of every chunk): 16 B per position read twice and written once.
-//   k_rhs_flows    one lane per node: node record (16 B), position, two 16 B prefix sums, the tree arc's walk record read
-//                  and its flow written (16 + 8 B); an artificial arc that turns round rewrites 4 B of the node record and
-//                  seeds 16 B of a jump record.  Census by wave reduction, one atomic per wave and counter.
-// All sums are 128-bit: 2^30 arcs at capacities below 2^60 stay below 2^91, so no prefix can wrap.
-constexpr int kRhsThreads = 256;
-constexpr int kRhsPer = 8;                             // positions per lane in the scan
-constexpr int kRhsChunk = kRhsThreads * kRhsPer;       // positions per workgroup
-enum { RHS_VIOL = 0, RHS_WRONG = 1, RHS_FLIPS = 2, RHS_MOVED = 3, RHS_COUNTERS = 4 };
-
-// logical preorder position of `node` in the view mcf_get_tree reports (cur: the copy that is current); -1: record out of range
-__device__ __forceinline__ int32_t rhs_pos(const McfView& v, int32_t cur, int32_t node) {
-    if (MCF_HAS_BPL(v)) {
-        const int32_t s = v.posbuf[0][node] & MCF_LOC_SLOT;
-        const int32_t b = s >> v.blk_shift;
-        if (b < 0 || b >= v.blk_cap) return -1;
-        const int32_t base = (cur ? v.bmeta[1] : v.bmeta[0])[b].base;
-        if (base == MCF_BLK_FREE) return -1;
-        const int32_t p = base + (s & ((1 << v.blk_shift) - 1));
-        return p < v.n_nodes ? p : -1;
-    }
-    const int32_t p = (cur ? v.posbuf[1] : v.posbuf[0])[node];
-    return (p < 0 || p >= v.n_nodes) ? -1 : p;
-}
-
-__device__ __forceinline__ void rhs_count(unsigned long long* info, int which, int32_t mine) {
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
-    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&info[which], (unsigned long long)mine);
-}
-
-__global__ __launch_bounds__(kRhsThreads) void k_rhs_scatter(McfView v, int64_t n_sup, const int32_t* __restrict__ snode, const int64_t* __restrict__ sval,
-                                                             int64_t* __restrict__ supply, int64_t n_cap, const int32_t* __restrict__ carc,
-                                                             const int64_t* __restrict__ cval, unsigned long long* __restrict__ info) {
-    const int64_t total = n_sup > n_cap ? n_sup : n_cap;
-    const int64_t stride = (int64_t)gridDim.x * kRhsThreads;
-    int32_t moved = 0;
-    for (int64_t i = (int64_t)blockIdx.x * kRhsThreads + threadIdx.x; i < total; i += stride) {
-        if (i < n_sup) supply[snode[i]] = sval[i];
-        if (i >= n_cap) continue;
-        const int32_t e = carc[i];
-        const int64_t nc = cval[i];
-        McfArcW w = v.arcw[e];
-        if (w.cap == nc) continue;
-        w.cap = nc;
-        if (v.state[e] == -1) {   // non-basic at capacity: the flow follows the capacity
-            ++moved;
-            if (nc >= MCF_INF || nc == 0) {   // no capacity to sit at: back to the lower bound (mcf_apply_basis' state rule)
-                v.state[e] = 1;
-                w.flow = 0;
-                if (v.vkey) v.vkey[e] = mcf_vkey(-v.rcache[e], v.vk_bigm, v.vk_half);
-            } else {
-                w.flow = nc;
-            }
-        }
-        v.arcw[e] = w;
-    }
-    rhs_count(info, RHS_MOVED, moved);
-}
-
-__global__ __launch_bounds__(kRhsThreads) void k_rhs_balance(McfView v, int32_t cur, const int64_t* __restrict__ supply, const int64_t* __restrict__ adj_off,
-                                                             const int64_t* __restrict__ adj, mcf_u128* __restrict__ bal) {
-    const int32_t n = v.n_nodes - 1;
-    for (int32_t u = blockIdx.x * kRhsThreads + threadIdx.x; u < n; u += gridDim.x * kRhsThreads) {
-        const int32_t p = rhs_pos(v, cur, u);
-        if (p < 0) continue;   // (a broken record: the flow pass counts it as a violation)
-        __int128 b = supply[u];
-        const int64_t lo = adj_off[u], hi = adj_off[u + 1];
-        for (int64_t k = lo; k < hi; ++k) {
-            const int64_t w = adj[k];
-            const int64_t e = (w & 0xffffffff) >> 1;
-            if (v.state[e] == 0) continue;   // basic arcs get their flow from the subtree sums
-            const int64_t f = v.arcw[e].flow;
-            b += (w & 1) ? -(__int128)f : (__int128)f;
-        }
-        bal[p] = (mcf_u128)b;
-    }
-}
-
-// thread t of a workgroup owns positions [chunk base + t * kRhsPer, + kRhsPer): 128 contiguous bytes, 16-byte accesses
-__global__ __launch_bounds__(kRhsThreads) void k_rhs_scan_totals(const mcf_u128* __restrict__ bal, int32_t count, mcf_u128* __restrict__ part) {
-    __shared__ mcf_u128 s[kRhsThreads / 64];
-    const int64_t base = (int64_t)blockIdx.x * kRhsChunk + (int64_t)threadIdx.x * kRhsPer;
-    mcf_u128 sum = 0;
-#pragma unroll
-    for (int k = 0; k < kRhsPer; ++k) if (base + k < count) sum += bal[base + k];
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t lo = __shfl_down((unsigned long long)(uint64_t)sum, off, 64), hi = __shfl_down((unsigned long long)(uint64_t)(sum >> 64), off, 64);
-        sum += ((mcf_u128)hi << 64) | lo;   // (lanes past the end add what their neighbours hold: only lane 0's sum is used)
-    }
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
-}
-
-// part[b] <- sum of part[0 .. b) (one workgroup, like k_bn_scan)
-__global__ __launch_bounds__(1024) void k_rhs_scan_parts(mcf_u128* __restrict__ part, int64_t nb) {
-    __shared__ mcf_u128 s[1024];
-    const int64_t per = (nb + 1023) / 1024, lo = threadIdx.x * per < nb ? threadIdx.x * per : nb, hi = lo + per < nb ? lo + per : nb;
-    mcf_u128 sum = 0;
-    for (int64_t b = lo; b < hi; ++b) sum += part[b];
-    s[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        mcf_u128 run = 0;
-        for (int k = 0; k < 1024; ++k) { const mcf_u128 x = s[k]; s[k] = run; run += x; }
-    }
-    __syncthreads();
-    mcf_u128 run = s[threadIdx.x];
-    for (int64_t b = lo; b < hi; ++b) { const mcf_u128 x = part[b]; part[b] = run; run += x; }
-}
-
-// bal[p] <- sum of bal[0 .. p] (inclusive, in place)
-__global__ __launch_bounds__(kRhsThreads) void k_rhs_scan_apply(mcf_u128* __restrict__ bal, int32_t count, const mcf_u128* __restrict__ part) {
-    __shared__ mcf_u128 s[kRhsThreads];
-    const int64_t base = (int64_t)blockIdx.x * kRhsChunk + (int64_t)threadIdx.x * kRhsPer;
-    mcf_u128 x[kRhsPer];
-    mcf_u128 sum = 0;
-#pragma unroll
-    for (int k = 0; k < kRhsPer; ++k) { x[k] = base + k < count ? bal[base + k] : (mcf_u128)0; sum += x[k]; x[k] = sum; }
-    s[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < kRhsThreads; off <<= 1) {   // Hillis-Steele over the lanes' totals
-        const mcf_u128 add = (int)threadIdx.x >= off ? s[threadIdx.x - off] : (mcf_u128)0;
-        __syncthreads();
-        s[threadIdx.x] += add;
-        __syncthreads();
-    }
-    const mcf_u128 before = part[blockIdx.x] + (threadIdx.x > 0 ? s[threadIdx.x - 1] : (mcf_u128)0);
-#pragma unroll
-    for (int k = 0; k < kRhsPer; ++k) if (base + k < count) bal[base + k] = x[k] + before;
-}
-
-__global__ __launch_bounds__(kRhsThreads) void k_rhs_flows(McfView v, int32_t cur, const mcf_u128* __restrict__ pre, int64_t bigm, McfJump* __restrict__ jump,
-                                                           unsigned long long* __restrict__ info) {
-    const int32_t N = v.n_nodes, n = N - 1;
-    const int64_t m = v.m;
-    int32_t viol = 0, wrong = 0, flips = 0;
-    for (int32_t u = blockIdx.x * kRhsThreads + threadIdx.x; u < n; u += gridDim.x * kRhsThreads) {
-        const McfNode nd = v.node[u];
-        const int32_t p = rhs_pos(v, cur, u);
-        if (p < 1 || nd.size < 1 || (int64_t)p + nd.size > N || nd.pred < 0) { ++viol; continue; }
-        const __int128 x = (__int128)(pre[p + nd.size - 1] - pre[p - 1]);   // surplus the subtree of u sends up
-        const int64_t a = nd.pred >> 1;
-        const bool up = (nd.pred & 1) != 0;
-        if (a < m) {
-            const __int128 f = up ? x : -x;
-            const int64_t cap = v.arcw[a].cap;
-            if (f < 0 || f > cap || f >= MCF_INF) { ++viol; continue; }
-            v.arcw[a].flow = (int64_t)f;
-            if ((up && cap < MCF_INF && f == cap) || (!up && f == 0)) ++wrong;
-        } else {
-            const __int128 ax = x < 0 ? -x : x;
-            if (ax >= MCF_INF) { ++viol; continue; }
-            v.arcw[a].flow = (int64_t)ax;
-            const bool nup = x >= 0;
-            if (nup != up) {   // the arc turns round: pi[u] = pi[root] -+ big-M, and with it every potential below
-                ++flips;
-                v.node[u].pred = (int32_t)((a << 1) | (nup ? 1 : 0));
-                jump[u].val = nup ? -2 * bigm : 2 * bigm;
-            }
-        }
-    }
-    rhs_count(info, RHS_VIOL, viol);
-    rhs_count(info, RHS_WRONG, wrong);
-    rhs_count(info, RHS_FLIPS, flips);
-}
+#include "mcf_passes_dev.h"
 
 }  // namespace
 
@@ -2864,6 +2106,14 @@ hipError_t h2d(mcf_handle* h, void* dst, const void* src, size_t bytes) {
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
 }
 
+// the captured graph carries the view and the launch shapes by value: whatever changes either drops it, and the next
+// batch captures a new one
+void drop_graph(mcf_handle* h) {
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    h->graph_batch = 0;
+}
+
 int upload_image(mcf_handle* h) {
     const McfHostImage& im = h->im;
     std::lock_guard<std::mutex> stage_lock(g_stage_mu);
@@ -2873,16 +2123,12 @@ int upload_image(mcf_handle* h) {
         h->rcached = true;
         h->overlap = h->overlap_cfg;
         h->view.rcache = h->d_rcache; h->view.vkey = h->d_vkey; h->view.dirty = h->d_dirty;
-        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-        if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-        h->graph_batch = 0;
+        drop_graph(h);
     }
     h->sw_pivots = 0; h->sw_subtree = 0;
     if (h->run_pairs != h->run_pairs_cfg) {   // (a fresh start gets the run shape back)
         h->run_pairs = h->run_pairs_cfg;
-        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-        if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-        h->graph_batch = 0;
+        drop_graph(h);
     }
     h->run_low = 0; h->run_seen = 0;
     HIP_TRY(h, h2d(h, h->d_tail, im.tail.data(), im.m_pad * 4));
@@ -3102,8 +2348,7 @@ void launch_pivot_triplet(mcf_handle* h, hipStream_t s, int slot = 0, int64_t ar
 
 int build_graph(mcf_handle* h, int batch) {
     if (h->graph_exec && h->graph_batch == batch) return MCF_OK;
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    drop_graph(h);
     if (h->overlap) {
         while (h->fork_ev.size() < (size_t)batch * 2) {
             hipEvent_t e;
@@ -3184,6 +2429,13 @@ int read_ctx(mcf_handle* h, hipStream_t s) {
 // the host copy of the control block, refreshed only when something ran since it was last read
 int sync_ctx(mcf_handle* h, hipStream_t s) { return (h->ctx_current && !h->external_driver) ? MCF_OK : read_ctx(h, s); }
 
+// Which copies of the preorder arrays hold the tree mcf_get_tree reports, a flip the last update left pending counted (c must be
+// current).  cur: dense position / order / size arrays and the blocked list's block table; arena: its slot arena.
+struct TreeSel { int32_t cur, arena; };
+TreeSel tree_sel(const McfCtx& c) {
+    return {c.cur ^ (c.pending_flip ? 1 : 0), c.arena ^ ((c.pending_flip && c.rebuild) ? 1 : 0)};
+}
+
 void free_all(mcf_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);   // (a borrowed stream may still hold this handle's work)
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
@@ -3209,142 +2461,9 @@ void free_all(mcf_handle* h) {
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
 }
 
-// ---- certificate on the device: host helpers
-// the caller's flows (caller's order, as they are) into the scratch buffer; nullptr stays nullptr
-int cert_upload_flow(mcf_handle* h, const int64_t* flow, const int64_t** dev) {
-    *dev = nullptr;
-    if (!flow || h->im.m == 0) return MCF_OK;
-    if (!h->d_ct_flow && dalloc(&h->d_ct_flow, (size_t)h->im.m) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc certificate flows"; return MCF_E_ALLOC; }
-    HIP_TRY(h, hipMemcpyAsync(h->d_ct_flow, flow, (size_t)h->im.m * 8, hipMemcpyHostToDevice, h->stream));
-    *dev = h->d_ct_flow;
-    return MCF_OK;
-}
-
-// (lazy scratch is allocated in groups; a group that could not be completed is given back whole)
-template <typename T> void cert_free(T** p) { (void)hipFree(*p); *p = nullptr; }
-
-// what the certificate needs beyond the solver's arrays: supplies, a FULL adjacency (need_adj), partial buffers, events
-int cert_prepare(mcf_handle* h, bool need_adj = true) {
-    const McfHostImage& im = h->im;
-    if (!h->d_ct_supply) {
-        if (dalloc(&h->d_ct_supply, (size_t)im.n) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc supplies"; return MCF_E_ALLOC; }
-        if (hipMemcpy(h->d_ct_supply, im.supply.data(), (size_t)im.n * 8, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError(); cert_free(&h->d_ct_supply); h->err = "hipMemcpy supplies"; return MCF_E_HIP;
-        }
-    }
-    const bool own_adj = h->d_adj && !h->view.rc_partial;   // (h->view.adj goes away with dropped reduced costs; the arrays stay)
-    if (need_adj && !own_adj && !h->d_ct_adj_off) {
-        std::vector<int64_t> off((size_t)im.n + 1, 0), adj((size_t)(2 * im.m));
-        for (int64_t e = 0; e < im.m; ++e) { off[(size_t)im.tail[e] + 1]++; off[(size_t)im.head[e] + 1]++; }
-        for (int32_t u = 0; u < im.n; ++u) off[(size_t)u + 1] += off[u];
-        std::vector<int64_t> fill(off.begin(), off.end() - 1);
-        for (int64_t e = 0; e < im.m; ++e) {
-            const int64_t t = im.tail[e], hd = im.head[e];
-            adj[(size_t)fill[t]++] = (hd << 32) | (e << 1) | 1;
-            adj[(size_t)fill[hd]++] = (t << 32) | (e << 1);
-        }
-        // a group is complete or absent: the guard above looks at its first pointer only
-        if (dalloc(&h->d_ct_adj_off, off.size()) != hipSuccess || dalloc(&h->d_ct_adj, adj.size()) != hipSuccess) {
-            (void)hipGetLastError(); cert_free(&h->d_ct_adj_off); cert_free(&h->d_ct_adj);
-            h->err = "hipMalloc certificate adjacency"; return MCF_E_ALLOC;
-        }
-        if (hipMemcpy(h->d_ct_adj_off, off.data(), off.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            (!adj.empty() && hipMemcpy(h->d_ct_adj, adj.data(), adj.size() * 8, hipMemcpyHostToDevice) != hipSuccess)) {
-            (void)hipGetLastError(); cert_free(&h->d_ct_adj_off); cert_free(&h->d_ct_adj);
-            h->err = "hipMemcpy certificate adjacency"; return MCF_E_HIP;
-        }
-    }
-    if (!h->d_ct_arc) {
-        if (dalloc(&h->d_ct_arc, kCertMaxBlocks + 1) != hipSuccess || dalloc(&h->d_ct_node, kCertMaxBlocks + 1) != hipSuccess ||
-            dalloc(&h->d_ct_csum, (size_t)im.n_nodes) != hipSuccess) {
-            (void)hipGetLastError(); cert_free(&h->d_ct_arc); cert_free(&h->d_ct_node); cert_free(&h->d_ct_csum);
-            h->err = "hipMalloc certificate partials"; return MCF_E_ALLOC;
-        }
-    }
-    for (hipEvent_t& e : h->ct_ev) if (!e) HIP_TRY(h, hipEventCreate(&e));
-    return MCF_OK;
-}
-
-
-// ---- shared by mcf_update_costs and mcf_update_rhs
-unsigned uc_blocks_for(int64_t items) { const int64_t b = (items + kUcThreads - 1) / kUcThreads; return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
-
-// caller's arc index -> engine arc index, and the stamps that resolve duplicates (arcs and nodes)
-void uc_index(mcf_handle* h) {
-    const McfHostImage& im = h->im;
-    if (!h->uc_inv.empty() || im.m == 0) return;
-    h->uc_inv.assign((size_t)im.m, 0);
-    for (int64_t e = 0; e < im.m; ++e) h->uc_inv[(size_t)im.orig[(size_t)e]] = (int32_t)e;
-    h->uc_stamp.assign((size_t)im.m, 0);
-}
-void uc_next_gen(mcf_handle* h) {
-    if (h->rhs_nstamp.empty()) h->rhs_nstamp.assign((size_t)h->im.n, 0);
-    if (++h->uc_gen == 0) {
-        std::fill(h->uc_stamp.begin(), h->uc_stamp.end(), 0u);
-        std::fill(h->rhs_nstamp.begin(), h->rhs_nstamp.end(), 0u);
-        h->uc_gen = 1;
-    }
-}
-
-// jump records (double buffered) and the info words
-int uc_alloc(mcf_handle* h) {
-    if (h->d_uc_info) return MCF_OK;
-    for (int a = 0; a < 2; ++a)
-        if (dalloc(&h->d_uc_jump[a], (size_t)h->im.n_nodes) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc jump records"; return MCF_E_ALLOC; }
-    if (dalloc(&h->d_uc_info, 2) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc update info"; return MCF_E_ALLOC; }
-    return MCF_OK;
-}
-
-// potentials from the seeded records in d_uc_jump[0]: rounds = ceil(log2(greatest depth)), at least the final one
-void uc_jump_rounds(mcf_handle* h, int32_t depth) {
-    const int32_t N = h->im.n_nodes;
-    hipStream_t s = h->stream;
-    int rounds = 1;
-    while (((int64_t)1 << rounds) < (int64_t)depth) ++rounds;
-    int cur = 0;
-    for (int r = 0; r < rounds; ++r) {
-        if (r + 1 < rounds) hipLaunchKernelGGL(k_uc_jump<false>, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfJump*)h->d_uc_jump[cur], h->d_uc_jump[cur ^ 1], h->d_pi, N);
-        else hipLaunchKernelGGL(k_uc_jump<true>, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfJump*)h->d_uc_jump[cur], h->d_uc_jump[cur ^ 1], h->d_pi, N);
-        cur ^= 1;
-    }
-}
-
-// The tail of both calls: resident reduced costs / key codes from the potentials (`rebuild`; only where the handle keeps
-// them), everything derived for pricing starts over, the control block says "running" again with its counters kept.
-// *h_ctx must be current (sync_ctx, and nothing since has touched the device's copy).
-int uc_finish(mcf_handle* h, bool rebuild) {
-    const McfHostImage& im = h->im;
-    hipStream_t s = h->stream;
-    if (rebuild && h->rcached) {   // (a handle that dropped its reduced costs, or never kept any, prices from the potentials)
-        int64_t pb = (im.m_pad / 4 / MCF_NUM_BUCKETS + kUcThreads * kUcUnroll - 1) / (kUcThreads * kUcUnroll);
-        pb = pb < 1 ? 1 : (pb > 2048 / MCF_NUM_BUCKETS ? 2048 / MCF_NUM_BUCKETS : pb);
-        hipLaunchKernelGGL(k_uc_rebuild, dim3((unsigned)pb * MCF_NUM_BUCKETS), dim3(kUcThreads), 0, s, h->view, im.m_pad);
-    }
-    // derived pricing state: candidate list and cache, clean / dirty marks, Devex weights, block cursor, tuner
-    HIP_TRY(h, hipMemsetAsync(h->d_cand, 0xff, kMaxPriceBlocks * sizeof(McfCand), s));
-    if (h->d_candx) HIP_TRY(h, hipMemsetAsync(h->d_candx, 0xff, kMaxPriceBlocks * sizeof(McfCandX), s));
-    if (h->d_dirty) HIP_TRY(h, hipMemsetAsync(h->d_dirty->flag, 1, sizeof(h->d_dirty->flag), s));
-    if (h->opt.rule == MCF_RULE_DEVEX_BLOCK) hipLaunchKernelGGL(k_uc_ones, dim3(uc_blocks_for(im.m_pad / 4)), dim3(kUcThreads), 0, s, reinterpret_cast<float4*>(h->d_weight), im.m_pad / 4);
-    HIP_TRY(h, hipGetLastError());
-    {
-        McfCtx& c = *h->h_ctx;
-        c.status = MCF_RUNNING;
-        c.limit_checked = 0;
-        c.unbounded_arc = -1;
-        c.minor_left = 0;
-        mcf_init_block_state(&c, h->opt.rule, im.m, h->opt.block_size);
-        if (h->opt.rule == MCF_RULE_DEVEX_BLOCK) {
-            if (h->opt.devex_tuner > 0) c.auto_tune = 1; else if (h->opt.devex_tuner < 0) c.auto_tune = 0;
-            if (h->opt.devex_stay > 0) c.devex_cyclic = 0;
-        }
-        HIP_TRY(h, hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    h->ctx_current = false;
-    return MCF_OK;
-}
-
 }  // namespace
+
+#include "mcf_passes_host.h"
 
 // ====================================================================== C ABI
 extern "C" {
@@ -3723,262 +2842,6 @@ int mcf_set_basis(mcf_handle* h, const int8_t* in_tree, const int8_t* at_upper) 
     return MCF_OK;
 }
 
-// Re-optimise after a cost change: the resident basis stays, potentials / reduced costs / key codes follow the new costs
-// (kernels k_uc_* above).  Everything is validated on the host before the first byte moves.
-int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int64_t* new_cost) {
-    if (!h) return MCF_E_BAD_ARG;
-    if (h->shards != 1) {
-        h->err = "mcf_update_costs: handle was created with shard_count > 1; sharded handles cannot change their costs";
-        return MCF_E_STATE;
-    }
-    if (count < 0 || (count > 0 && (!arc || !new_cost))) { h->err = "mcf_update_costs: bad count / null array"; return MCF_E_BAD_ARG; }
-    McfHostImage& im = h->im;
-    for (int64_t i = 0; i < count; ++i)
-        if (arc[i] < 0 || arc[i] >= im.m) { h->err = "mcf_update_costs: arc index out of range"; return MCF_E_BAD_ARG; }
-    for (int64_t i = 0; i < count; ++i)
-        if (new_cost[i] > INT32_MAX || new_cost[i] < -(int64_t)INT32_MAX) { h->err = "mcf_update_costs: |cost| must fit int32"; return MCF_E_RANGE; }
-    uc_index(h);
-    uc_next_gen(h);
-    // duplicates: the last entry wins (walk backwards, keep the first sighting of every arc)
-    std::vector<int32_t> ue, uc;
-    ue.reserve((size_t)count); uc.reserve((size_t)count);
-    int64_t max_abs = 0;
-    for (int64_t i = count - 1; i >= 0; --i) {
-        const int32_t e = h->uc_inv[(size_t)arc[i]];
-        if (h->uc_stamp[(size_t)e] == h->uc_gen) continue;
-        h->uc_stamp[(size_t)e] = h->uc_gen;
-        ue.push_back(e); uc.push_back((int32_t)new_cost[i]);
-        const int64_t a = new_cost[i] < 0 ? -new_cost[i] : new_cost[i];
-        if (a > max_abs) max_abs = a;
-    }
-    // big-M never shrinks; it grows when a new cost needs it (same rule as mcf_build_image)
-    int64_t big_m = im.big_m;
-    if ((max_abs + 1) * ((int64_t)im.n + 2) > big_m) big_m = (max_abs + 1) * ((int64_t)im.n + 2);
-    if (big_m >= ((int64_t)1 << 44)) { h->err = "mcf_update_costs: max|cost| * n too large for big-M"; return MCF_E_RANGE; }
-    const int64_t d_bigm = big_m - im.big_m;
-    const int64_t nu = (int64_t)ue.size();
-
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = uc_alloc(h);   // temporaries
-    if (rc) return rc;
-    if (nu > h->uc_cap) {
-        (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost);
-        h->d_uc_arc = nullptr; h->d_uc_cost = nullptr; h->uc_cap = 0;
-        const int64_t cap = nu + nu / 2 + 1024;
-        if (dalloc(&h->d_uc_arc, (size_t)cap) != hipSuccess || dalloc(&h->d_uc_cost, (size_t)cap) != hipSuccess) {
-            (void)hipGetLastError();
-            h->err = "hipMalloc cost changes";
-            return MCF_E_ALLOC;
-        }
-        h->uc_cap = cap;
-    }
-    rc = sync_ctx(h, h->stream);
-    if (rc) return rc;
-    if (h->h_ctx->status == MCF_INTERNAL_ERROR) { h->err = "mcf_update_costs: the handle's tree is not usable"; return MCF_E_STATE; }
-
-    hipStream_t s = h->stream;
-    const int32_t N = im.n_nodes;
-    auto blocks_for = uc_blocks_for;
-    if (nu > 0) {
-        HIP_TRY(h, hipMemcpyAsync(h->d_uc_arc, ue.data(), (size_t)nu * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(h->d_uc_cost, uc.data(), (size_t)nu * 4, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(h, hipMemsetAsync(h->d_uc_info, 0, 2 * sizeof(int32_t), s));
-    hipLaunchKernelGGL(k_uc_seed, dim3(blocks_for(N)), dim3(kUcThreads), 0, s, (const McfNode*)h->d_node, N, im.m, d_bigm, h->d_uc_jump[0], h->d_uc_info);
-    if (nu > 0)
-        hipLaunchKernelGGL(k_uc_scatter, dim3(blocks_for(nu)), dim3(kUcThreads), 0, s, nu, (const int32_t*)h->d_uc_arc, (const int32_t*)h->d_uc_cost,
-                           h->d_cost, (const int8_t*)h->d_state, (const int32_t*)h->d_tail, (const int32_t*)h->d_head, (const McfNode*)h->d_node,
-                           h->d_uc_jump[0], h->d_uc_info);
-    HIP_TRY(h, hipGetLastError());
-    int32_t info[2] = {0, 0};
-    HIP_TRY(h, hipMemcpyAsync(info, h->d_uc_info, sizeof info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));   // (also: the pageable sources above are free again)
-    // potentials: only when a tree arc changed (or big-M grew)
-    if (info[1] > 0 || d_bigm != 0) uc_jump_rounds(h, info[0]);
-    // the view's big-M first: the key codes below are formed with it, and captured graphs carry the view by value
-    if (d_bigm != 0) {
-        h->view.vk_bigm = big_m;
-        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-        if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-        h->graph_batch = 0;
-    }
-    rc = uc_finish(h, true);
-    if (rc) return rc;
-    // host image: a later mcf_reset / mcf_set_basis (which rebuild its potentials and reduced costs from these) and the
-    // objective of mcf_get_result use the new costs
-    for (int64_t i = 0; i < nu; ++i) { im.cost[(size_t)ue[(size_t)i]] = uc[(size_t)i]; im.cost64[(size_t)ue[(size_t)i]] = uc[(size_t)i]; }
-    im.big_m = big_m;
-    return MCF_OK;
-}
-
-// Re-optimise after supplies / capacities changed (kernels k_rhs_* above).  Non-basic flows follow their capacities, tree
-// flows are recomputed as subtree sums of the node balances, and a census decides: the basis stays (path 0), is repaired
-// on the host at mcf_set_basis cost (path 1, mcf_repair_basis), or the handle goes to the cold start (path 2).
-int mcf_update_rhs(mcf_handle* h, int64_t n_sup, const int64_t* node, const int64_t* new_supply, int64_t n_cap,
-                   const int64_t* arc, const int64_t* new_cap, mcf_rhs_report* out) {
-    if (!h) return MCF_E_BAD_ARG;
-    if (h->shards != 1) {
-        h->err = "mcf_update_rhs: handle was created with shard_count > 1; sharded handles cannot change their supplies / capacities";
-        return MCF_E_STATE;
-    }
-    if (n_sup < 0 || n_cap < 0 || (n_sup > 0 && (!node || !new_supply)) || (n_cap > 0 && (!arc || !new_cap))) {
-        h->err = "mcf_update_rhs: bad count / null array";
-        return MCF_E_BAD_ARG;
-    }
-    McfHostImage& im = h->im;
-    for (int64_t i = 0; i < n_sup; ++i)
-        if (node[i] < 0 || node[i] >= im.n) { h->err = "mcf_update_rhs: node index out of range"; return MCF_E_BAD_ARG; }
-    for (int64_t i = 0; i < n_cap; ++i)
-        if (arc[i] < 0 || arc[i] >= im.m) { h->err = "mcf_update_rhs: arc index out of range"; return MCF_E_BAD_ARG; }
-    uc_index(h);
-    uc_next_gen(h);
-    // duplicates: the last entry wins (walk backwards, keep the first sighting); nodes first, then arcs, in one pair of arrays
-    std::vector<int32_t> idx;
-    std::vector<int64_t> val;
-    idx.reserve((size_t)(n_sup + n_cap)); val.reserve((size_t)(n_sup + n_cap));
-    __int128 total = 0, positive = 0;
-    for (int32_t v = 0; v < im.n; ++v) if (im.supply[(size_t)v] > 0) positive += im.supply[(size_t)v];
-    for (int64_t i = n_sup - 1; i >= 0; --i) {
-        const int32_t v = (int32_t)node[i];
-        if (h->rhs_nstamp[(size_t)v] == h->uc_gen) continue;
-        h->rhs_nstamp[(size_t)v] = h->uc_gen;
-        idx.push_back(v); val.push_back(new_supply[i]);
-        const int64_t was = im.supply[(size_t)v];
-        total += (__int128)new_supply[i] - was;
-        positive += (__int128)(new_supply[i] > 0 ? new_supply[i] : 0) - (was > 0 ? was : 0);
-    }
-    if (total != 0) { h->err = "mcf_update_rhs: supplies do not balance"; return MCF_E_RANGE; }
-    if (positive >= (__int128)MCF_INF) { h->err = "mcf_update_rhs: the sum of the positive supplies must stay below 2^60"; return MCF_E_RANGE; }
-    const int64_t ns = (int64_t)idx.size();
-    for (int64_t i = n_cap - 1; i >= 0; --i) {
-        const int32_t e = h->uc_inv[(size_t)arc[i]];
-        if (h->uc_stamp[(size_t)e] == h->uc_gen) continue;
-        h->uc_stamp[(size_t)e] = h->uc_gen;
-        idx.push_back(e); val.push_back((new_cap[i] < 0 || new_cap[i] >= MCF_INF) ? MCF_INF : new_cap[i]);
-    }
-    const int64_t nc = (int64_t)idx.size() - ns;
-
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = uc_alloc(h);
-    if (rc) return rc;
-    if ((rc = cert_prepare(h)) != MCF_OK) return rc;   // device supplies, a full adjacency, two events
-    const int32_t N = im.n_nodes;
-    const int64_t chunks = ((int64_t)N + kRhsChunk - 1) / kRhsChunk;
-    if (!h->d_rhs_bal) {
-        if (dalloc(&h->d_rhs_bal, (size_t)N) != hipSuccess || dalloc(&h->d_rhs_part, (size_t)chunks) != hipSuccess ||
-            dalloc(&h->d_rhs_info, (size_t)RHS_COUNTERS) != hipSuccess) {
-            (void)hipGetLastError(); cert_free(&h->d_rhs_bal); cert_free(&h->d_rhs_part); cert_free(&h->d_rhs_info);
-            h->err = "hipMalloc balances"; return MCF_E_ALLOC;
-        }
-    }
-    if (ns + nc > h->rhs_cap) {
-        cert_free(&h->d_rhs_idx); cert_free(&h->d_rhs_val); h->rhs_cap = 0;
-        const int64_t cap = (ns + nc) + (ns + nc) / 2 + 1024;
-        if (dalloc(&h->d_rhs_idx, (size_t)cap) != hipSuccess || dalloc(&h->d_rhs_val, (size_t)cap) != hipSuccess) {
-            (void)hipGetLastError(); cert_free(&h->d_rhs_idx); cert_free(&h->d_rhs_val);
-            h->err = "hipMalloc supply / capacity changes"; return MCF_E_ALLOC;
-        }
-        h->rhs_cap = cap;
-    }
-    rc = sync_ctx(h, h->stream);
-    if (rc) return rc;
-    if (h->h_ctx->status == MCF_INTERNAL_ERROR) { h->err = "mcf_update_rhs: the handle's tree is not usable"; return MCF_E_STATE; }
-
-    // ---- device passes
-    hipStream_t s = h->stream;
-    const int32_t cur = h->h_ctx->cur ^ (h->h_ctx->pending_flip ? 1 : 0);   // as mcf_get_tree reads the arrays
-    const bool own_adj = h->d_adj && !h->view.rc_partial;
-    McfView vw = h->view;
-    if (h->rcached) { vw.rcache = h->d_rcache; } else { vw.vkey = nullptr; }   // (key codes are patched only where they are kept)
-    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
-    if (ns + nc > 0) {
-        HIP_TRY(h, hipMemcpyAsync(h->d_rhs_idx, idx.data(), (size_t)(ns + nc) * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(h->d_rhs_val, val.data(), (size_t)(ns + nc) * 8, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(h, hipMemsetAsync(h->d_rhs_info, 0, RHS_COUNTERS * sizeof(unsigned long long), s));
-    HIP_TRY(h, hipMemsetAsync(h->d_uc_info, 0, 2 * sizeof(int32_t), s));
-    HIP_TRY(h, hipMemsetAsync(h->d_rhs_bal, 0, (size_t)N * sizeof(mcf_u128), s));
-    if (ns + nc > 0)
-        hipLaunchKernelGGL(k_rhs_scatter, dim3(uc_blocks_for(ns > nc ? ns : nc)), dim3(kRhsThreads), 0, s, vw, ns, (const int32_t*)h->d_rhs_idx,
-                           (const int64_t*)h->d_rhs_val, h->d_ct_supply, nc, (const int32_t*)(h->d_rhs_idx + ns), (const int64_t*)(h->d_rhs_val + ns), h->d_rhs_info);
-    hipLaunchKernelGGL(k_rhs_balance, dim3(uc_blocks_for(N)), dim3(kRhsThreads), 0, s, vw, cur, (const int64_t*)h->d_ct_supply,
-                       (const int64_t*)(own_adj ? h->d_adj_off : h->d_ct_adj_off), (const int64_t*)(own_adj ? h->d_adj : h->d_ct_adj), h->d_rhs_bal);
-    hipLaunchKernelGGL(k_rhs_scan_totals, dim3((unsigned)chunks), dim3(kRhsThreads), 0, s, (const mcf_u128*)h->d_rhs_bal, N, h->d_rhs_part);
-    hipLaunchKernelGGL(k_rhs_scan_parts, dim3(1), dim3(1024), 0, s, h->d_rhs_part, chunks);
-    hipLaunchKernelGGL(k_rhs_scan_apply, dim3((unsigned)chunks), dim3(kRhsThreads), 0, s, h->d_rhs_bal, N, (const mcf_u128*)h->d_rhs_part);
-    // jump records for the potentials below an artificial arc that turns round (seeded with 0; the flow pass marks the turns)
-    hipLaunchKernelGGL(k_uc_seed, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfNode*)h->d_node, N, im.m, (int64_t)0, h->d_uc_jump[0], h->d_uc_info);
-    hipLaunchKernelGGL(k_rhs_flows, dim3(uc_blocks_for(N)), dim3(kRhsThreads), 0, s, vw, cur, (const mcf_u128*)h->d_rhs_bal, im.big_m, h->d_uc_jump[0], h->d_rhs_info);
-    HIP_TRY(h, hipGetLastError());
-    unsigned long long info[RHS_COUNTERS] = {0, 0, 0, 0};
-    int32_t depth[2] = {0, 0};
-    HIP_TRY(h, hipMemcpyAsync(info, h->d_rhs_info, sizeof info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(depth, h->d_uc_info, sizeof depth, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));   // (also: the pageable sources above are free again)
-
-    // host image: the objective, a later mcf_reset / mcf_set_basis and the repair below use the new data
-    for (int64_t i = 0; i < ns; ++i) im.supply[(size_t)idx[(size_t)i]] = val[(size_t)i];
-    for (int64_t i = ns; i < ns + nc; ++i) im.arcw[(size_t)idx[(size_t)i]].cap = val[(size_t)i];
-
-    mcf_rhs_report rep;
-    std::memset(&rep, 0, sizeof rep);
-    rep.tree_violations = (int64_t)info[RHS_VIOL];
-    rep.wrong_way = (int64_t)info[RHS_WRONG];
-    rep.art_flips = (int64_t)info[RHS_FLIPS];
-    rep.upper_moved = (int64_t)info[RHS_MOVED];
-    if (rep.tree_violations == 0 && rep.wrong_way == 0) {
-        // ---- path 0: the basis stays
-        if (rep.art_flips > 0) uc_jump_rounds(h, depth[0]);
-        if ((rc = uc_finish(h, rep.art_flips > 0)) != MCF_OK) return rc;
-        HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
-        HIP_TRY(h, hipEventSynchronize(h->ct_ev[1]));
-    } else {
-        // ---- path 1: states and node records come down, the basis is repaired on the host and installed as mcf_set_basis
-        // does; path 2 (cold start) when the repair refuses
-        HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
-        std::vector<int8_t> st((size_t)im.m_pad), in_tree((size_t)(im.m ? im.m : 1), 0), at_upper((size_t)(im.m ? im.m : 1), 0), hang((size_t)im.n, 0);
-        std::vector<McfNode> nodes((size_t)N);
-        HIP_TRY(h, hipMemcpy(st.data(), h->d_state, st.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(h, hipMemcpy(nodes.data(), h->d_node, nodes.size() * sizeof(McfNode), hipMemcpyDeviceToHost));
-        for (int64_t e = 0; e < im.m; ++e) {
-            in_tree[(size_t)im.orig[(size_t)e]] = st[(size_t)e] == 0;
-            at_upper[(size_t)im.orig[(size_t)e]] = st[(size_t)e] == -1;
-        }
-        for (int32_t v = 0; v < im.n; ++v) hang[(size_t)v] = nodes[(size_t)v].pred >= 0 && (int64_t)(nodes[(size_t)v].pred >> 1) >= im.m;
-        McfRepairReport rr;
-        const std::string msg = mcf_repair_basis(im, in_tree.data(), at_upper.data(), hang.data(), &rr);
-        rep.path = 1;
-        rep.arcs_cut = rr.arcs_cut;
-        rep.repair_rounds = rr.rounds;
-        if (!msg.empty()) { mcf_init_cold_basis(im); rep.path = 2; rep.arcs_cut = 0; }
-        mcf_refresh_rcache(im);
-        // the counters keep counting: upload_image starts them over, so they are carried across it
-        const McfCtx was = *h->h_ctx;
-        const mcf_stats stats_was = h->stats;
-        if ((rc = upload_image(h)) != MCF_OK) return rc;
-        McfCtx& c = *h->h_ctx;
-        c.pivots = was.pivots; c.degenerate = was.degenerate; c.bound_flips = was.bound_flips; c.arcs_priced = was.arcs_priced;
-        c.nodes_moved = was.nodes_moved; c.subtree_nodes = was.subtree_nodes; c.cycle_arcs = was.cycle_arcs;
-        c.scans = was.scans; c.scan_rounds = was.scan_rounds; c.minor_pivots = was.minor_pivots; c.major_sweeps = was.major_sweeps;
-        c.rebuilds = was.rebuilds;
-        const int64_t price_bytes = h->stats.price_bytes;
-        h->stats = stats_was;
-        h->stats.price_bytes = price_bytes;
-        h->stats.rc_dropped_at = 0; h->stats.run_left_at = 0;   // (a fresh image keeps its reduced costs and its run shape again)
-        h->sw_pivots = c.pivots; h->sw_subtree = c.subtree_nodes; h->run_seen = c.pivots;
-        HIP_TRY(h, hipMemsetAsync(h->d_cand, 0xff, kMaxPriceBlocks * sizeof(McfCand), s));
-        if (h->d_candx) HIP_TRY(h, hipMemsetAsync(h->d_candx, 0xff, kMaxPriceBlocks * sizeof(McfCandX), s));
-        HIP_TRY(h, hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        h->ctx_current = true;
-    }
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, h->ct_ev[0], h->ct_ev[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
-    rep.device_ms = ms;
-    if (out) *out = rep;
-    return MCF_OK;
-}
-
 int mcf_set_max_pivots(mcf_handle* h, int64_t max_total_pivots) {
     if (!h) return MCF_E_BAD_ARG;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -4091,9 +2954,7 @@ int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user,
                 if (h->run_low >= 3) {
                     h->run_pairs = 0;
                     h->stats.run_left_at = h->h_ctx->pivots;
-                    (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr;
-                    (void)hipGraphDestroy(h->graph); h->graph = nullptr;
-                    h->graph_batch = 0;
+                    drop_graph(h);
                     rc = build_graph(h, batch);
                     if (rc) return rc;
                 }
@@ -4114,9 +2975,7 @@ int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user,
                         h->view.rcache = nullptr; h->view.vkey = nullptr; h->view.dirty = nullptr;
                         h->stats.rc_dropped_at = h->h_ctx->pivots;
                         if (graph) {
-                            (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr;
-                            (void)hipGraphDestroy(h->graph); h->graph = nullptr;
-                            h->graph_batch = 0;
+                            drop_graph(h);
                             rc = build_graph(h, batch);
                             if (rc) return rc;
                         }
@@ -4567,10 +3426,9 @@ int mcf_get_tree(mcf_handle* h, int32_t* parent, int32_t* pred_arc, int32_t* siz
         if (size) size[v] = nodes[v].size;
         if (depth) depth[v] = nodes[v].depth;
     }
-    const int cur = h->h_ctx->cur ^ (h->h_ctx->pending_flip ? 1 : 0);
+    const int cur = tree_sel(*h->h_ctx).cur, arena = tree_sel(*h->h_ctx).arena;
     if (h->bpl) {
         // blocked preorder list: flatten the blocks handed out so far into the logical arrays the dense layout would hold
-        const int arena = h->h_ctx->arena ^ ((h->h_ctx->pending_flip && h->h_ctx->rebuild) ? 1 : 0);
         const int32_t nb = h->h_ctx->alloc_next;
         const size_t slots = (size_t)nb << h->bpl_shift;
         std::vector<int32_t> tok(slots), psz(slots), ext((size_t)nb);
@@ -4657,289 +3515,6 @@ int mcf_get_weights(mcf_handle* h, float* weight_out) {
     std::vector<float> w(im.m_pad);
     HIP_TRY(h, hipMemcpy(w.data(), h->d_weight, w.size() * 4, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < im.m; ++i) weight_out[im.orig[i]] = w[i];
-    return MCF_OK;
-}
-
-// ---- certificate on the device (include/mcf.h)
-int mcf_certify(mcf_handle* h, const int64_t* flow, const int64_t* potential, uint32_t checks, mcf_certificate* out) {
-    if (!h || !out || (checks & ~MCF_CERT_ALL)) return MCF_E_BAD_ARG;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = sync_ctx(h, h->stream);
-    if (rc) return rc;
-    const McfHostImage& im = h->im;
-    if (!checks) checks = MCF_CERT_ALL;
-    if (flow || potential) checks &= ~(MCF_CERT_BASIS | MCF_CERT_PRICING);
-    std::vector<int64_t> pi_host;   // (outlives the asynchronous copy: the call ends with a synchronisation)
-    if (potential) {
-        pi_host.assign((size_t)im.n_nodes, 0);
-        for (int32_t v = 0; v < im.n; ++v) {
-            if (potential[v] > ((int64_t)1 << 61) || potential[v] < -((int64_t)1 << 61)) { h->err = "mcf_certify: |potential| must not exceed 2^61"; return MCF_E_RANGE; }
-            pi_host[(size_t)v] = potential[v];
-        }
-    }
-    if ((rc = cert_prepare(h)) != MCF_OK) return rc;
-    CertArgs a;
-    std::memset(&a, 0, sizeof a);
-    if ((rc = cert_upload_flow(h, flow, &a.cflow)) != MCF_OK) return rc;
-    a.pi = h->d_pi;
-    if (potential) {
-        if (!h->d_ct_pi && dalloc(&h->d_ct_pi, (size_t)im.n_nodes) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc certificate potentials"; return MCF_E_ALLOC; }
-        HIP_TRY(h, hipMemcpyAsync(h->d_ct_pi, pi_host.data(), pi_host.size() * 8, hipMemcpyHostToDevice, h->stream));
-        a.pi = h->d_ct_pi;
-    }
-    const bool own_adj = h->d_adj && !h->view.rc_partial;
-    a.supply = h->d_ct_supply;
-    a.adj_off = own_adj ? h->d_adj_off : h->d_ct_adj_off;
-    a.adj = own_adj ? h->d_adj : h->d_ct_adj;
-    a.rcache = (checks & MCF_CERT_PRICING) && h->rcached ? h->d_rcache : nullptr;
-    a.vkey = (checks & MCF_CERT_PRICING) && h->rcached ? h->view.vkey : nullptr;
-    a.csum = h->d_ct_csum;
-    a.checks = checks;
-    a.resident_flow = flow ? 0 : 1;
-    a.cur = h->h_ctx->cur ^ (h->h_ctx->pending_flip ? 1 : 0);                                   // as mcf_get_tree reads the arrays
-    a.arena = h->h_ctx->arena ^ ((h->h_ctx->pending_flip && h->h_ctx->rebuild) ? 1 : 0);
-    a.partial = h->view.rc_partial;
-    a.shard = h->shard; a.shards = h->shards;
-    a.bigm = im.big_m;
-    const int ab = mcf_price_blocks(im.m, 1, 0);
-    int64_t nb64 = ((int64_t)im.n_nodes + kCertThreads - 1) / kCertThreads;
-    const int nb = (int)(nb64 < kCertMaxBlocks ? nb64 : kCertMaxBlocks);
-    hipStream_t s = h->stream;
-    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
-    if (im.m >= kIncrementalMinArcs) hipLaunchKernelGGL(k_cert_arcs<true>, dim3(ab), dim3(kCertThreads), 0, s, h->view, a, h->d_ct_arc);
-    else hipLaunchKernelGGL(k_cert_arcs<false>, dim3(ab), dim3(kCertThreads), 0, s, h->view, a, h->d_ct_arc);
-    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
-    if (checks & MCF_CERT_BASIS) {
-        HIP_TRY(h, hipMemsetAsync(h->d_ct_csum, 0, (size_t)im.n_nodes * 4, s));
-        hipLaunchKernelGGL(k_cert_child, dim3(nb), dim3(kCertThreads), 0, s, h->view, h->d_ct_csum);
-    }
-    hipLaunchKernelGGL(k_cert_nodes, dim3(nb), dim3(kCertThreads), 0, s, h->view, a, h->d_ct_node);
-    HIP_TRY(h, hipEventRecord(h->ct_ev[2], s));
-    hipLaunchKernelGGL(k_cert_final, dim3(1), dim3(kCertThreads), 0, s, h->d_ct_arc, ab, h->d_ct_node, nb);
-    HIP_TRY(h, hipGetLastError());
-    McfCertArcAcc A;
-    McfCertNodeAcc N;
-    HIP_TRY(h, hipMemcpyAsync(&A, h->d_ct_arc + ab, sizeof A, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(&N, h->d_ct_node + nb, sizeof N, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    float ms_a = 0, ms_n = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms_a, h->ct_ev[0], h->ct_ev[1]));
-    HIP_TRY(h, hipEventElapsedTime(&ms_n, h->ct_ev[1], h->ct_ev[2]));
-
-    mcf_certificate c;
-    std::memset(&c, 0, sizeof c);
-    auto idx = [](int64_t i) { return i == MCF_CERT_NONE ? (int64_t)-1 : i; };
-    auto put = [](int64_t* hi_lo, __int128 x) { hi_lo[0] = (int64_t)(x >> 64); hi_lo[1] = (int64_t)(uint64_t)x; };
-    c.checks = checks;
-    c.negative_flow_count = A.neg_n; c.over_capacity_count = A.over_n; c.bounds_worst = A.bnd_w; c.bounds_worst_arc = idx(A.bnd_i);
-    c.imbalance_count = N.imb_n; c.imbalance_worst = N.imb_w; c.imbalance_worst_node = idx(N.imb_i);
-    c.dual_lower_count = A.dlo_n; c.dual_lower_worst = A.dlo_w; c.dual_lower_arc = idx(A.dlo_i);
-    c.dual_upper_count = A.dup_n; c.dual_upper_worst = A.dup_w; c.dual_upper_arc = idx(A.dup_i);
-    const int64_t art_resident = (int64_t)N.art_lo;   // (below 2^60: "Numeric domain")
-    c.artificial_flow = flow ? 0 : art_resident;
-    c.big_m = im.big_m;
-    const __int128 primal = (__int128)(((mcf_u128)A.primal_hi << 64) | A.primal_lo);
-    const __int128 bigm_term = (__int128)c.big_m * c.artificial_flow;
-    const __int128 dual = (__int128)((((mcf_u128)N.dnode_hi << 64) | N.dnode_lo) + (((mcf_u128)A.dcap_hi << 64) | A.dcap_lo));
-    const __int128 gap = primal + bigm_term - dual;
-    if (checks & MCF_CERT_OBJECTIVES) { put(c.primal, primal); put(c.bigm_term, bigm_term); put(c.dual, dual); put(c.gap, gap); }
-    c.basic_arcs = A.basic_n + N.art_basic;
-    c.basic_count_mismatch = (checks & MCF_CERT_BASIS) && c.basic_arcs != im.n ? 1 : 0;
-    c.tree_rc_count = N.tree_rc_bad; c.state_flow_count = A.stf_n; c.tree_shape_count = N.shape_bad; c.strong_count = N.strong_bad;
-    c.rc_compared = A.rc_n; c.rc_mismatch_count = A.rc_bad; c.key_compared = A.key_n; c.key_mismatch_count = A.key_bad;
-    c.saturated_arcs = A.sat_n;
-    c.arc_pass_ms = ms_a; c.node_pass_ms = ms_n;
-    const int32_t st = h->h_ctx->status;
-    c.status = st == MCF_RUNNING ? -1 : st == MCF_UNBOUNDED ? MCF_ST_UNBOUNDED
-               : st == MCF_OPTIMAL ? (art_resident > 0 ? MCF_ST_INFEASIBLE : MCF_ST_OPTIMAL) : MCF_ST_ITERATION_LIMIT;
-    const uint32_t need = MCF_CERT_BOUNDS | MCF_CERT_CONSERVATION | MCF_CERT_DUAL | MCF_CERT_OBJECTIVES;
-    c.verdict = MCF_CERT_NOT_PROVEN;
-    if ((checks & need) == need && !A.neg_n && !A.over_n && !N.imb_n && !A.dlo_n && !A.dup_n && gap == 0)
-        c.verdict = c.artificial_flow > 0 ? MCF_CERT_INFEASIBLE : MCF_CERT_OPTIMAL;
-    c.proves_status = (c.status == MCF_ST_OPTIMAL && c.verdict == MCF_CERT_OPTIMAL) || (c.status == MCF_ST_INFEASIBLE && c.verdict == MCF_CERT_INFEASIBLE) ? 1 : 0;
-    *out = c;
-    return MCF_OK;
-}
-
-int mcf_bottlenecks(mcf_handle* h, const int64_t* flow, int64_t num, int64_t den, int64_t* idx_out, int64_t idx_cap, int64_t* count) {
-    if (!h || !count || num < 0 || den <= 0 || idx_cap < 0 || (idx_cap > 0 && !idx_out)) return MCF_E_BAD_ARG;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const McfHostImage& im = h->im;
-    *count = 0;
-    if (im.m == 0) return MCF_OK;
-    const int64_t nb = (im.m + kBnChunk - 1) / kBnChunk;
-    if (!h->d_bn_flag) {
-        if (dalloc(&h->d_bn_flag, (size_t)im.m) != hipSuccess || dalloc(&h->d_bn_cnt, (size_t)nb) != hipSuccess || dalloc(&h->d_bn_off, (size_t)nb + 1) != hipSuccess) {
-            (void)hipGetLastError(); cert_free(&h->d_bn_flag); cert_free(&h->d_bn_cnt); cert_free(&h->d_bn_off);
-            h->err = "hipMalloc bottleneck scratch"; return MCF_E_ALLOC;
-        }
-    }
-    const int64_t want = idx_cap < im.m ? idx_cap : im.m;
-    if (want > h->bn_idx_cap) {
-        (void)hipFree(h->d_bn_idx); h->d_bn_idx = nullptr; h->bn_idx_cap = 0;
-        if (dalloc(&h->d_bn_idx, (size_t)want) != hipSuccess) { (void)hipGetLastError(); h->err = "hipMalloc bottleneck indices"; return MCF_E_ALLOC; }
-        h->bn_idx_cap = want;
-    }
-    const int64_t* cflow = nullptr;
-    int rc = cert_upload_flow(h, flow, &cflow);
-    if (rc) return rc;
-    hipStream_t s = h->stream;
-    int64_t fb = (im.m + kCertThreads - 1) / kCertThreads;
-    if (fb > kCertMaxBlocks) fb = kCertMaxBlocks;
-    hipLaunchKernelGGL(k_bn_flag, dim3((unsigned)fb), dim3(kCertThreads), 0, s, h->view, cflow, num, den, h->d_bn_flag);
-    hipLaunchKernelGGL(k_bn_count, dim3((unsigned)nb), dim3(kCertThreads), 0, s, h->d_bn_flag, im.m, h->d_bn_cnt);
-    hipLaunchKernelGGL(k_bn_scan, dim3(1), dim3(1024), 0, s, h->d_bn_cnt, nb, h->d_bn_off);
-    if (want > 0) hipLaunchKernelGGL(k_bn_write, dim3((unsigned)nb), dim3(kCertThreads), 0, s, h->d_bn_flag, im.m, h->d_bn_off, h->d_bn_idx, want);
-    HIP_TRY(h, hipGetLastError());
-    int64_t total = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, h->d_bn_off + nb, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    *count = total;
-    const int64_t got = total < want ? total : want;
-    if (got > 0) HIP_TRY(h, hipMemcpy(idx_out, h->d_bn_idx, (size_t)got * 8, hipMemcpyDeviceToHost));
-    return MCF_OK;
-}
-
-// ---- witnesses of the unbounded and the infeasible verdict (include/mcf.h)
-int mcf_certify_ray(mcf_handle* h, int64_t arc, int64_t* idx_out, int64_t idx_cap, mcf_ray* out) {
-    if (!h || !out || idx_cap < 0 || (idx_cap > 0 && !idx_out)) return MCF_E_BAD_ARG;
-    const McfHostImage& im = h->im;
-    if (arc < -1 || arc >= im.m) { h->err = "mcf_certify_ray: arc index outside [0, m)"; return MCF_E_BAD_ARG; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = sync_ctx(h, h->stream);
-    if (rc) return rc;
-    int64_t e;
-    if (arc < 0) {
-        if (h->h_ctx->status != MCF_UNBOUNDED || h->h_ctx->unbounded_arc < 0 || h->h_ctx->unbounded_arc >= im.m) {
-            h->err = "mcf_certify_ray: the handle's status is not unbounded"; return MCF_E_STATE;
-        }
-        e = h->h_ctx->unbounded_arc;
-    } else {
-        uc_index(h);
-        e = h->uc_inv[(size_t)arc];
-    }
-    int8_t st = 0;
-    HIP_TRY(h, hipMemcpy(&st, h->d_state + e, 1, hipMemcpyDeviceToHost));
-    if (st == 0) { h->err = "mcf_certify_ray: the arc is basic"; return MCF_E_BAD_ARG; }
-    const int32_t backward = st < 0 ? 1 : 0;
-    if (!h->d_ray_part) {
-        if (dalloc(&h->d_ray_part, kCertMaxBlocks + 1) != hipSuccess || dalloc(&h->d_ray_idx, (size_t)im.n_nodes) != hipSuccess) {
-            (void)hipGetLastError(); cert_free(&h->d_ray_part); cert_free(&h->d_ray_idx);
-            h->err = "hipMalloc ray scratch"; return MCF_E_ALLOC;
-        }
-    }
-    for (hipEvent_t& ev : h->ct_ev) if (!ev) HIP_TRY(h, hipEventCreate(&ev));
-    CertArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.pi = h->d_pi;
-    a.cur = h->h_ctx->cur ^ (h->h_ctx->pending_flip ? 1 : 0);                                   // as mcf_get_tree reads the arrays
-    a.arena = h->h_ctx->arena ^ ((h->h_ctx->pending_flip && h->h_ctx->rebuild) ? 1 : 0);
-    a.bigm = im.big_m;
-    int64_t nb64 = ((int64_t)im.n_nodes + kCertThreads - 1) / kCertThreads;
-    const int nb = (int)(nb64 < kCertMaxBlocks ? nb64 : kCertMaxBlocks);
-    const int64_t want = idx_cap < im.n_nodes ? idx_cap : im.n_nodes;   // a cycle has at most n + 1 = n_nodes arcs
-    hipStream_t s = h->stream;
-    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
-    hipLaunchKernelGGL(k_ray_nodes, dim3(nb), dim3(kCertThreads), 0, s, h->view, a, e, backward, h->d_ray_part);
-    hipLaunchKernelGGL(k_ray_final, dim3(1), dim3(kCertThreads), 0, s, h->d_ray_part, nb);
-    if (want > 0) hipLaunchKernelGGL(k_ray_write, dim3(nb), dim3(kCertThreads), 0, s, h->view, a, e, backward, h->d_ray_part + nb, h->d_ray_idx, want);
-    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
-    HIP_TRY(h, hipGetLastError());
-    McfRayAcc R;
-    HIP_TRY(h, hipMemcpyAsync(&R, h->d_ray_part + nb, sizeof R, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->ct_ev[0], h->ct_ev[1]));
-    mcf_ray r;
-    std::memset(&r, 0, sizeof r);
-    r.arc = im.orig[e];
-    r.entering_backward = backward;
-    r.length = R.tree_n + 1;
-    r.join = R.join_i == MCF_CERT_NONE ? -1 : R.join_i;
-    r.backward_count = R.back_n; r.capped_count = R.cap_n; r.artificial_count = R.art_n;
-    r.cost = R.cost; r.reduced_cost = R.rc;
-    r.theta = R.theta; r.theta_arc = R.theta_i == MCF_CERT_NONE ? -1 : R.theta_i;
-    r.proven = mcf_ray_proven(R, backward != 0) ? 1 : 0;
-    r.device_ms = ms;
-    const int64_t got = r.length < want ? r.length : want;
-    if (got > 0) HIP_TRY(h, hipMemcpy(idx_out, h->d_ray_idx, (size_t)got * 8, hipMemcpyDeviceToHost));
-    *out = r;
-    return MCF_OK;
-}
-
-int mcf_certify_cut(mcf_handle* h, const int8_t* in_S, int8_t* S_out, mcf_cut* out) {
-    if (!h || !out) return MCF_E_BAD_ARG;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = sync_ctx(h, h->stream);
-    if (rc) return rc;
-    const McfHostImage& im = h->im;
-    if ((rc = cert_prepare(h, in_S == nullptr)) != MCF_OK) return rc;   // device supplies, events; a full adjacency for the search only
-    if (!h->d_cut_mark) {
-        if (dalloc(&h->d_cut_mark, (size_t)im.n) != hipSuccess || dalloc(&h->d_cut_level, 1) != hipSuccess ||
-            dalloc(&h->d_cut_byte, (size_t)im.n) != hipSuccess || dalloc(&h->d_cut_part, 2 * kCertMaxBlocks + 1) != hipSuccess) {
-            (void)hipGetLastError(); cert_free(&h->d_cut_mark); cert_free(&h->d_cut_level); cert_free(&h->d_cut_byte); cert_free(&h->d_cut_part);
-            h->err = "hipMalloc cut scratch"; return MCF_E_ALLOC;
-        }
-    }
-    const bool own_adj = h->d_adj && !h->view.rc_partial;
-    const int64_t* adj_off = own_adj ? h->d_adj_off : h->d_ct_adj_off;
-    const int64_t* adj = own_adj ? h->d_adj : h->d_ct_adj;
-    int64_t nb64 = ((int64_t)im.n + kCertThreads - 1) / kCertThreads;
-    const int nb = (int)(nb64 < kCertMaxBlocks ? nb64 : kCertMaxBlocks);
-    const int ab = mcf_price_blocks(im.m, 1, 0);
-    hipStream_t s = h->stream;
-    int32_t level = 0;
-    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
-    if (in_S) {
-        HIP_TRY(h, hipMemcpyAsync(h->d_cut_byte, in_S, (size_t)im.n, hipMemcpyHostToDevice, s));   // (the call ends with a synchronisation)
-        hipLaunchKernelGGL(k_cut_widen, dim3(nb), dim3(kCertThreads), 0, s, h->d_cut_byte, im.n, h->d_cut_mark);
-    } else {
-        HIP_TRY(h, hipMemsetAsync(h->d_cut_level, 0, 4, s));
-        hipLaunchKernelGGL(k_cut_seed, dim3(nb), dim3(kCertThreads), 0, s, h->view, h->d_cut_mark, h->d_cut_level);
-        HIP_TRY(h, hipMemcpyAsync(&level, h->d_cut_level, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        // Round r expands level r and fills level r + 1; a level holds at least one new node, so there are at most n of them
-        // and round n finds nothing new: the loop ends at r > n whatever the device arrays hold.
-        int32_t r = 1;
-        while (level > 0 && r <= im.n) {
-            const int32_t stop = r + kCutBatch - 1 < im.n ? r + kCutBatch - 1 : im.n;
-            for (; r <= stop; ++r) hipLaunchKernelGGL(k_cut_round, dim3(nb), dim3(kCertThreads), 0, s, h->view, adj_off, adj, h->d_cut_mark, h->d_cut_level, r);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipMemcpyAsync(&level, h->d_cut_level, 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-            if (level < r) break;   // the last level was expanded (r is one past the rounds queued) and reached nothing new
-        }
-    }
-    const int32_t resident = in_S ? 0 : 1;
-    if (im.m >= kIncrementalMinArcs) hipLaunchKernelGGL(k_cut_arcs<true>, dim3(ab), dim3(kCertThreads), 0, s, h->view, h->d_cut_mark, resident, h->d_cut_part);
-    else hipLaunchKernelGGL(k_cut_arcs<false>, dim3(ab), dim3(kCertThreads), 0, s, h->view, h->d_cut_mark, resident, h->d_cut_part);
-    hipLaunchKernelGGL(k_cut_nodes, dim3(nb), dim3(kCertThreads), 0, s, h->view, h->d_cut_mark, h->d_ct_supply, resident, h->d_cut_part + ab);
-    hipLaunchKernelGGL(k_cut_final, dim3(1), dim3(kCertThreads), 0, s, h->d_cut_part, ab + nb);
-    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
-    HIP_TRY(h, hipGetLastError());
-    McfCutAcc C;
-    HIP_TRY(h, hipMemcpyAsync(&C, h->d_cut_part + ab + nb, sizeof C, hipMemcpyDeviceToHost, s));
-    if (S_out) {
-        hipLaunchKernelGGL(k_cut_narrow, dim3(nb), dim3(kCertThreads), 0, s, h->d_cut_mark, im.n, h->d_cut_byte);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(S_out, h->d_cut_byte, (size_t)im.n, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->ct_ev[0], h->ct_ev[1]));
-    mcf_cut c;
-    std::memset(&c, 0, sizeof c);
-    auto put = [](int64_t* hi_lo, __int128 x) { hi_lo[0] = (int64_t)(x >> 64); hi_lo[1] = (int64_t)(uint64_t)x; };
-    c.seeds = C.seeds; c.nodes_in_S = C.in_s; c.rounds = level; c.deficit_in_S = C.deficit;
-    c.leaving_arcs = C.leave_n; c.leaving_uncapacitated = C.leave_uncap; c.leaving_unsaturated = C.leave_unsat; c.entering_with_flow = C.enter_flow;
-    __int128 excess = 0;
-    c.proven = mcf_cut_proven(C, &excess) ? 1 : 0;
-    put(c.capacity, (__int128)(((mcf_u128)C.cap_hi << 64) | C.cap_lo));
-    put(c.supply, (__int128)(((mcf_u128)C.sup_hi << 64) | C.sup_lo));
-    put(c.excess, excess);
-    put(c.artificial_out, (__int128)(((mcf_u128)C.art_hi << 64) | C.art_lo));
-    c.device_ms = ms;
-    *out = c;
     return MCF_OK;
 }
 

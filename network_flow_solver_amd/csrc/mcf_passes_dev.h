@@ -1,0 +1,752 @@
+// mcf_passes_dev.h -- kernels of the post-solve passes on a resident handle (host drivers: mcf_passes_host.h).  Not a header
+// of its own: mcf_engine.hip includes it inside its anonymous namespace, after the pivot-path kernels.
+
+// ------------------------------------------------------------------ mcf_update_costs: re-price a resident basis
+// Flows, states and the tree do not depend on costs, so a cost change on a handle that holds a basis moves only the
+// potentials below a changed TREE arc and, after them, the reduced costs / key codes.  Four kinds of launches, none of
+// which depends on how many arcs changed or (beyond a logarithm) on the depth of the tree:
+//   k_uc_seed     one lane per node: jump record {val = 0 (root children on an artificial arc: +-(growth of big-M)),
+//                 anc = parent}, and the greatest depth of the tree (decides the number of jump rounds);
+//   k_uc_scatter  one lane per changed arc: store cost[e]; a basic arc adds +-delta to the record of the end point it is
+//                 the tree arc of (every node has its own tree arc: plain stores, nothing to resolve);
+//   k_uc_jump     pointer jumping, ceil(log2(max depth)) rounds over double buffers: val[v] += val[anc[v]],
+//                 anc[v] = anc[anc[v]] -- after the last round val[v] is the sum of the deltas on v's root path.  Reads
+//                 parent pointers only, so it serves the dense preorder array and the blocked preorder list alike;
+//                 the last round adds the sum to pi[v] itself;
+//   k_uc_rebuild  one streaming pass over all m_pad arcs in the shape of k_price's gather: rc = cost + pi[tail] - pi[head]
+//                 into rcache (and the key code into vkey), 16-byte accesses throughout.
+struct alignas(16) McfJump {
+    int64_t val;   // sum of the potential shifts of the tree arcs from this node up to (excluding) anc
+    int32_t anc;   // -1: the path has reached the root
+    int32_t pad;
+};
+
+constexpr int kUcThreads = 256;
+
+__global__ __launch_bounds__(kUcThreads) void k_uc_seed(const McfNode* __restrict__ node, int32_t n_nodes, int64_t m, int64_t d_bigm,
+                                                        McfJump* __restrict__ out, int32_t* __restrict__ info) {
+    __shared__ int32_t s_depth;
+    if (threadIdx.x == 0) s_depth = 0;
+    __syncthreads();
+    int32_t deepest = 0;
+    const int32_t stride = (int32_t)(gridDim.x * kUcThreads);
+    for (int32_t v = (int32_t)(blockIdx.x * kUcThreads + threadIdx.x); v < n_nodes; v += stride) {
+        const McfNode r = node[v];
+        McfJump j;
+        j.val = 0; j.anc = r.parent; j.pad = 0;
+        // an artificial arc costs big-M: a larger big-M is a cost change on the tree arc of every node that still hangs on one
+        if (r.pred >= 0 && (int64_t)(r.pred >> 1) >= m) j.val = (r.pred & 1) ? -d_bigm : d_bigm;
+        out[v] = j;
+        deepest = r.depth > deepest ? r.depth : deepest;
+    }
+    atomicMax(&s_depth, deepest);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_depth > 0) atomicMax(&info[0], s_depth);
+}
+
+__global__ __launch_bounds__(kUcThreads) void k_uc_scatter(int64_t count, const int32_t* __restrict__ arc, const int32_t* __restrict__ new_cost,
+                                                           int32_t* __restrict__ cost, const int8_t* __restrict__ state,
+                                                           const int32_t* __restrict__ tail, const int32_t* __restrict__ head,
+                                                           const McfNode* __restrict__ node, McfJump* __restrict__ jump, int32_t* __restrict__ info) {
+    const int64_t stride = (int64_t)gridDim.x * kUcThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kUcThreads + threadIdx.x; i < count; i += stride) {
+        const int32_t e = arc[i];
+        const int64_t delta = (int64_t)new_cost[i] - (int64_t)cost[e];
+        cost[e] = new_cost[i];
+        if (delta == 0 || state[e] != 0) continue;
+        // basic: the arc is the tree arc of exactly one of its end points; pi[x] = pi[parent] -+ cost (up / down)
+        const int32_t t = tail[e], hd = head[e];
+        const int32_t pt = node[t].pred, ph = node[hd].pred;
+        int32_t x = -1;
+        if (pt >= 0 && (pt >> 1) == e) x = t; else if (ph >= 0 && (ph >> 1) == e) x = hd;
+        if (x < 0) continue;
+        jump[x].val = x == t ? -delta : delta;
+        atomicAdd(&info[1], 1);
+    }
+}
+
+template <bool LAST>   // LAST: the sums are complete after this round and go straight into the potentials
+__global__ __launch_bounds__(kUcThreads) void k_uc_jump(const McfJump* __restrict__ in, McfJump* __restrict__ out, int64_t* __restrict__ pi, int32_t n_nodes) {
+    const int32_t stride = (int32_t)(gridDim.x * kUcThreads);
+    for (int32_t v = (int32_t)(blockIdx.x * kUcThreads + threadIdx.x); v < n_nodes; v += stride) {
+        McfJump a = in[v];
+        if (a.anc >= 0) {
+            const McfJump b = in[a.anc];
+            a.val += b.val;
+            a.anc = b.anc;
+        }
+        if (LAST) { if (a.val != 0) pi[v] += a.val; }
+        else out[v] = a;
+    }
+}
+
+// Bucket x's share of the 4-arc groups: a group that straddles a bucket boundary belongs to the lower bucket, the last
+// bucket takes the padding.  Workgroup b sweeps bucket b % 8 like k_price, so that the head gathers of an XCD's workgroups
+// stay inside one eighth of the potential array.
+__device__ __forceinline__ int64_t uc_group_lo(const McfView& v, int x, int64_t ngroups) {
+    if (x <= 0) return 0;
+    if (x >= MCF_NUM_BUCKETS) return ngroups;
+    return (v.bucket_off[x] + 3) >> 2;
+}
+
+constexpr int kUcUnroll = 2;   // 4-arc groups in flight per lane, as in k_price
+
+__global__ __launch_bounds__(kUcThreads) void k_uc_rebuild(McfView v, int64_t m_pad) {
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t ngroups = m_pad >> 2;
+    const int64_t g_lo = uc_group_lo(v, x, ngroups), g_hi = uc_group_lo(v, x + 1, ngroups);
+    const int4* __restrict__ tail4 = reinterpret_cast<const int4*>(v.tail);
+    const int4* __restrict__ head4 = reinterpret_cast<const int4*>(v.head);
+    const int4* __restrict__ cost4 = reinterpret_cast<const int4*>(v.cost);
+    const int32_t* __restrict__ state4 = reinterpret_cast<const int32_t*>(v.state);
+    const int64_t* __restrict__ pi = v.pi;
+    longlong2* __restrict__ rc2 = reinterpret_cast<longlong2*>(v.rcache);
+    int4* __restrict__ vk4 = reinterpret_cast<int4*>(v.vkey);
+    const int64_t bigm = v.vk_bigm;
+    const int32_t half = v.vk_half;
+    const int64_t stride = nlb * kUcThreads;
+    for (int64_t g0 = g_lo + lb * kUcThreads + threadIdx.x; g0 < g_hi; g0 += stride * kUcUnroll) {
+        int4 t[kUcUnroll], h[kUcUnroll], cc[kUcUnroll];
+        int32_t st[kUcUnroll];
+#pragma unroll
+        for (int u = 0; u < kUcUnroll; ++u) {
+            const int64_t g = g0 + u * stride;
+            const int64_t gs = g < g_hi ? g : g_lo;   // clamp: the loads stay unconditional and in range
+            t[u] = tail4[gs]; h[u] = head4[gs]; cc[u] = cost4[gs]; st[u] = state4[gs];
+        }
+        int64_t pt[kUcUnroll][4], ph[kUcUnroll][4];
+#pragma unroll
+        for (int u = 0; u < kUcUnroll; ++u) {
+            pt[u][0] = pi[t[u].x]; pt[u][1] = pi[t[u].y]; pt[u][2] = pi[t[u].z]; pt[u][3] = pi[t[u].w];
+            ph[u][0] = pi[h[u].x]; ph[u][1] = pi[h[u].y]; ph[u][2] = pi[h[u].z]; ph[u][3] = pi[h[u].w];
+        }
+#pragma unroll
+        for (int u = 0; u < kUcUnroll; ++u) {
+            const int64_t g = g0 + u * stride;
+            if (g >= g_hi) continue;
+            const int64_t r0 = (int64_t)cc[u].x + pt[u][0] - ph[u][0], r1 = (int64_t)cc[u].y + pt[u][1] - ph[u][1];
+            const int64_t r2 = (int64_t)cc[u].z + pt[u][2] - ph[u][2], r3 = (int64_t)cc[u].w + pt[u][3] - ph[u][3];
+            longlong2 a, b;
+            a.x = r0; a.y = r1; b.x = r2; b.y = r3;
+            rc2[2 * g] = a;
+            rc2[2 * g + 1] = b;
+            if (vk4) {
+                const int32_t s = st[u];
+                int4 k;
+                k.x = mcf_vkey(-(int64_t)(int8_t)s * r0, bigm, half);
+                k.y = mcf_vkey(-(int64_t)(int8_t)(s >> 8) * r1, bigm, half);
+                k.z = mcf_vkey(-(int64_t)(int8_t)(s >> 16) * r2, bigm, half);
+                k.w = mcf_vkey(-(int64_t)(int8_t)(s >> 24) * r3, bigm, half);
+                vk4[g] = k;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kUcThreads) void k_uc_ones(float4* __restrict__ w4, int64_t n4) {
+    const int64_t stride = (int64_t)gridDim.x * kUcThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kUcThreads + threadIdx.x; i < n4; i += stride) w4[i] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+}
+
+// ------------------------------------------------------------------ certificate (mcf_certify / mcf_bottlenecks)
+// k_cert_arcs    ONE streaming pass over the arcs in engine order, workgroup b on head bucket b % 8 like the pricing sweeps
+//                (the two potential gathers of an arc then stay inside one XCD's L2 share): tail, head, cost, orig (4 B
+//                each), the walk record (cap, flow: 16 B), and for the resident groups state (1 B), reduced cost (8 B) and
+//                key code (4 B) -- 32 B per arc for the primal / dual / objective groups, 45 B with everything.  Read once
+//                per call: non-temporal loads from kIncrementalMinArcs arcs on, as for the key-code sweep.
+// k_cert_child   size[v] added to csum[parent[v]] (integer atomics: the sum does not depend on their order).
+// k_cert_nodes   one lane per node: conservation as a gather over the node's adjacency list (128-bit balance), the dual
+//                objective's node term, the artificial arc, and the tree records (mcf_get_tree's view of them).
+// k_cert_final   one workgroup merges the per-workgroup partials.
+// Every partial combines by integer +, max or (max, lowest index) (mcf_core.h), so no merge order can change the result.
+constexpr int kCertThreads = 256;
+constexpr int kCertMaxBlocks = 2048;
+
+struct CertArgs {
+    const int64_t* cflow;     // caller's flows in the caller's order; nullptr = resident
+    const int64_t* pi;        // [n_nodes] potentials, root included (resident, or the caller's with root = 0)
+    const int64_t* supply;    // [n]
+    const int64_t* adj_off;   // full node -> arc adjacency (the handle's, or the certificate's own)
+    const int64_t* adj;
+    const int64_t* rcache;    // resident copies to compare, nullptr = none
+    const int32_t* vkey;
+    int32_t* csum;            // [n_nodes] scratch: sum of the children's sizes
+    uint32_t checks;
+    int32_t resident_flow;
+    int32_t cur, arena;       // which copies of the preorder arrays are current (mcf_get_tree)
+    int32_t partial;          // resident reduced costs / key codes are exact on this rank's shard only
+    int64_t shard, shards;
+    int64_t bigm;
+};
+
+template <bool NT, typename T>
+__device__ __forceinline__ T cert_ld(const T* p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+
+// ---- building blocks shared by the passes below (workgroups of kPassThreads = 4 waves)
+constexpr int kPassThreads = 256;
+constexpr int kPassWaves = kPassThreads / 64;
+static_assert(kCertThreads == kPassThreads, "block_reduce / wave_block_sum are written for 4 waves");
+
+// an accumulator of mcf_core.h (mcf_acc_init / mcf_acc_merge): the workgroup's partials into thread 0's acc
+template <typename Acc>
+__device__ __forceinline__ void block_reduce(Acc& acc, Acc* s_wave) {
+    for (int off = 32; off > 0; off >>= 1) {
+        Acc o;
+        unsigned long long* po = reinterpret_cast<unsigned long long*>(&o);
+        const unsigned long long* pa = reinterpret_cast<const unsigned long long*>(&acc);
+#pragma unroll
+        for (int k = 0; k < mcf_acc_words<Acc>(); ++k) po[k] = __shfl_down(pa[k], off, 64);
+        if ((int)(threadIdx.x & 63) + off < 64) mcf_acc_merge(&acc, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) s_wave[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < kPassWaves; ++w) mcf_acc_merge(&acc, s_wave[w]);
+}
+
+// part[0 .. n) -> part[n], by one workgroup
+template <typename Acc>
+__device__ __forceinline__ void merge_partials(Acc* __restrict__ part, int n, Acc* s_wave) {
+    Acc acc;
+    mcf_acc_init(&acc);
+    for (int i = threadIdx.x; i < n; i += kPassThreads) mcf_acc_merge(&acc, part[i]);
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[n] = acc;
+}
+template <typename Acc>
+__global__ __launch_bounds__(kPassThreads) void k_final(Acc* __restrict__ part, int n) {
+    __shared__ Acc s_wave[kPassWaves];
+    merge_partials(part, n, s_wave);
+}
+
+// integer sums: lane 0 of every wave gets its wave's (lanes past a shuffle's end add what their neighbours hold) ...
+__device__ __forceinline__ int32_t wave_sum(int32_t x) {
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    return x;
+}
+__device__ __forceinline__ mcf_u128 wave_sum(mcf_u128 x) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t lo = __shfl_down((unsigned long long)(uint64_t)x, off, 64), hi = __shfl_down((unsigned long long)(uint64_t)(x >> 64), off, 64);
+        x += ((mcf_u128)hi << 64) | lo;
+    }
+    return x;
+}
+// ... and thread 0 the workgroup's (s: one slot per wave)
+template <typename T>
+__device__ __forceinline__ T wave_block_sum(T x, T* s) {
+    x = wave_sum(x);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return s[0] + s[1] + s[2] + s[3];
+}
+
+// Exclusive scan of nb chunk totals by ONE workgroup of 1024 threads: out[b] = in[0] + .. + in[b - 1] (out may be in),
+// *total = the sum of all of them when asked for.  Thread t owns `per` consecutive chunks; thread 0 scans the 1024 sums.
+template <typename In, typename Out>
+__device__ __forceinline__ void scan_chunk_totals(const In* in, int64_t nb, Out* out, Out* total, Out* s) {
+    const int64_t per = (nb + 1023) / 1024, lo = threadIdx.x * per < nb ? threadIdx.x * per : nb, hi = lo + per < nb ? lo + per : nb;
+    Out sum = 0;
+    for (int64_t b = lo; b < hi; ++b) sum += in[b];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        Out run = 0;
+        for (int k = 0; k < 1024; ++k) { const Out x = s[k]; s[k] = run; run += x; }
+        if (total) *total = run;
+    }
+    __syncthreads();
+    Out run = s[threadIdx.x];
+    for (int64_t b = lo; b < hi; ++b) { const Out x = in[b]; out[b] = run; run += x; }
+}
+template <typename In, typename Out>
+__global__ __launch_bounds__(1024) void k_scan_chunks(const In* in, int64_t nb, Out* out, Out* total) {
+    __shared__ Out s[1024];
+    scan_chunk_totals(in, nb, out, total, s);
+}
+
+// Preorder position of `node` and the slot that holds it, in the view mcf_get_tree reports (cur: the copy that is current,
+// a flip the last update left pending already accounted for -- tree_sel); -1 when a record points outside its array.
+__device__ __forceinline__ int32_t tree_pos(const McfView& v, int32_t cur, int32_t node, int32_t* slot) {
+    if (MCF_HAS_BPL(v)) {
+        const int32_t s = v.posbuf[0][node] & MCF_LOC_SLOT;
+        const int32_t b = s >> v.blk_shift;
+        *slot = s;
+        if (b < 0 || b >= v.blk_cap) return -1;
+        const int32_t base = (cur ? v.bmeta[1] : v.bmeta[0])[b].base;
+        if (base == MCF_BLK_FREE) return -1;
+        const int32_t p = base + (s & ((1 << v.blk_shift) - 1));
+        return p < v.n_nodes ? p : -1;
+    }
+    const int32_t p = (cur ? v.posbuf[1] : v.posbuf[0])[node];
+    *slot = p;
+    return (p < 0 || p >= v.n_nodes) ? -1 : p;
+}
+
+// node u's artificial arc: does it point u -> root ("up")?  A non-basic one carries nothing and counts as up.
+__device__ __forceinline__ bool art_flow_up(const McfView& v, int32_t u) {
+    const int32_t pred = v.node[u].pred;
+    return (int64_t)(pred >> 1) == v.m + u ? (pred & 1) != 0 : true;
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kCertThreads) void k_cert_arcs(McfView v, CertArgs a, McfCertArcAcc* __restrict__ part) {
+    __shared__ McfCertArcAcc s_wave[kCertThreads / 64];
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+    int64_t own_lo = lo, own_hi = hi;
+    if (a.partial) mcf_bucket_slice(v.bucket_off, x, a.shard, a.shards, 0, 1, &own_lo, &own_hi);
+    const bool resident = (a.checks & (MCF_CERT_BASIS | MCF_CERT_PRICING)) != 0;
+    McfCertArcAcc acc;
+    mcf_acc_init(&acc);
+    for (int64_t e = lo + lb * kCertThreads + threadIdx.x; e < hi; e += nlb * kCertThreads) {
+        const int32_t t = cert_ld<NT>(v.tail + e), hd = cert_ld<NT>(v.head + e);
+        const int64_t cost = cert_ld<NT>(v.cost + e);
+        const int64_t o = cert_ld<NT>(v.orig + e);
+        const int64_t* aw = reinterpret_cast<const int64_t*>(v.arcw + e);
+        const int64_t cap = cert_ld<NT>(aw);
+        const int64_t flow = a.cflow ? a.cflow[o] : cert_ld<NT>(aw + 1);
+        const int64_t rc = cost + a.pi[t] - a.pi[hd];
+        mcf_cert_arc(&acc, a.checks, o, cost, cap, flow, rc);
+        if (resident) {
+            const int32_t st = cert_ld<NT>(v.state + e);
+            const bool own = e >= own_lo && e < own_hi;
+            int64_t rres = 0;
+            int32_t kres = 0;
+            if (a.rcache && own) rres = cert_ld<NT>(a.rcache + e);
+            if (a.vkey && own) kres = cert_ld<NT>(a.vkey + e);
+            mcf_cert_arc_resident(&acc, a.checks, cap, flow, rc, st, a.rcache && own ? &rres : nullptr, a.vkey && own ? &kres : nullptr,
+                                  v.vk_bigm, v.vk_half);
+        }
+    }
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_cert_child(McfView v, int32_t* __restrict__ csum) {
+    const int32_t N = v.n_nodes;
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N - 1; u += gridDim.x * kCertThreads) {
+        const McfNode nd = v.node[u];
+        if (nd.parent >= 0 && nd.parent < N) atomicAdd(&csum[nd.parent], nd.size);
+    }
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_cert_nodes(McfView v, CertArgs a, McfCertNodeAcc* __restrict__ part) {
+    __shared__ McfCertNodeAcc s_wave[kCertThreads / 64];
+    const int32_t N = v.n_nodes, root = N - 1;
+    const int64_t m = v.m;
+    const int32_t sel = MCF_HAS_BPL(v) ? a.arena : a.cur;
+    const int32_t* ord = sel ? v.order[1] : v.order[0];
+    const int32_t* psz = sel ? v.psz[1] : v.psz[0];
+    const int64_t pi_root = a.pi[root];
+    McfCertNodeAcc acc;
+    mcf_acc_init(&acc);
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
+        const McfNode nd = v.node[u];
+        if (u < root) {
+            const int64_t af = v.arcw[m + u].flow;
+            mcf_cert_add128(&acc.art_lo, &acc.art_hi, (mcf_u128)(__int128)af);
+            if (a.checks & MCF_CERT_CONSERVATION) {
+                // 128 bits: a node may have 2^30 arcs of up to 2^63 each
+                __int128 bal = a.supply[u];
+                for (int64_t k = a.adj_off[u]; k < a.adj_off[u + 1]; ++k) {
+                    const int64_t w = a.adj[k];
+                    const int64_t e = (w & 0xffffffff) >> 1;
+                    const int64_t f = a.cflow ? a.cflow[v.orig[e]] : v.arcw[e].flow;
+                    bal += (w & 1) ? -(__int128)f : (__int128)f;
+                }
+                if (a.resident_flow) {   // the node's artificial arc: node -> root when "up" (a non-basic one carries nothing)
+                    bal += art_flow_up(v, u) ? -(__int128)af : (__int128)af;
+                }
+                mcf_cert_node_balance(&acc, u, bal);
+            }
+            if (a.checks & MCF_CERT_OBJECTIVES)
+                mcf_cert_add128(&acc.dnode_lo, &acc.dnode_hi, (mcf_u128)(-(__int128)(a.pi[u] - pi_root) * a.supply[u]));
+        }
+        if (!(a.checks & MCF_CERT_BASIS)) continue;
+        bool bad = false;
+        int32_t slot = 0;
+        const int32_t pos = tree_pos(v, a.cur, u, &slot);
+        if (pos < 0) bad = true;
+        else {
+            if (ord[slot] != u) bad = true;
+            if (psz && psz[slot] != nd.size) bad = true;
+        }
+        if (nd.size != 1 + a.csum[u]) bad = true;
+        if (u == root) {
+            if (nd.parent != -1 || pos != 0 || nd.size != N || nd.depth != 0) bad = true;
+        } else if (nd.parent < 0 || nd.parent >= N || nd.pred < 0) {
+            bad = true;
+        } else {
+            const int32_t p = nd.parent;
+            const McfNode pn = v.node[p];
+            int32_t pslot = 0;
+            const int32_t ppos = tree_pos(v, a.cur, p, &pslot);
+            if (ppos < 0 || pos < 0 || !(ppos < pos && (int64_t)pos + nd.size <= (int64_t)ppos + pn.size)) bad = true;
+            if (nd.depth != pn.depth + 1) bad = true;
+            const int64_t arc = nd.pred >> 1;
+            const bool up = (nd.pred & 1) != 0;
+            if (arc < m) {
+                const int32_t t = v.tail[arc], hd = v.head[arc];
+                if (up ? (t != u || hd != p) : (hd != u || t != p)) bad = true;
+                if (v.state[arc] != 0) bad = true;
+                if ((int64_t)v.cost[arc] + a.pi[t] - a.pi[hd] != 0) ++acc.tree_rc_bad;
+                const McfArcW w = v.arcw[arc];
+                if ((up && w.cap < MCF_INF && w.flow == w.cap) || (!up && w.flow == 0)) ++acc.strong_bad;
+            } else {
+                if (arc != m + u || p != root) bad = true;
+                if (a.bigm + (up ? a.pi[u] - pi_root : pi_root - a.pi[u]) != 0) ++acc.tree_rc_bad;
+                if (!up && v.arcw[m + u].flow == 0) ++acc.strong_bad;
+                ++acc.art_basic;
+            }
+        }
+        if (bad) ++acc.shape_bad;
+    }
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// part[0 .. n) -> part[n] (arcs and nodes alike)
+__global__ __launch_bounds__(kCertThreads) void k_cert_final(McfCertArcAcc* __restrict__ ap, int na, McfCertNodeAcc* __restrict__ np, int nn) {
+    __shared__ McfCertArcAcc s_a[kPassWaves];
+    __shared__ McfCertNodeAcc s_n[kPassWaves];
+    merge_partials(ap, na, s_a);
+    merge_partials(np, nn, s_n);
+}
+
+// ---- bottleneck arcs, compacted in ascending caller's index: flag per caller's index (scatter from the engine-order
+// stream), count per chunk, exclusive scan of the chunk counts by one workgroup, write.
+constexpr int kBnChunk = 4096;   // caller's indices per workgroup: 16 rounds of 256
+__global__ __launch_bounds__(kCertThreads) void k_bn_flag(McfView v, const int64_t* __restrict__ cflow, int64_t num, int64_t den,
+                                                          uint8_t* __restrict__ flag) {
+    for (int64_t e = (int64_t)blockIdx.x * kCertThreads + threadIdx.x; e < v.m; e += (int64_t)gridDim.x * kCertThreads) {
+        const McfArcW w = v.arcw[e];
+        const int32_t o = v.orig[e];
+        flag[o] = mcf_cert_bottleneck(w.cap, cflow ? cflow[o] : w.flow, num, den) ? 1 : 0;
+    }
+}
+__global__ __launch_bounds__(kCertThreads) void k_bn_count(const uint8_t* __restrict__ flag, int64_t m, int32_t* __restrict__ cnt) {
+    __shared__ int32_t s[kCertThreads / 64];
+    const int64_t base = (int64_t)blockIdx.x * kBnChunk;
+    int32_t c = 0;
+    for (int r = 0; r < kBnChunk / kCertThreads; ++r) {
+        const int64_t i = base + r * kCertThreads + threadIdx.x;
+        if (i < m && flag[i]) ++c;
+    }
+    c = wave_block_sum(c, s);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = c;
+}
+__global__ __launch_bounds__(kCertThreads) void k_bn_write(const uint8_t* __restrict__ flag, int64_t m, const int64_t* __restrict__ off,
+                                                           int64_t* __restrict__ idx, int64_t idx_cap) {
+    __shared__ int32_t s[kCertThreads / 64];
+    const int64_t base = (int64_t)blockIdx.x * kBnChunk;
+    int64_t run = off[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = 0; r < kBnChunk / kCertThreads; ++r) {
+        const int64_t i = base + r * kCertThreads + threadIdx.x;
+        const bool f = i < m && flag[i];
+        const uint64_t mask = __ballot(f);
+        if (lane == 0) s[wave] = __popcll(mask);
+        __syncthreads();
+        int64_t before = run;
+        for (int w = 0; w < wave; ++w) before += s[w];
+        const int64_t at = before + __popcll(mask & (((uint64_t)1 << lane) - 1));
+        if (f && at < idx_cap) idx[at] = i;
+        run += s[0] + s[1] + s[2] + s[3];
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------ witnesses (mcf_certify_ray / mcf_certify_cut)
+// k_ray_nodes   one lane per node record (16 B) + its preorder position (4 B dense; 4 + 8 B blocked: slot, block base): the
+//               interval test against the two end points says whether the node's tree arc is on the cycle and on which
+//               side; only the <= length lanes that are read the arc's walk record (16 B), cost and caller's index.
+// k_final       one workgroup merges the per-workgroup partials (ray and cut alike).
+// k_ray_write   the same pass once more, now that the length is known: a node of the arriving side lands at
+//               1 + depth[first] - depth[u], one of the leaving side at length - 1 - (depth[second] - depth[u]).  8 B per cycle arc out.
+// k_cut_seed    one lane per node: node record + artificial walk record in, a 4 B level mark out (1 = seed, 0 = not reached).
+// k_cut_round   round r: one lane per node reads its mark (4 B); the lanes at level r walk their adjacency list (8 B per entry +
+//               the arc's 16 B walk record + the other end's mark) and mark what the residual arcs reach with r + 1.  Every list
+//               is expanded in exactly one round; all lanes that reach a node in a round store the same value.
+// k_cut_arcs    the streaming pass of k_cert_arcs: tail, head (4 B each), the walk record (16 B), two gathered marks.
+// k_cut_nodes   one lane per node: mark, supply (8 B), node record and artificial walk record of the nodes of S.
+constexpr int kCutBatch = 32;   // rounds queued between two looks at the level word
+
+__global__ __launch_bounds__(kCertThreads) void k_ray_nodes(McfView v, CertArgs a, int64_t e, int32_t backward, McfRayAcc* __restrict__ part) {
+    __shared__ McfRayAcc s_wave[kCertThreads / 64];
+    const int32_t N = v.n_nodes;
+    const int64_t m = v.m;
+    const int32_t t = v.tail[e], hd = v.head[e];
+    const int32_t first = backward ? t : hd, second = backward ? hd : t;
+    int32_t slot = 0;
+    const int32_t pf = tree_pos(v, a.cur, first, &slot), ps = tree_pos(v, a.cur, second, &slot);
+    McfRayAcc acc;
+    mcf_acc_init(&acc);
+    if (pf >= 0 && ps >= 0) {
+        for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
+            const McfNode nd = v.node[u];
+            const int32_t pu = tree_pos(v, a.cur, u, &slot);
+            if (pu < 0) continue;
+            const int side = mcf_ray_side(pu, nd.size, pf, ps);
+            if (side == 3) mcf_cert_worst(&acc.join_d, &acc.join_i, (int64_t)nd.depth + 1, u);
+            else if (side && nd.pred >= 0) {
+                const int64_t arc = nd.pred >> 1;
+                const bool up = (nd.pred & 1) != 0;
+                const bool forward = side == 1 ? up : !up;
+                if (arc < m) {
+                    const McfArcW w = v.arcw[arc];
+                    mcf_ray_arc(&acc, v.orig[arc], true, false, forward, v.cost[arc], w.cap, w.flow);
+                } else if (arc < m + N - 1) {
+                    mcf_ray_arc(&acc, arc, true, true, forward, a.bigm, MCF_INF, v.arcw[arc].flow);
+                }
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const McfArcW w = v.arcw[e];
+        const int64_t cost = v.cost[e];
+        mcf_ray_arc(&acc, v.orig[e], false, false, !backward, cost, w.cap, w.flow);
+        const int64_t rc = cost + a.pi[t] - a.pi[hd];
+        acc.rc = backward ? -rc : rc;
+    }
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_ray_write(McfView v, CertArgs a, int64_t e, int32_t backward, const McfRayAcc* __restrict__ total,
+                                                            int64_t* __restrict__ idx, int64_t idx_cap) {
+    const int32_t N = v.n_nodes;
+    const int64_t m = v.m;
+    const int32_t t = v.tail[e], hd = v.head[e];
+    const int32_t first = backward ? t : hd, second = backward ? hd : t;
+    int32_t slot = 0;
+    const int32_t pf = tree_pos(v, a.cur, first, &slot), ps = tree_pos(v, a.cur, second, &slot);
+    const int64_t length = total->tree_n + 1;
+    const int64_t df = v.node[first].depth, ds = v.node[second].depth;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && idx_cap > 0) idx[0] = v.orig[e];
+    if (pf < 0 || ps < 0) return;
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < N; u += gridDim.x * kCertThreads) {
+        const McfNode nd = v.node[u];
+        const int32_t pu = tree_pos(v, a.cur, u, &slot);
+        if (pu < 0 || nd.pred < 0) continue;
+        const int side = mcf_ray_side(pu, nd.size, pf, ps);
+        if (side != 1 && side != 2) continue;
+        const int64_t arc = nd.pred >> 1;
+        const int64_t at = side == 1 ? 1 + df - nd.depth : length - 1 - (ds - nd.depth);
+        if (at >= 1 && at < idx_cap && at < length) idx[at] = arc < m ? (int64_t)v.orig[arc] : arc;
+    }
+}
+
+// the flow of node u's artificial arc, > 0 towards the root, < 0 from it (a non-basic one carries nothing and counts as "up")
+__device__ __forceinline__ int64_t cut_art(const McfView& v, int32_t u) {
+    const int64_t af = v.arcw[v.m + u].flow;
+    return art_flow_up(v, u) ? af : -af;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_cut_seed(McfView v, int32_t* __restrict__ mark, int32_t* __restrict__ level) {
+    const int32_t n = v.n_nodes - 1;
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) {
+        const bool seed = cut_art(v, u) > 0;
+        mark[u] = seed ? 1 : 0;
+        if (seed) *level = 1;
+    }
+}
+
+// mark[] is read while other lanes store r + 1 into entries that hold 0: a lane sees 0 or r + 1 there, and either is right
+__global__ __launch_bounds__(kCertThreads) void k_cut_round(McfView v, const int64_t* __restrict__ adj_off, const int64_t* __restrict__ adj,
+                                                            int32_t* mark, int32_t* __restrict__ level, int32_t r) {
+    const int32_t n = v.n_nodes - 1;
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) {
+        if (mark[u] != r) continue;
+        for (int64_t k = adj_off[u]; k < adj_off[u + 1]; ++k) {
+            const int64_t w = adj[k];
+            const int32_t other = (int32_t)(w >> 32);
+            if (other < 0 || other >= n || mark[other] != 0) continue;
+            const McfArcW aw = v.arcw[(w & 0xffffffff) >> 1];
+            if (mcf_cut_extends((w & 1) != 0, aw.cap, aw.flow)) { mark[other] = r + 1; *level = r + 1; }
+        }
+    }
+}
+
+// the caller's set, one byte per node, into level marks (1 / 0) -- and the marks back into bytes for S_out
+__global__ __launch_bounds__(kCertThreads) void k_cut_widen(const int8_t* __restrict__ in, int32_t n, int32_t* __restrict__ mark) {
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) mark[u] = in[u] != 0 ? 1 : 0;
+}
+__global__ __launch_bounds__(kCertThreads) void k_cut_narrow(const int32_t* __restrict__ mark, int32_t n, int8_t* __restrict__ out) {
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads) out[u] = mark[u] != 0 ? 1 : 0;
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kCertThreads) void k_cut_arcs(McfView v, const int32_t* __restrict__ mark, int32_t resident, McfCutAcc* __restrict__ part) {
+    __shared__ McfCutAcc s_wave[kCertThreads / 64];
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+    McfCutAcc acc;
+    mcf_acc_init(&acc);
+    for (int64_t e = lo + lb * kCertThreads + threadIdx.x; e < hi; e += nlb * kCertThreads) {
+        const int32_t t = cert_ld<NT>(v.tail + e), hd = cert_ld<NT>(v.head + e);
+        const bool tin = mark[t] != 0, hin = mark[hd] != 0;
+        if (tin == hin) continue;
+        const int64_t* aw = reinterpret_cast<const int64_t*>(v.arcw + e);
+        mcf_cut_arc(&acc, tin, hin, cert_ld<NT>(aw), cert_ld<NT>(aw + 1), resident != 0);
+    }
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(kCertThreads) void k_cut_nodes(McfView v, const int32_t* __restrict__ mark, const int64_t* __restrict__ supply, int32_t resident,
+                                                            McfCutAcc* __restrict__ part) {
+    __shared__ McfCutAcc s_wave[kCertThreads / 64];
+    const int32_t n = v.n_nodes - 1;
+    McfCutAcc acc;
+    mcf_acc_init(&acc);
+    for (int32_t u = blockIdx.x * kCertThreads + threadIdx.x; u < n; u += gridDim.x * kCertThreads)
+        if (mark[u] != 0) mcf_cut_node(&acc, supply[u], resident ? cut_art(v, u) : 0);
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// ------------------------------------------------------------------ mcf_update_rhs: new supplies / capacities under a resident basis
+// Flows and states of non-basic arcs do not depend on supplies; tree flows are subtree sums of node balances, and a
+// subtree is a contiguous range of the preorder.  Bytes each pass moves (n nodes, m arcs, k changes):
+//   k_rhs_scatter  one lane per change: 12 B in; a capacity change reads and writes the arc's 16 B walk record (+ 1 B state,
+//                  and 8 B reduced cost -> 4 B key code when a non-basic arc at capacity falls back to its lower bound);
+//                  a supply change is one 8 B store.
+//   k_rhs_balance  one lane per node: supply (8 B), position (4 B dense; 4 + 8 B blocked: slot, block base), and per
+//                  adjacency entry (2 m of them) 8 B entry + 1 B state + 16 B walk record of the NON-BASIC arcs only;
+//                  16 B out (the 128-bit balance, at the node's preorder position).
+//   k_rhs_scan_*   inclusive prefix sum over the n + 1 positions in three launches (chunk totals, scan of the totals by one
+//                  workgroup, scan of every chunk): 16 B per position read twice and written once.
+//   k_rhs_flows    one lane per node: node record (16 B), position, two 16 B prefix sums, the tree arc's walk record read
+//                  and its flow written (16 + 8 B); an artificial arc that turns round rewrites 4 B of the node record and
+//                  seeds 16 B of a jump record.  Census by wave reduction, one atomic per wave and counter.
+// All sums are 128-bit: 2^30 arcs at capacities below 2^60 stay below 2^91, so no prefix can wrap.
+constexpr int kRhsThreads = kPassThreads;
+constexpr int kRhsPer = 8;                             // positions per lane in the scan
+constexpr int kRhsChunk = kRhsThreads * kRhsPer;       // positions per workgroup
+enum { RHS_VIOL = 0, RHS_WRONG = 1, RHS_FLIPS = 2, RHS_MOVED = 3, RHS_COUNTERS = 4 };
+
+__device__ __forceinline__ void rhs_count(unsigned long long* info, int which, int32_t mine) {
+    mine = wave_sum(mine);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&info[which], (unsigned long long)mine);
+}
+
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_scatter(McfView v, int64_t n_sup, const int32_t* __restrict__ snode, const int64_t* __restrict__ sval,
+                                                             int64_t* __restrict__ supply, int64_t n_cap, const int32_t* __restrict__ carc,
+                                                             const int64_t* __restrict__ cval, unsigned long long* __restrict__ info) {
+    const int64_t total = n_sup > n_cap ? n_sup : n_cap;
+    const int64_t stride = (int64_t)gridDim.x * kRhsThreads;
+    int32_t moved = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kRhsThreads + threadIdx.x; i < total; i += stride) {
+        if (i < n_sup) supply[snode[i]] = sval[i];
+        if (i >= n_cap) continue;
+        const int32_t e = carc[i];
+        const int64_t nc = cval[i];
+        McfArcW w = v.arcw[e];
+        if (w.cap == nc) continue;
+        w.cap = nc;
+        if (v.state[e] == -1) {   // non-basic at capacity: the flow follows the capacity
+            ++moved;
+            if (nc >= MCF_INF || nc == 0) {   // no capacity to sit at: back to the lower bound (mcf_apply_basis' state rule)
+                v.state[e] = 1;
+                w.flow = 0;
+                if (v.vkey) v.vkey[e] = mcf_vkey(-v.rcache[e], v.vk_bigm, v.vk_half);
+            } else {
+                w.flow = nc;
+            }
+        }
+        v.arcw[e] = w;
+    }
+    rhs_count(info, RHS_MOVED, moved);
+}
+
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_balance(McfView v, int32_t cur, const int64_t* __restrict__ supply, const int64_t* __restrict__ adj_off,
+                                                             const int64_t* __restrict__ adj, mcf_u128* __restrict__ bal) {
+    const int32_t n = v.n_nodes - 1;
+    for (int32_t u = blockIdx.x * kRhsThreads + threadIdx.x; u < n; u += gridDim.x * kRhsThreads) {
+        int32_t slot = 0;
+        const int32_t p = tree_pos(v, cur, u, &slot);
+        if (p < 0) continue;   // (a broken record: the flow pass counts it as a violation)
+        __int128 b = supply[u];
+        const int64_t lo = adj_off[u], hi = adj_off[u + 1];
+        for (int64_t k = lo; k < hi; ++k) {
+            const int64_t w = adj[k];
+            const int64_t e = (w & 0xffffffff) >> 1;
+            if (v.state[e] == 0) continue;   // basic arcs get their flow from the subtree sums
+            const int64_t f = v.arcw[e].flow;
+            b += (w & 1) ? -(__int128)f : (__int128)f;
+        }
+        bal[p] = (mcf_u128)b;
+    }
+}
+
+// thread t of a workgroup owns positions [chunk base + t * kRhsPer, + kRhsPer): 128 contiguous bytes, 16-byte accesses
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_scan_totals(const mcf_u128* __restrict__ bal, int32_t count, mcf_u128* __restrict__ part) {
+    __shared__ mcf_u128 s[kRhsThreads / 64];
+    const int64_t base = (int64_t)blockIdx.x * kRhsChunk + (int64_t)threadIdx.x * kRhsPer;
+    mcf_u128 sum = 0;
+#pragma unroll
+    for (int k = 0; k < kRhsPer; ++k) if (base + k < count) sum += bal[base + k];
+    sum = wave_block_sum(sum, s);
+    if (threadIdx.x == 0) part[blockIdx.x] = sum;
+}
+
+// bal[p] <- sum of bal[0 .. p] (inclusive, in place)
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_scan_apply(mcf_u128* __restrict__ bal, int32_t count, const mcf_u128* __restrict__ part) {
+    __shared__ mcf_u128 s[kRhsThreads];
+    const int64_t base = (int64_t)blockIdx.x * kRhsChunk + (int64_t)threadIdx.x * kRhsPer;
+    mcf_u128 x[kRhsPer];
+    mcf_u128 sum = 0;
+#pragma unroll
+    for (int k = 0; k < kRhsPer; ++k) { x[k] = base + k < count ? bal[base + k] : (mcf_u128)0; sum += x[k]; x[k] = sum; }
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int off = 1; off < kRhsThreads; off <<= 1) {   // Hillis-Steele over the lanes' totals
+        const mcf_u128 add = (int)threadIdx.x >= off ? s[threadIdx.x - off] : (mcf_u128)0;
+        __syncthreads();
+        s[threadIdx.x] += add;
+        __syncthreads();
+    }
+    const mcf_u128 before = part[blockIdx.x] + (threadIdx.x > 0 ? s[threadIdx.x - 1] : (mcf_u128)0);
+#pragma unroll
+    for (int k = 0; k < kRhsPer; ++k) if (base + k < count) bal[base + k] = x[k] + before;
+}
+
+__global__ __launch_bounds__(kRhsThreads) void k_rhs_flows(McfView v, int32_t cur, const mcf_u128* __restrict__ pre, int64_t bigm, McfJump* __restrict__ jump,
+                                                           unsigned long long* __restrict__ info) {
+    const int32_t N = v.n_nodes, n = N - 1;
+    const int64_t m = v.m;
+    int32_t viol = 0, wrong = 0, flips = 0;
+    for (int32_t u = blockIdx.x * kRhsThreads + threadIdx.x; u < n; u += gridDim.x * kRhsThreads) {
+        const McfNode nd = v.node[u];
+        int32_t slot = 0;
+        const int32_t p = tree_pos(v, cur, u, &slot);
+        if (p < 1 || nd.size < 1 || (int64_t)p + nd.size > N || nd.pred < 0) { ++viol; continue; }
+        const __int128 x = (__int128)(pre[p + nd.size - 1] - pre[p - 1]);   // surplus the subtree of u sends up
+        const int64_t a = nd.pred >> 1;
+        const bool up = (nd.pred & 1) != 0;
+        if (a < m) {
+            const __int128 f = up ? x : -x;
+            const int64_t cap = v.arcw[a].cap;
+            if (f < 0 || f > cap || f >= MCF_INF) { ++viol; continue; }
+            v.arcw[a].flow = (int64_t)f;
+            if ((up && cap < MCF_INF && f == cap) || (!up && f == 0)) ++wrong;
+        } else {
+            const __int128 ax = x < 0 ? -x : x;
+            if (ax >= MCF_INF) { ++viol; continue; }
+            v.arcw[a].flow = (int64_t)ax;
+            const bool nup = x >= 0;
+            if (nup != up) {   // the arc turns round: pi[u] = pi[root] -+ big-M, and with it every potential below
+                ++flips;
+                v.node[u].pred = (int32_t)((a << 1) | (nup ? 1 : 0));
+                jump[u].val = nup ? -2 * bigm : 2 * bigm;
+            }
+        }
+    }
+    rhs_count(info, RHS_VIOL, viol);
+    rhs_count(info, RHS_WRONG, wrong);
+    rhs_count(info, RHS_FLIPS, flips);
+}

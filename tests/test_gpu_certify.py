@@ -448,6 +448,23 @@ def test_bottlenecks_equal_exact_integers(gpu_engine_module, kw):
                 eng.bottlenecks(1, 0)
 
 
+def test_bottlenecks_scan_more_than_1024_chunks(gpu_engine_module):
+    """The scan of the chunk counts is one workgroup of 1 024 threads; from 1 024 * 4 096 + 4 097 arcs on there are more
+    than 1 024 chunks of 4 096 indices and a thread scans more than one of them (`per > 1` in scan_chunk_totals)."""
+    e = gpu_engine_module
+    n, m = 64, 1024 * 4096 + 4097
+    i = np.arange(m, dtype=np.int64)
+    tail, head = (i % n).astype(np.int32), ((i + 1) % n).astype(np.int32)
+    hit = i % 1000 == 7
+    flow = np.where(hit, 10, 0).astype(np.int64)
+    want = np.flatnonzero(hit)
+    with e.McfEngine(n, tail, head, np.ones(m, dtype=np.int64), np.full(m, 10, dtype=np.int64), np.zeros(n, dtype=np.int64)) as eng:
+        idx, count = eng.bottlenecks(1, 1, flow=flow, limit=m)
+        assert count == want.size and np.array_equal(idx, want)
+        few, count = eng.bottlenecks(1, 1, flow=flow, limit=10)
+        assert count == want.size and np.array_equal(few, want[:10])
+
+
 # ------------------------------------------------------------------ 8. scale
 def test_a_quarter_million_nodes_certified_on_the_device(gpu_engine_module, capsys):
     """262 144 nodes / 2 M arcs on the auto-selected blocked list (the size of the update-costs scale test): the device
