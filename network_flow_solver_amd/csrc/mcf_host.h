@@ -101,7 +101,10 @@ inline std::string mcf_apply_basis(McfHostImage& im, const int8_t* in_tree, cons
     }
     if (nbasic == 0) return "empty basis";
     // --- non-basic flows and node balances
-    std::vector<int64_t> flow(m, 0), bal(N, 0);
+    // (balances and subtree surpluses are 128-bit, as in mcf_repair_basis: non-basic arcs at capacities near 2^60 add up
+    // past 64 bits, and a surplus that wrapped would pass the bounds check below)
+    std::vector<int64_t> flow(m, 0);
+    std::vector<__int128> bal(N, 0);
     for (int32_t v = 0; v < n; ++v) bal[v] = im.supply[v];
     for (int64_t e = 0; e < m; ++e) {
         if (basic[e] || !at_upper || !at_upper[im.orig[e]]) continue;
@@ -159,19 +162,21 @@ inline std::string mcf_apply_basis(McfHostImage& im, const int8_t* in_tree, cons
     std::vector<int64_t> art_flow(n, 0);
     std::vector<int8_t> art_up(n, 1);
     auto flows_ok = [&]() -> bool {
-        std::vector<int64_t> b2(bal);
+        std::vector<__int128> b2(bal);
         for (int32_t k = N - 1; k >= 1; --k) {
             const int32_t v = order[k];
             const int64_t a = parc[v];
-            const int64_t x = b2[v];  // surplus the subtree of v has to send up (negative: must receive)
+            const __int128 x = b2[v];  // surplus the subtree of v has to send up (negative: must receive)
             if (a >= m) {
+                const __int128 ax = x >= 0 ? x : -x;
+                if (ax >= (__int128)MCF_INF) return false;   // outside the engine's numeric domain ("Numeric domain", include/mcf.h)
                 art_up[v] = x >= 0 ? 1 : 0;
-                art_flow[v] = x >= 0 ? x : -x;
+                art_flow[v] = (int64_t)ax;
             } else {
                 const bool up = im.tail[a] == v;
-                const int64_t f = up ? x : -x;
-                if (f < 0 || f > im.arcw[a].cap) return false;
-                flow[a] = f;
+                const __int128 f = up ? x : -x;
+                if (f < 0 || f > im.arcw[a].cap || f >= (__int128)MCF_INF) return false;
+                flow[a] = (int64_t)f;
             }
             b2[parent[v]] += x;
         }
@@ -245,7 +250,7 @@ inline std::string mcf_apply_basis(McfHostImage& im, const int8_t* in_tree, cons
     if (changed) {
         build_adj(adj);
         // the dropped arcs' flows were tree flows so far: move them into the node balances
-        std::vector<int64_t> b3(N, 0);
+        std::vector<__int128> b3(N, 0);
         for (int32_t v = 0; v < n; ++v) b3[v] = im.supply[v];
         for (int64_t e = 0; e < m; ++e) if (!basic[e] && flow[e] != 0) { b3[im.tail[e]] -= flow[e]; b3[im.head[e]] += flow[e]; }
         bal.swap(b3);

@@ -1,4 +1,4 @@
-// mcf_repair_host.cpp -- mcf_repair_basis (mcf_host.h) behind a plain C function, test infrastructure only.
+// mcf_repair_host.cpp -- mcf_repair_basis and mcf_apply_basis (mcf_host.h) behind plain C functions, test infrastructure only.
 //
 // mcf_update_rhs repairs a basis on the host when the device census finds tree flows outside their bounds (path 1).  That
 // repair is host code and needs no device: this file lets the CPU test-suite run it on arbitrary forests and hold the
@@ -44,6 +44,27 @@ int mcf_repair_host(int32_t n, int64_t m, const int32_t* tail, const int32_t* he
     if (art_flow) for (int32_t v = 0; v < n; ++v) art_flow[v] = im.arcw[(size_t)(m + v)].flow;
     if (report) { report[0] = rr.violations; report[1] = rr.wrong_way; report[2] = rr.arcs_cut; report[3] = rr.rounds; }
     return 0;
+}
+
+// mcf_apply_basis (what mcf_set_basis runs on the host) on the caller's instance and basis.  Outputs (any may be null):
+// state[m] and flow[m] in the caller's arc order, art_flow[n].  Returns 0 when the basis was installed; 1 when it was refused
+// (text in err): the outputs then show the cold start mcf_set_basis falls back to; -1 on bad arguments.
+int mcf_apply_host(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, const int64_t* cost, const int64_t* cap,
+                   const int64_t* supply, const int8_t* in_tree, const int8_t* at_upper, int8_t* state, int64_t* flow,
+                   int64_t* art_flow, char* err, int32_t err_len) {
+    auto say = [&](const std::string& s) { if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", s.c_str()); };
+    McfHostImage im;
+    int code = 0;
+    const std::string bad = mcf_build_image(n, m, tail, head, cost, cap, supply, im, &code);
+    if (!bad.empty()) { say(bad); return -1; }
+    const std::string msg = mcf_apply_basis(im, in_tree, at_upper);
+    if (!msg.empty()) { mcf_init_cold_basis(im); say(msg); }
+    for (int64_t e = 0; e < m; ++e) {
+        if (state) state[im.orig[(size_t)e]] = im.state[(size_t)e];
+        if (flow) flow[im.orig[(size_t)e]] = im.arcw[(size_t)e].flow;
+    }
+    if (art_flow) for (int32_t v = 0; v < n; ++v) art_flow[v] = im.arcw[(size_t)(m + v)].flow;
+    return msg.empty() ? 0 : 1;
 }
 
 }  // extern "C"

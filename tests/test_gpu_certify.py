@@ -1,7 +1,7 @@
 """mcf_certify / mcf_bottlenecks on the device, against numpy and Python-int yardsticks computed from downloaded arrays.
 
 What is compared: every count, every worst value and its index (ties: lowest index), the 128-bit objectives, the
-verdict.  Yardsticks: ``_np_cert`` below (numpy on int64 where the values fit, Python ints for the sums),
+verdict.  Yardsticks: ``planted_trees.np_cert`` (numpy on int64 where the values fit, Python ints for the sums),
 ``wide_range_instances.exact_certificate`` and ``conftest.check_optimality``.  Nothing here has a tolerance: the call is
 exact integer arithmetic.
 """
@@ -17,6 +17,7 @@ import verdict_instances as vi
 import wide_range_instances as wri
 from conftest import check_optimality, check_tree_invariants
 from network_flow_solver_amd import generators
+from planted_trees import first_worst as _first_worst, np_cert as _np_cert   # (shared with test_gpu_passes_geometry.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -44,46 +45,6 @@ BASIS_COUNTS = ("basic_count_mismatch", "tree_rc_count", "state_flow_count", "tr
 
 def _engine(e, inst, rule, **kw):
     return e.McfEngine(inst.n, inst.tail, inst.head, inst.cost, inst.cap, inst.supply, rule=rule, **kw)
-
-
-def _first_worst(mask, mag):
-    """(count, worst magnitude, lowest index attaining it) of the entries of `mag` selected by `mask`."""
-    if not mask.any():
-        return 0, 0, -1
-    w = int(mag[mask].max())
-    return int(mask.sum()), w, int(np.flatnonzero(mask & (mag == w))[0])
-
-
-def _np_cert(inst, cost, flow, pi):
-    """The primal / dual groups and the objectives of mcf_certify for caller's arrays (no artificial arcs)."""
-    flow = np.asarray(flow, np.int64)
-    pi = np.asarray(pi, np.int64)
-    cost = np.asarray(cost, np.int64)
-    capped = (inst.cap >= 0) & (inst.cap < MCF_INF)
-    neg = flow < 0
-    over = capped & (flow > inst.cap) & ~neg
-    _, bw, bi = _first_worst(neg | over, np.where(neg, -flow, flow - np.where(capped, inst.cap, 0)))
-    bal = [int(s) for s in inst.supply.tolist()]
-    for t, h, f in zip(inst.tail.tolist(), inst.head.tolist(), flow.tolist()):
-        bal[t] -= f
-        bal[h] += f
-    absbal = [abs(b) for b in bal]
-    iw = max(absbal) if absbal else 0
-    rc = cost + pi[inst.tail] - pi[inst.head]
-    lo = (rc < 0) & (~capped | (flow < inst.cap))
-    up = (rc > 0) & (flow > 0)
-    ln, lw, li = _first_worst(lo, -rc)
-    un, uw, ui = _first_worst(up, rc)
-    primal = sum(int(f) * int(c) for f, c in zip(flow.tolist(), cost.tolist()))
-    dual = -sum(int(p) * int(s) for p, s in zip(pi.tolist(), inst.supply.tolist()))
-    dual += sum(int(r) * int(c) for r, c, k in zip(rc.tolist(), inst.cap.tolist(), (capped & (rc < 0)).tolist()) if k)
-    return {"negative_flow_count": int(neg.sum()), "over_capacity_count": int(over.sum()), "bounds_worst": bw, "bounds_worst_arc": bi,
-            "imbalance_count": sum(1 for b in bal if b), "imbalance_worst": min(iw, (1 << 63) - 1),
-            "imbalance_worst_node": absbal.index(iw) if iw else -1,
-            "dual_lower_count": ln, "dual_lower_worst": lw, "dual_lower_arc": li,
-            "dual_upper_count": un, "dual_upper_worst": uw, "dual_upper_arc": ui,
-            "primal": primal, "dual": dual, "gap": primal - dual,
-            "saturated_arcs": int((capped & (flow == inst.cap) & (flow > 0)).sum())}
 
 
 def _assert_matches(cert, want):
