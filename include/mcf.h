@@ -24,6 +24,8 @@
  *   solving again after supplies / demands / capacities changed: the reference builds a new NetworkSimplex from the edited
  *       problem and passes solve(warm_start_basis=...), which recomputes the tree flows and falls back to the cold start
  *       when one of them leaves its bounds  simplex.py:99-265, 905-1010, 1491-1532 ...  mcf_update_rhs (the resident basis stays or is repaired)
+ *   adding arcs to a solved problem (examples/incremental_resolving_example.py:222-266, scenario 4): the reference builds a new
+ *       NetworkSimplex from the extended problem and warm-starts it  simplex.py:99-265, 1491-1532 ...  mcf_add_arcs (the resident basis stays)
  *   validate_flow / compute_bottleneck_arcs  utils.py:169-312 (conservation, bounds, arcs
  *       near capacity of a solution; the reference checks nothing on the dual side) ......  mcf_certify / mcf_bottlenecks
  *   UnboundedProblemError / status "infeasible" carry no witness in the reference (exceptions.py:65-93 names the entering
@@ -237,7 +239,7 @@ int mcf_create(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, c
  * the reference's default budget max(100, 20 * (m + n)), simplex.py:1470).
  * A verdict is final: on a handle whose status is already optimal, infeasible or unbounded the call is a no-op that makes no
  * pivot and leaves status, counters (mcf_stats.pivots, unbounded_arc, ...) and every array as they are; only an iteration
- * limit is resumed.  mcf_reset, mcf_set_basis, mcf_update_costs and mcf_update_rhs are what put such a handle back to "running". */
+ * limit is resumed.  mcf_reset, mcf_set_basis, mcf_update_costs, mcf_update_rhs and mcf_add_arcs are what put such a handle back to "running". */
 int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user, int64_t cb_interval);
 
 /* Solve `count` INDEPENDENT instances side by side: one persistent workgroup (one CU) per handle, each running its whole
@@ -352,6 +354,59 @@ int mcf_update_rhs(mcf_handle* h,
                    int64_t n_sup, const int64_t* node, const int64_t* new_supply,
                    int64_t n_cap, const int64_t* arc,  const int64_t* new_cap,
                    mcf_rhs_report* out /* may be NULL */);
+
+/* Add arcs to the resident handle: `count` new arcs tail[i] -> head[i] with cost[i] and cap[i] (mcf_create's conventions;
+ * arc_priority[i] as in mcf_options.arc_priority for key_mode 2, NULL = 0).  New arc i gets the caller's index m + i, m the arc
+ * count before the call.  A new arc enters non-basic at its lower bound with flow 0, so flows, potentials, the tree and every
+ * existing reduced cost stay exactly as they are and the basis stays primal and strongly feasible: what has to happen is a
+ * re-layout.  Engine order is a total order (head bucket, tail, caller's index); the new arcs belong inside it, and every
+ * per-arc array, the node -> arc adjacency and the nodes' pred words follow.  That merge of two sorted sequences runs on the
+ * device as streaming passes over the arrays that are already there; only the new arcs cross the bus (sorted on the host,
+ * uploaded with their keys and the sorted list of their 2 * count end points), and nothing of size m comes down.  It replaces
+ * a new mcf_create of the extended instance plus mcf_set_basis, which uploads the whole instance, walks the tree on the host
+ * and throws the resident reduced costs, key codes and the blocked preorder list away.  Removing an arc needs no call of its
+ * own: capacity 0 through mcf_update_rhs closes it and keeps every index.
+ *   valid        between solves in any state of the handle (fresh, mid-solve after an iteration limit, optimal, infeasible,
+ *                unbounded), on both tree layouts, every rule and key_mode, handles that dropped their resident reduced costs
+ *                and handles with no_rcache.  count == 0 is valid and behaves like an empty mcf_update_costs.  Handles with
+ *                shard_count > 1: MCF_E_STATE.  Nodes cannot be added: n, the root's id and the head-bucket node ranges stay.
+ *   engine path  the handle keeps the path, the pricing grid (price_blocks), the sweep variant and the tree layout it was
+ *                created with; the fused LDS path recomputes its LDS plan for the grown m.  Where the grown instance no longer
+ *                satisfies a hard limit of that path -- the LDS capacity of the fused small-instance loop (k_solve_small) is
+ *                the only one -- the call returns MCF_E_STATE with a message that names the limit, before anything changes
+ *                (the way on is a new handle plus mcf_set_basis).
+ *   errors       all checked before anything changes.  MCF_E_BAD_ARG: null handle, negative count, null arrays with a positive
+ *                count, an end point outside [0, n), a self-loop.  MCF_E_RANGE: |cost| > INT32_MAX, big-M would reach 2^44, or
+ *                m + count + n >= 2^30.  MCF_E_ALLOC: a new array cannot be allocated -- the re-layout is out of place and the
+ *                pointers are swapped only after every pass has completed, so the handle is exactly as it was.  The arc arrays
+ *                (and the adjacency) exist TWICE for the duration of the call.  MCF_E_HIP from a device pass AFTER the swap
+ *                (the message says so) is the one failure that leaves the handle unusable: destroy it.
+ *   afterwards   the static arrays -- tail / head / cost / orig / cap, the bucket offsets, the adjacency as a set per node
+ *                (the order inside a node's list is not part of the contract), the priorities, the Devex granule table -- are
+ *                exactly what mcf_create of the extended instance (old arcs, then the new ones in the given order) holds, and
+ *                so is the host image: mcf_reset, mcf_set_basis, mcf_update_*, the certificates and the objective work on the
+ *                extended instance.  Old arcs keep flow and state; new arcs have state +1 and flow 0.  parent / size / pos /
+ *                order / depth / psize and the blocked list's arenas are untouched; pred words are re-indexed, the artificial
+ *                arc of node v is now m' + v (in the walk records and in mcf_get_tree).  Potentials are unchanged, except below
+ *                artificial tree arcs when a new cost raised big-M (the mechanism of mcf_update_costs; bigm_grew = 1).
+ *                Resident reduced costs and key codes are exact for every arc where the handle keeps them: old ones carried
+ *                over, not recomputed (unless big-M grew), new ones gathered from the potentials.  The solve status is back to
+ *                "running" and the counters keep counting; everything derived for pricing starts over exactly as after
+ *                mcf_update_costs; captured graphs are dropped; scratch of the other passes whose size depends on m is
+ *                released and allocated again on its next use. */
+typedef struct mcf_arcs_report {
+    int64_t first_index;   /* caller's index of the first new arc = m before the call; new arc i is first_index + i */
+    int64_t m;             /* arcs after the call */
+    int64_t eligible;      /* new arcs with reduced cost < 0 under the resident potentials (census on the device) */
+    int64_t bigm_grew;     /* 1 = a new cost raised big-M (potentials below artificial tree arcs moved, as in mcf_update_costs) */
+    int64_t shifted_only;  /* old arcs that moved by a constant offset inside a chunk that received no new arc (diagnostic) */
+    double  device_ms;     /* HIP events round the device passes: the stream work of the re-layout plus that of the passes after
+                              the swap; the host image's own merge and the frees are outside both pairs of events */
+} mcf_arcs_report;
+
+int mcf_add_arcs(mcf_handle* h, int64_t count, const int32_t* tail, const int32_t* head, const int64_t* cost,
+                 const int64_t* cap, const int8_t* arc_priority /* key_mode 2; may be NULL = 0 */,
+                 mcf_arcs_report* out /* may be NULL */);
 
 /* ---- certificate on the device (the reference's validate_flow / compute_bottleneck_arcs, utils.py:169-312, plus the dual
  * half the reference never checks).  Conservation, bounds, complementary slackness, the exact objectives and the

@@ -2101,3 +2101,37 @@ MCF_HD bool mcf_cut_proven(const McfCutAcc& a, __int128* excess) {
     *excess = (__int128)(((mcf_u128)a.sup_hi << 64) | a.sup_lo) - (__int128)(((mcf_u128)a.cap_hi << 64) | a.cap_lo);
     return a.leave_uncap == 0 && *excess > 0;
 }
+
+// ---- topology change (mcf_add_arcs): index arithmetic of the merge of k new arcs into engine order
+// Engine order is a total order (mcf_host.h: mcf_build_image): head bucket first, then tail, then the caller's index.  New arcs
+// get the caller's indices m, m + 1, ..., so among arcs of equal (bucket, tail) every old arc precedes every new one and the new
+// ones keep the given order.  With the new arcs sorted by that key, the merged order follows from two counting rules; the same
+// two serve the node -> arc adjacency, merged with the sorted list of the 2k new end points.
+MCF_HD int64_t mcf_topo_per(int32_t n) { return ((int64_t)n + MCF_NUM_BUCKETS - 1) / MCF_NUM_BUCKETS; }   // nodes per head bucket
+MCF_HD int64_t mcf_topo_key(int32_t tail, int32_t head, int64_t per) { return (((int64_t)head / per) << 32) | (int64_t)tail; }
+// entries of the ascending a[0 .. n) that are < x / <= x
+MCF_HD int64_t mcf_count_below(const int64_t* a, int64_t n, int64_t x) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a[mid] < x) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+MCF_HD int64_t mcf_count_upto(const int64_t* a, int64_t n, int64_t x) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a[mid] <= x) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// new engine index of OLD engine arc e: e plus the new arcs whose key is strictly smaller
+MCF_HD int64_t mcf_topo_old_index(int64_t e, int64_t key, const int64_t* new_keys, int64_t k) { return e + mcf_count_below(new_keys, k, key); }
+// new engine index of the NEW arc of sorted rank r: r plus the old arcs whose key is <= its own -- every old arc of a lower
+// bucket, and inside its own bucket an upper bound on the (ascending) tails
+MCF_HD int64_t mcf_topo_new_index(int64_t r, int64_t key, const int32_t* old_tail, const int64_t* bucket_off) {
+    const int32_t x = (int32_t)(key >> 32), t = (int32_t)(key & 0xffffffff);
+    int64_t lo = bucket_off[x], hi = bucket_off[x + 1];
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (old_tail[mid] <= t) lo = mid + 1; else hi = mid; }
+    return r + lo;
+}
+// adjacency: the list of node u starts at its old offset plus the new end points on nodes below u ...
+MCF_HD int64_t mcf_topo_adj_off(int64_t old_off, int64_t u, const int64_t* ep_node, int64_t k2) { return old_off + mcf_count_below(ep_node, k2, u); }
+// ... old entry p moves up by the new end points appended to lists that end at or before it (ep_end[j] = old end of the list
+// of end point j's node, ascending with j), and end point j lands at ep_end[j] + j
+MCF_HD int64_t mcf_topo_adj_index(int64_t p, const int64_t* ep_end, int64_t k2) { return p + mcf_count_upto(ep_end, k2, p); }

@@ -2461,6 +2461,43 @@ void free_all(mcf_handle* h) {
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
 }
 
+// LDS plan of the fused small-instance path (every offset a multiple of 16) for an instance of m_pad padded arcs; false when
+// it does not fit the LDS capacity of k_solve_small
+bool small_plan(int64_t m_pad, size_t arcw_count, int32_t n_nodes, bool devex, SmallLayout* out) {
+    SmallLayout L;
+    uint32_t off = 0;
+    auto take = [&](uint64_t bytes) { const uint32_t o = off; off += (uint32_t)((bytes + 15) / 16 * 16); return o; };
+    const uint64_t mp = (uint64_t)m_pad, Nn = (uint64_t)n_nodes;
+    const uint64_t need = mp * 21 + (uint64_t)arcw_count * 16 + Nn * 112 + 4096;
+    if (need >= 150 * 1024) return false;   // (before the offsets are formed: they are 32-bit)
+    L.tail = take(mp * 4); L.head = take(mp * 4); L.cost = take(mp * 4); L.orig = take(mp * 4);
+    L.state = take(mp); L.weight = take(devex ? mp * 4 : 0);
+    L.arcw = take((uint64_t)arcw_count * 16); L.pi = take(Nn * 8); L.node = take(Nn * 16);
+    L.order0 = take(Nn * 4); L.order1 = take(Nn * 4); L.pos0 = take(Nn * 4); L.pos1 = take(Nn * 4);
+    L.path1 = take(Nn * 4); L.path2 = take(Nn * 4); L.ppos1 = take(Nn * 4); L.ppos2 = take(Nn * 4);
+    L.rec1 = take(Nn * 16); L.rec2 = take(Nn * 16);
+    L.seg = take((2 * Nn + 2) * sizeof(McfSeg)); L.ctx = take(sizeof(McfCtx));
+    L.total = off;
+    if (L.total > kSmallMaxLds) return false;
+    *out = L;
+    return true;
+}
+
+// The dynamic-LDS limit of the fused kernels covers `total` bytes on this device.  (The limit is a property of the kernel,
+// not of the handle: it only ever grows, so that handles of different sizes can be alive together -- and share one batched launch.)
+bool small_reserve(int device, uint32_t total) {
+    static std::mutex lds_mu;
+    static int lds_limits[64] = {0};   // per device: the attribute belongs to the device's copy of the function
+    int& lds_limit = lds_limits[device & 63];
+    std::lock_guard<std::mutex> lock(lds_mu);
+    if ((int)total <= lds_limit) return true;
+    hipError_t fe = hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
+    if (fe == hipSuccess) fe = hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve_small_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
+    if (fe != hipSuccess) { (void)hipGetLastError(); return false; }   // (the refusal must not surface later as some launch's error)
+    lds_limit = (int)total;
+    return true;
+}
+
 }  // namespace
 
 #include "mcf_passes_host.h"
@@ -2620,40 +2657,10 @@ int mcf_create(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, c
     v.reach = nullptr; v.chg = nullptr;
     v.path1 = h->d_path1; v.path2 = h->d_path2; v.ppos1 = h->d_ppos1; v.ppos2 = h->d_ppos2; v.rec1 = h->d_rec1; v.rec2 = h->d_rec2; v.seg = h->d_seg; v.ctx = h->d_ctx;
 
-    {
-        // LDS plan of the fused small-instance path (every offset a multiple of 16)
-        SmallLayout& L = h->small_layout;
-        uint32_t off = 0;
-        auto take = [&](uint64_t bytes) { const uint32_t o = off; off += (uint32_t)((bytes + 15) / 16 * 16); return o; };
-        const uint64_t mp = (uint64_t)im.m_pad, Nn = (uint64_t)im.n_nodes;
-        L.tail = take(mp * 4); L.head = take(mp * 4); L.cost = take(mp * 4); L.orig = take(mp * 4);
-        L.state = take(mp); L.weight = take(opt.rule == MCF_RULE_DEVEX_BLOCK ? mp * 4 : 0);
-        L.arcw = take((uint64_t)im.arcw.size() * 16); L.pi = take(Nn * 8); L.node = take(Nn * 16);
-        L.order0 = take(Nn * 4); L.order1 = take(Nn * 4); L.pos0 = take(Nn * 4); L.pos1 = take(Nn * 4);
-        L.path1 = take(Nn * 4); L.path2 = take(Nn * 4); L.ppos1 = take(Nn * 4); L.ppos2 = take(Nn * 4);
-        L.rec1 = take(Nn * 16); L.rec2 = take(Nn * 16);
-        L.seg = take((2 * Nn + 2) * sizeof(McfSeg)); L.ctx = take(sizeof(McfCtx));
-        L.total = off;
-        const uint64_t need = mp * 21 + (uint64_t)im.arcw.size() * 16 + Nn * 112 + 4096;
-        h->small = !h->bpl && !opt.no_fused && !opt.profile && h->shards == 1 && need < 150 * 1024 && L.total <= kSmallMaxLds;
-        if (h->small) {
-            // (the limit is a property of the kernel, not of the handle: it only ever grows, so that handles of different
-            //  sizes can be alive together -- and share one batched launch)
-            static std::mutex lds_mu;
-            static int lds_limits[64] = {0};   // per device: the attribute belongs to the device's copy of the function
-            int& lds_limit = lds_limits[h->device & 63];
-            std::lock_guard<std::mutex> lock(lds_mu);
-            hipError_t fe = hipSuccess;
-            if ((int)L.total > lds_limit) {
-                fe = hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
-                if (fe == hipSuccess) fe = hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve_small_batch),
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total);
-                if (fe == hipSuccess) lds_limit = (int)L.total;
-                else (void)hipGetLastError();   // (the refusal must not surface later as some launch's error)
-            }
-            if (fe != hipSuccess) h->small = false;  // fall back to the three-kernel GPU path
-        }
-    }
+    // the fused small-instance path: its LDS plan, and the kernels' dynamic-LDS limit raised to it (refused: the three-kernel GPU path)
+    h->small = !h->bpl && !opt.no_fused && !opt.profile && h->shards == 1 &&
+               small_plan(im.m_pad, im.arcw.size(), im.n_nodes, opt.rule == MCF_RULE_DEVEX_BLOCK, &h->small_layout) &&
+               small_reserve(h->device, h->small_layout.total);
     // position-space subtree sizes for the cycle scan: every handle but the LDS-resident ones
     const bool scan_ok = opt.cycle_scan >= 0 && im.n_nodes <= kScanMaxNodes && !h->small;  // -1: never scan
     v.bmeta[0] = v.bmeta[1] = nullptr; v.bext[0] = v.bext[1] = nullptr; v.blk_shift = 0; v.blk_cap = 0; v.ncandx = 0; v.candx = nullptr;

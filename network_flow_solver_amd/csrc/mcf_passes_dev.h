@@ -750,3 +750,187 @@ __global__ __launch_bounds__(kRhsThreads) void k_rhs_flows(McfView v, int32_t cu
     rhs_count(info, RHS_WRONG, wrong);
     rhs_count(info, RHS_FLIPS, flips);
 }
+
+// ------------------------------------------------------------------ mcf_add_arcs: merge new arcs into a resident handle
+// A new arc enters non-basic at its lower bound with flow 0: flows, potentials, the tree and every existing reduced cost stay.
+// What moves is the layout -- engine order is a total order (head bucket, tail, caller's index) and the k new arcs belong
+// inside it.  Index arithmetic: mcf_core.h (mcf_topo_*).  All passes are out of place; the host swaps the pointers afterwards.
+//   k_aa_new      one lane per new arc (sorted by key): its engine index (an upper bound on tail inside its bucket) and its
+//                 static fields -- state +1, flow 0;
+//   k_aa_scatter  ONE streaming pass over the old arcs in chunks of kAaChunk: old arcs are sorted by the same key, so their
+//                 offset is monotone, and a chunk with the same offset at both ends is a shifted copy -- 16-byte loads, 16-byte
+//                 stores where the offset keeps the alignment, no search per arc.  Other chunks search per arc.  Either way
+//                 the map old index -> new index is left in emap[] for the adjacency and the node records;
+//   k_aa_adj*     the adjacency: offsets, old entries (engine index remapped through emap), the 2k new entries appended to
+//                 their nodes' lists;
+//   k_aa_nodes    pred words: real arcs through emap, artificial ones + k;
+//   k_aa_price    one lane per new arc: rc = cost + pi[tail] - pi[head], key code, census of the eligible ones.
+constexpr int kAaThreads = 256;
+constexpr int kAaChunk = kAaThreads * 4;
+
+typedef int aa_int4 __attribute__((ext_vector_type(4)));
+typedef long long aa_long2 __attribute__((ext_vector_type(2)));
+template <bool NT, typename T>
+__device__ __forceinline__ T aa_ld(const T* p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+
+struct AaArgs {
+    int64_t m, k, per;                         // old arcs, new arcs, nodes per head bucket
+    int64_t bucket_off[MCF_NUM_BUCKETS + 1];   // of the OLD layout
+    // the new arcs, sorted by (bucket, tail, given order)
+    const int64_t* nkey;                       // [k]
+    const int32_t *ntail, *nhead, *ncost, *norig;
+    const int64_t* ncap;
+    const int8_t* nprio;                       // nullptr unless the handle keeps priorities
+    int64_t* npos;                             // [k] out: engine index of every new arc
+    // old arrays / new arrays (prio, rcache, vkey: nullptr where the handle has none)
+    const int32_t *tail, *head, *cost, *orig;
+    const int8_t *state, *prio;
+    const int64_t* rcache;
+    const int32_t* vkey;
+    const McfArcW* arcw;
+    int32_t *tail2, *head2, *cost2, *orig2;
+    int8_t *state2, *prio2;
+    int64_t* rcache2;
+    int32_t* vkey2;
+    McfArcW* arcw2;
+    int32_t* emap;                             // [m] out: old engine index -> new engine index
+    unsigned long long* info;                  // [0] arcs of shifted chunks, [1] eligible new arcs
+};
+
+__global__ __launch_bounds__(kAaThreads) void k_aa_new(AaArgs a) {
+    const int64_t stride = (int64_t)gridDim.x * kAaThreads;
+    for (int64_t r = (int64_t)blockIdx.x * kAaThreads + threadIdx.x; r < a.k; r += stride) {
+        const int64_t d = mcf_topo_new_index(r, a.nkey[r], a.tail, a.bucket_off);
+        a.npos[r] = d;
+        a.tail2[d] = a.ntail[r]; a.head2[d] = a.nhead[r]; a.cost2[d] = a.ncost[r]; a.orig2[d] = a.norig[r];
+        a.state2[d] = 1;
+        if (a.prio2) a.prio2[d] = a.nprio ? (int8_t)(a.nprio[r] & 3) : (int8_t)0;
+        if (a.rcache2) a.rcache2[d] = 0;   // (k_aa_price fills both where the handle keeps them)
+        if (a.vkey2) a.vkey2[d] = 0;
+        McfArcW w;
+        w.cap = a.ncap[r]; w.flow = 0;
+        a.arcw2[d] = w;
+    }
+}
+
+__device__ __forceinline__ void aa_move_one(const AaArgs& a, int64_t e, int64_t d) {
+    a.tail2[d] = a.tail[e]; a.head2[d] = a.head[e]; a.cost2[d] = a.cost[e]; a.orig2[d] = a.orig[e];
+    a.state2[d] = a.state[e];
+    if (a.prio2) a.prio2[d] = a.prio[e];
+    if (a.rcache2) a.rcache2[d] = a.rcache[e];
+    if (a.vkey2) a.vkey2[d] = a.vkey[e];
+    a.arcw2[d] = a.arcw[e];
+    a.emap[e] = (int32_t)d;
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kAaThreads) void k_aa_scatter(AaArgs a) {
+    const int64_t chunks = (a.m + kAaChunk - 1) / kAaChunk;
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const int64_t lo = c * kAaChunk, hi = lo + kAaChunk < a.m ? lo + kAaChunk : a.m;
+        // the offsets of the chunk's first and last arc (the same addresses in every lane: scalar loads)
+        const int64_t off = mcf_count_below(a.nkey, a.k, mcf_topo_key(a.tail[lo], a.head[lo], a.per));
+        const int64_t off_hi = mcf_count_below(a.nkey, a.k, mcf_topo_key(a.tail[hi - 1], a.head[hi - 1], a.per));
+        if (off == off_hi) {
+            // shifted copy: lane t owns arcs [e, e + 4), e a multiple of 4 (every array is padded to a multiple of 1024 arcs,
+            // so the wide loads stay inside it; stores are cut at hi)
+            const int64_t e = lo + 4 * (int64_t)threadIdx.x, d = e + off;
+            if (threadIdx.x == 0) atomicAdd(&a.info[0], (unsigned long long)(hi - lo));
+            if (e >= hi) continue;
+            const aa_int4 t4 = aa_ld<NT>(reinterpret_cast<const aa_int4*>(a.tail + e)), h4 = aa_ld<NT>(reinterpret_cast<const aa_int4*>(a.head + e));
+            const aa_int4 c4 = aa_ld<NT>(reinterpret_cast<const aa_int4*>(a.cost + e)), o4 = aa_ld<NT>(reinterpret_cast<const aa_int4*>(a.orig + e));
+            const int32_t s4 = aa_ld<NT>(reinterpret_cast<const int32_t*>(a.state + e));
+            const int32_t p4 = a.prio2 ? aa_ld<NT>(reinterpret_cast<const int32_t*>(a.prio + e)) : 0;
+            aa_long2 r01 = {0, 0}, r23 = {0, 0};
+            if (a.rcache2) { r01 = aa_ld<NT>(reinterpret_cast<const aa_long2*>(a.rcache + e)); r23 = aa_ld<NT>(reinterpret_cast<const aa_long2*>(a.rcache + e + 2)); }
+            aa_int4 k4 = {0, 0, 0, 0};
+            if (a.vkey2) k4 = aa_ld<NT>(reinterpret_cast<const aa_int4*>(a.vkey + e));
+            aa_long2 w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = e + j < hi ? aa_ld<NT>(reinterpret_cast<const aa_long2*>(a.arcw + e + j)) : aa_long2{0, 0};
+            const aa_int4 m4 = {(int32_t)d, (int32_t)d + 1, (int32_t)d + 2, (int32_t)d + 3};
+            if (e + 4 <= hi) *reinterpret_cast<aa_int4*>(a.emap + e) = m4;
+            else for (int j = 0; e + j < hi; ++j) a.emap[e + j] = m4[j];
+            if ((off & 3) == 0 && e + 4 <= hi) {
+                *reinterpret_cast<aa_int4*>(a.tail2 + d) = t4; *reinterpret_cast<aa_int4*>(a.head2 + d) = h4;
+                *reinterpret_cast<aa_int4*>(a.cost2 + d) = c4; *reinterpret_cast<aa_int4*>(a.orig2 + d) = o4;
+                *reinterpret_cast<int32_t*>(a.state2 + d) = s4;
+                if (a.prio2) *reinterpret_cast<int32_t*>(a.prio2 + d) = p4;
+                if (a.rcache2) { *reinterpret_cast<aa_long2*>(a.rcache2 + d) = r01; *reinterpret_cast<aa_long2*>(a.rcache2 + d + 2) = r23; }
+                if (a.vkey2) *reinterpret_cast<aa_int4*>(a.vkey2 + d) = k4;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (e + j >= hi) break;
+                    a.tail2[d + j] = t4[j]; a.head2[d + j] = h4[j]; a.cost2[d + j] = c4[j]; a.orig2[d + j] = o4[j];
+                    a.state2[d + j] = (int8_t)(s4 >> (8 * j));
+                    if (a.prio2) a.prio2[d + j] = (int8_t)(p4 >> (8 * j));
+                    if (a.rcache2) a.rcache2[d + j] = j < 2 ? r01[j] : r23[j - 2];
+                    if (a.vkey2) a.vkey2[d + j] = k4[j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (e + j < hi) *reinterpret_cast<aa_long2*>(a.arcw2 + d + j) = w[j];
+        } else {
+            for (int64_t e = lo + threadIdx.x; e < hi; e += kAaThreads)
+                aa_move_one(a, e, mcf_topo_old_index(e, mcf_topo_key(a.tail[e], a.head[e], a.per), a.nkey, a.k));
+        }
+    }
+}
+
+// adjacency offsets: one lane per node (n + 1 entries)
+__global__ __launch_bounds__(kAaThreads) void k_aa_adj_off(const int64_t* __restrict__ off, int64_t count, const int64_t* __restrict__ ep_node, int64_t k2,
+                                                           int64_t* __restrict__ off2) {
+    const int64_t stride = (int64_t)gridDim.x * kAaThreads;
+    for (int64_t u = (int64_t)blockIdx.x * kAaThreads + threadIdx.x; u < count; u += stride) off2[u] = mcf_topo_adj_off(off[u], u, ep_node, k2);
+}
+// old entries: one lane per entry
+__global__ __launch_bounds__(kAaThreads) void k_aa_adj(const int64_t* __restrict__ adj, int64_t count, const int64_t* __restrict__ ep_end, int64_t k2,
+                                                       const int32_t* __restrict__ emap, int64_t* __restrict__ adj2) {
+    const int64_t stride = (int64_t)gridDim.x * kAaThreads;
+    for (int64_t p = (int64_t)blockIdx.x * kAaThreads + threadIdx.x; p < count; p += stride) {
+        const int64_t x = adj[p];
+        const int64_t e = (x & 0xffffffffll) >> 1;
+        adj2[mcf_topo_adj_index(p, ep_end, k2)] = (x & ~0xfffffffell) | ((int64_t)emap[e] << 1);
+    }
+}
+// new entries: ep_val[j] = (other end point << 32) | (sorted rank of the arc << 1) | (1 when the node is the arc's tail)
+__global__ __launch_bounds__(kAaThreads) void k_aa_adj_new(const int64_t* __restrict__ ep_val, const int64_t* __restrict__ ep_end, int64_t k2,
+                                                           const int64_t* __restrict__ npos, int64_t* __restrict__ adj2) {
+    const int64_t stride = (int64_t)gridDim.x * kAaThreads;
+    for (int64_t j = (int64_t)blockIdx.x * kAaThreads + threadIdx.x; j < k2; j += stride) {
+        const int64_t x = ep_val[j];
+        adj2[ep_end[j] + j] = (x & ~0xfffffffell) | (npos[(x & 0xffffffffll) >> 1] << 1);
+    }
+}
+
+__global__ __launch_bounds__(kAaThreads) void k_aa_nodes(const McfNode* __restrict__ node, int32_t n_nodes, int64_t m, int64_t k,
+                                                         const int32_t* __restrict__ emap, McfNode* __restrict__ node2) {
+    const int32_t stride = (int32_t)(gridDim.x * kAaThreads);
+    for (int32_t v = (int32_t)(blockIdx.x * kAaThreads + threadIdx.x); v < n_nodes; v += stride) {
+        McfNode r = node[v];
+        if (r.pred >= 0) {
+            const int64_t arc = r.pred >> 1;
+            const int64_t arc2 = arc >= m ? arc + k : (int64_t)emap[arc];
+            r.pred = (int32_t)((arc2 << 1) | (r.pred & 1));
+        }
+        node2[v] = r;
+    }
+}
+
+// reduced costs / key codes of the new arcs (state +1: the violation is -rc) on the NEW arrays, and the census
+__global__ __launch_bounds__(kAaThreads) void k_aa_price(McfView v, const int64_t* __restrict__ npos, int64_t k, int64_t* __restrict__ rcache,
+                                                         int32_t* __restrict__ vkey, unsigned long long* __restrict__ info) {
+    __shared__ int32_t s[kPassWaves];
+    int32_t eligible = 0;
+    const int64_t stride = (int64_t)gridDim.x * kAaThreads;
+    for (int64_t r = (int64_t)blockIdx.x * kAaThreads + threadIdx.x; r < k; r += stride) {
+        const int64_t e = npos[r];
+        const int64_t rc = (int64_t)v.cost[e] + v.pi[v.tail[e]] - v.pi[v.head[e]];
+        if (rcache) rcache[e] = rc;
+        if (vkey) vkey[e] = mcf_vkey(-rc, v.vk_bigm, v.vk_half);
+        eligible += rc < 0 ? 1 : 0;
+    }
+    const int32_t total = wave_block_sum(eligible, s);
+    if (threadIdx.x == 0 && total > 0) atomicAdd(&info[1], (unsigned long long)total);
+}

@@ -407,6 +407,328 @@ int mcf_update_rhs(mcf_handle* h, int64_t n_sup, const int64_t* node, const int6
     return MCF_OK;
 }
 
+// Add arcs to the resident handle (kernels k_aa_* above).  The new arcs are sorted on the host and uploaded with their keys
+// and the sorted list of their end points; the re-layout of everything the handle holds per arc runs on the device, out of
+// place, and the pointers are swapped once every pass has completed.  Everything is validated before the first byte moves.
+int mcf_add_arcs(mcf_handle* h, int64_t count, const int32_t* tail, const int32_t* head, const int64_t* cost, const int64_t* cap,
+                 const int8_t* arc_priority, mcf_arcs_report* out) {
+    if (!h) return MCF_E_BAD_ARG;
+    if (h->shards != 1) {
+        h->err = "mcf_add_arcs: handle was created with shard_count > 1; sharded handles cannot change their topology";
+        return MCF_E_STATE;
+    }
+    if (count < 0 || (count > 0 && (!tail || !head || !cost || !cap))) { h->err = "mcf_add_arcs: bad count / null array"; return MCF_E_BAD_ARG; }
+    McfHostImage& im = h->im;
+    const int64_t k = count, m = im.m, m2 = m + k;
+    const int32_t n = im.n, N = im.n_nodes;
+    // (on the count alone, before an array is read)
+    if (k >= ((int64_t)1 << 30) || (int64_t)n + m2 >= ((int64_t)1 << 30)) { h->err = "mcf_add_arcs: m + count + n must stay below 2^30"; return MCF_E_RANGE; }
+    for (int64_t i = 0; i < k; ++i) {
+        if (tail[i] < 0 || tail[i] >= n || head[i] < 0 || head[i] >= n) { h->err = "mcf_add_arcs: arc end point out of range"; return MCF_E_BAD_ARG; }
+        if (tail[i] == head[i]) { h->err = "mcf_add_arcs: self-loop"; return MCF_E_BAD_ARG; }
+    }
+    int64_t max_abs = 0;
+    for (int64_t i = 0; i < k; ++i) {
+        if (cost[i] > INT32_MAX || cost[i] < -(int64_t)INT32_MAX) { h->err = "mcf_add_arcs: |cost| must fit int32"; return MCF_E_RANGE; }
+        const int64_t a = cost[i] < 0 ? -cost[i] : cost[i];
+        if (a > max_abs) max_abs = a;
+    }
+    // big-M never shrinks; it grows when a new cost needs it (same rule as mcf_build_image)
+    int64_t big_m = im.big_m;
+    if ((max_abs + 1) * ((int64_t)n + 2) > big_m) big_m = (max_abs + 1) * ((int64_t)n + 2);
+    if (big_m >= ((int64_t)1 << 44)) { h->err = "mcf_add_arcs: max|cost| * n too large for big-M"; return MCF_E_RANGE; }
+    const int64_t d_bigm = big_m - im.big_m;
+    const int64_t m_pad2 = m2 > 0 ? ((m2 + 1023) / 1024) * 1024 : 1024;
+    // the handle keeps its engine path: the fused LDS loop has to hold the grown instance
+    SmallLayout L2 = h->small_layout;
+    if (h->small && k > 0 && !small_plan(m_pad2, (size_t)(m2 + n), N, h->opt.rule == MCF_RULE_DEVEX_BLOCK, &L2)) {
+        h->err = "mcf_add_arcs: the grown instance exceeds the LDS capacity of the fused small-instance loop (k_solve_small) this handle runs on";
+        return MCF_E_STATE;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->small && k > 0 && !small_reserve(h->device, L2.total)) {
+        h->err = "mcf_add_arcs: the device refuses the dynamic LDS the grown instance needs in the fused small-instance loop (k_solve_small)";
+        return MCF_E_STATE;
+    }
+    int rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    if (h->h_ctx->status == MCF_INTERNAL_ERROR) { h->err = "mcf_add_arcs: the handle's tree is not usable"; return MCF_E_STATE; }
+    if (d_bigm != 0 && (rc = uc_alloc(h)) != MCF_OK) return rc;
+    for (hipEvent_t& ev : h->ct_ev) if (!ev) HIP_TRY(h, hipEventCreate(&ev));
+    hipStream_t s = h->stream;
+    mcf_arcs_report rep;
+    std::memset(&rep, 0, sizeof rep);
+    rep.first_index = m;
+    rep.m = m2;
+
+    // ---- the new arcs in engine order: (head bucket, tail, given order)
+    const int64_t per = mcf_topo_per(n);
+    std::vector<int64_t> perm((size_t)k);
+    for (int64_t i = 0; i < k; ++i) perm[(size_t)i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return mcf_topo_key(tail[a], head[a], per) < mcf_topo_key(tail[b], head[b], per); });
+    std::vector<int64_t> nkey((size_t)k), ncap((size_t)k);
+    std::vector<int32_t> ntail((size_t)k), nhead((size_t)k), ncost((size_t)k), norig((size_t)k);
+    std::vector<int8_t> nprio((size_t)k, 0);
+    for (int64_t r = 0; r < k; ++r) {
+        const int64_t i = perm[(size_t)r];
+        nkey[(size_t)r] = mcf_topo_key(tail[i], head[i], per);
+        ntail[(size_t)r] = tail[i]; nhead[(size_t)r] = head[i]; ncost[(size_t)r] = (int32_t)cost[i]; norig[(size_t)r] = (int32_t)(m + i);
+        ncap[(size_t)r] = (cap[i] < 0 || cap[i] >= MCF_INF) ? MCF_INF : cap[i];
+        if (arc_priority) nprio[(size_t)r] = (int8_t)(arc_priority[i] & 3);
+    }
+    // ... and their 2k end points sorted by node (the handle's adjacency, where it holds one)
+    const bool with_adj = h->d_adj != nullptr;
+    const int64_t k2 = with_adj ? 2 * k : 0;
+    std::vector<int64_t> ep_node((size_t)k2), ep_end((size_t)k2), ep_val((size_t)k2);
+    if (with_adj) {
+        std::vector<int64_t> ep((size_t)k2);   // (node << 32) | (rank << 1) | is-tail: sorts by node, then rank
+        for (int64_t r = 0; r < k; ++r) {
+            ep[(size_t)(2 * r)] = ((int64_t)ntail[(size_t)r] << 32) | (r << 1) | 1;
+            ep[(size_t)(2 * r + 1)] = ((int64_t)nhead[(size_t)r] << 32) | (r << 1);
+        }
+        std::sort(ep.begin(), ep.end());
+        for (int64_t j = 0; j < k2; ++j) {
+            const int64_t u = ep[(size_t)j] >> 32, r = (ep[(size_t)j] & 0xffffffffll) >> 1, is_tail = ep[(size_t)j] & 1;
+            ep_node[(size_t)j] = u;
+            ep_end[(size_t)j] = im.adj_off[(size_t)u + 1];
+            ep_val[(size_t)j] = ((int64_t)(is_tail ? nhead[(size_t)r] : ntail[(size_t)r]) << 32) | (r << 1) | is_tail;
+        }
+    }
+
+    if (k == 0) {   // nothing to lay out: the tail of an empty mcf_update_costs
+        HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
+        if ((rc = uc_finish(h, true)) != MCF_OK) return rc;
+        HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+        HIP_TRY(h, hipEventSynchronize(h->ct_ev[1]));
+        float ms0 = 0;
+        if (hipEventElapsedTime(&ms0, h->ct_ev[0], h->ct_ev[1]) != hipSuccess) { (void)hipGetLastError(); ms0 = 0; }
+        rep.device_ms = ms0;
+        if (out) *out = rep;
+        return MCF_OK;
+    }
+
+    // ---- device memory: the upload buffers (freed on return) and the new arrays (the handle's once every pass has completed)
+    std::vector<void*> temps;
+    struct Fresh { void** field; void* ptr; };
+    std::vector<Fresh> fresh;
+    auto give_up = [&](int code, const char* what) {
+        (void)hipStreamSynchronize(s);
+        for (void* p : temps) (void)hipFree(p);
+        for (const Fresh& f : fresh) (void)hipFree(f.ptr);
+        (void)hipGetLastError();
+        if (what) h->err = std::string("mcf_add_arcs: ") + what;
+        return code;
+    };
+    bool alloc_ok = true;
+    auto temp = [&](auto** p, size_t cnt) {
+        *p = nullptr;
+        if (!alloc_ok) return;
+        if (dalloc(p, cnt) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; alloc_ok = false; return; }
+        temps.push_back(*p);
+    };
+    auto renew = [&](auto** field, auto** p, size_t cnt) {   // a new array for *field (skipped where the handle has none)
+        *p = nullptr;
+        if (!alloc_ok || !*field) return;
+        if (dalloc(p, cnt) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; alloc_ok = false; return; }
+        fresh.push_back({reinterpret_cast<void**>(field), *p});
+    };
+    int64_t *t_nkey, *t_ncap, *t_npos, *t_epn, *t_epe, *t_epv;
+    int32_t *t_ntail, *t_nhead, *t_ncost, *t_norig, *t_emap;
+    int8_t* t_nprio;
+    unsigned long long* t_info;
+    temp(&t_nkey, (size_t)k); temp(&t_ncap, (size_t)k); temp(&t_npos, (size_t)k);
+    temp(&t_epn, (size_t)k2); temp(&t_epe, (size_t)k2); temp(&t_epv, (size_t)k2);
+    temp(&t_ntail, (size_t)k); temp(&t_nhead, (size_t)k); temp(&t_ncost, (size_t)k); temp(&t_norig, (size_t)k); temp(&t_emap, (size_t)m);
+    temp(&t_nprio, (size_t)k); temp(&t_info, 2);
+    int32_t *x_tail, *x_head, *x_cost, *x_orig, *x_vkey;
+    int8_t *x_state, *x_prio;
+    float* x_weight;
+    McfArcW* x_arcw;
+    McfNode* x_node;
+    int64_t *x_rcache, *x_adj_off, *x_adj;
+    renew(&h->d_tail, &x_tail, (size_t)m_pad2); renew(&h->d_head, &x_head, (size_t)m_pad2);
+    renew(&h->d_cost, &x_cost, (size_t)m_pad2); renew(&h->d_orig, &x_orig, (size_t)m_pad2);
+    renew(&h->d_state, &x_state, (size_t)m_pad2); renew(&h->d_prio, &x_prio, (size_t)m_pad2);
+    renew(&h->d_weight, &x_weight, (size_t)m_pad2); renew(&h->d_arcw, &x_arcw, (size_t)(m2 + n));
+    renew(&h->d_node, &x_node, (size_t)N);
+    renew(&h->d_rcache, &x_rcache, (size_t)m_pad2); renew(&h->d_vkey, &x_vkey, (size_t)m_pad2);
+    renew(&h->d_adj_off, &x_adj_off, (size_t)n + 1); renew(&h->d_adj, &x_adj, (size_t)(2 * m2));
+    if (!alloc_ok) return give_up(MCF_E_ALLOC, "hipMalloc of the new arc arrays (the arc arrays exist twice for the duration of the call)");
+
+    // ---- device passes, part one: everything that does not touch what the handle holds
+    auto hip_ok = [&](hipError_t e) { return e == hipSuccess; };
+    bool ok = hip_ok(hipEventRecord(h->ct_ev[0], s));
+    auto up = [&](void* dst, const void* src, size_t bytes) { if (ok && bytes) ok = hip_ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s)); };
+    up(t_nkey, nkey.data(), (size_t)k * 8); up(t_ncap, ncap.data(), (size_t)k * 8);
+    up(t_ntail, ntail.data(), (size_t)k * 4); up(t_nhead, nhead.data(), (size_t)k * 4);
+    up(t_ncost, ncost.data(), (size_t)k * 4); up(t_norig, norig.data(), (size_t)k * 4); up(t_nprio, nprio.data(), (size_t)k);
+    up(t_epn, ep_node.data(), (size_t)k2 * 8); up(t_epe, ep_end.data(), (size_t)k2 * 8); up(t_epv, ep_val.data(), (size_t)k2 * 8);
+    if (ok) ok = hip_ok(hipMemsetAsync(t_info, 0, 2 * sizeof(unsigned long long), s));
+    // padding arcs [m2, m_pad2): zeros, state 0
+    const size_t padn = (size_t)(m_pad2 - m2);
+    auto zero = [&](void* base, size_t elem) { if (ok && base && padn) ok = hip_ok(hipMemsetAsync((char*)base + (size_t)m2 * elem, 0, padn * elem, s)); };
+    zero(x_tail, 4); zero(x_head, 4); zero(x_cost, 4); zero(x_orig, 4); zero(x_state, 1); zero(x_prio, 1); zero(x_rcache, 8); zero(x_vkey, 4);
+    if (!ok) return give_up(MCF_E_HIP, "upload of the new arcs");
+    AaArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.m = m; a.k = k; a.per = per;
+    for (int x = 0; x <= MCF_NUM_BUCKETS; ++x) a.bucket_off[x] = im.bucket_off[x];
+    a.nkey = t_nkey; a.ntail = t_ntail; a.nhead = t_nhead; a.ncost = t_ncost; a.norig = t_norig; a.ncap = t_ncap;
+    a.nprio = arc_priority ? t_nprio : nullptr; a.npos = t_npos;
+    a.tail = h->d_tail; a.head = h->d_head; a.cost = h->d_cost; a.orig = h->d_orig; a.state = h->d_state; a.prio = h->d_prio;
+    a.rcache = h->d_rcache; a.vkey = h->d_vkey; a.arcw = h->d_arcw;
+    a.tail2 = x_tail; a.head2 = x_head; a.cost2 = x_cost; a.orig2 = x_orig; a.state2 = x_state; a.prio2 = x_prio;
+    a.rcache2 = x_rcache; a.vkey2 = x_vkey; a.arcw2 = x_arcw;
+    a.emap = t_emap; a.info = t_info;
+    hipLaunchKernelGGL(k_aa_new, dim3(uc_blocks_for(k)), dim3(kAaThreads), 0, s, a);
+    if (m > 0) {
+        const int64_t chunks = (m + kAaChunk - 1) / kAaChunk;
+        const unsigned grid = (unsigned)(chunks < 4096 ? chunks : 4096);
+        hipLaunchKernelGGL(m >= kIncrementalMinArcs ? k_aa_scatter<true> : k_aa_scatter<false>, dim3(grid), dim3(kAaThreads), 0, s, a);
+    }
+    hipLaunchKernelGGL(k_uc_ones, dim3(uc_blocks_for(m_pad2 / 4)), dim3(kUcThreads), 0, s, reinterpret_cast<float4*>(x_weight), m_pad2 / 4);
+    ok = hip_ok(hipMemcpyAsync(x_arcw + m2, h->d_arcw + m, (size_t)n * sizeof(McfArcW), hipMemcpyDeviceToDevice, s));   // the artificial block, shifted by k
+    hipLaunchKernelGGL(k_aa_nodes, dim3(uc_blocks_for(N)), dim3(kAaThreads), 0, s, (const McfNode*)h->d_node, N, m, k, (const int32_t*)t_emap, x_node);
+    if (with_adj) {
+        hipLaunchKernelGGL(k_aa_adj_off, dim3(uc_blocks_for((int64_t)n + 1)), dim3(kAaThreads), 0, s, (const int64_t*)h->d_adj_off, (int64_t)n + 1, (const int64_t*)t_epn, k2, x_adj_off);
+        if (m > 0) hipLaunchKernelGGL(k_aa_adj, dim3(uc_blocks_for(2 * m)), dim3(kAaThreads), 0, s, (const int64_t*)h->d_adj, 2 * m, (const int64_t*)t_epe, k2, (const int32_t*)t_emap, x_adj);
+        hipLaunchKernelGGL(k_aa_adj_new, dim3(uc_blocks_for(k2)), dim3(kAaThreads), 0, s, (const int64_t*)t_epv, (const int64_t*)t_epe, k2, (const int64_t*)t_npos, x_adj);
+    }
+    if (!ok || hipGetLastError() != hipSuccess) return give_up(MCF_E_HIP, "launch of the re-layout passes");
+    // device_ms brackets stream work only: this pair closes behind the last re-layout pass, a second pair goes round part two
+    unsigned long long info[2] = {0, 0};
+    if (hipEventRecord(h->ct_ev[1], s) != hipSuccess || hipMemcpyAsync(info, t_info, sizeof info, hipMemcpyDeviceToHost, s) != hipSuccess)
+        return give_up(MCF_E_HIP, "launch of the re-layout passes");
+
+    // ---- the host image's own merge, while the device works: host work outside both event pairs.  The indices come from the
+    // same counting rules the kernels use (mcf_core.h).  Everything that can fail for lack of memory -- the extended image,
+    // the header of the incremental sweeps, the Devex granule table -- is built here, before anything changes.
+    McfHostImage nim;
+    std::vector<int32_t> emap_h((size_t)m);
+    std::vector<McfDirty> dirty_head;   // 0 or 1 entry
+    std::vector<McfDevex> granules;     // 0 or 1 entry
+    try {
+        nim.tail.assign((size_t)m_pad2, 0); nim.head.assign((size_t)m_pad2, 0); nim.cost.assign((size_t)m_pad2, 0); nim.orig.assign((size_t)m_pad2, 0);
+        nim.cost64.assign((size_t)m2, 0); nim.state.assign((size_t)m_pad2, 0); nim.weight.assign((size_t)m_pad2, 1.0f);
+        nim.arcw.assign((size_t)(m2 + n), McfArcW{0, 0});
+        if (!im.rcache.empty()) nim.rcache.assign((size_t)m_pad2, 0);
+        for (int64_t e = 0; e < m; ++e) {
+            const size_t d = (size_t)mcf_topo_old_index(e, mcf_topo_key(im.tail[(size_t)e], im.head[(size_t)e], per), nkey.data(), k);
+            emap_h[(size_t)e] = (int32_t)d;
+            nim.tail[d] = im.tail[(size_t)e]; nim.head[d] = im.head[(size_t)e]; nim.cost[d] = im.cost[(size_t)e]; nim.orig[d] = im.orig[(size_t)e];
+            nim.cost64[d] = im.cost64[(size_t)e]; nim.state[d] = im.state[(size_t)e]; nim.arcw[d] = im.arcw[(size_t)e];
+            if (!nim.rcache.empty()) nim.rcache[d] = im.rcache[(size_t)e];
+        }
+        for (int64_t r = 0; r < k; ++r) {
+            const size_t d = (size_t)mcf_topo_new_index(r, nkey[(size_t)r], im.tail.data(), im.bucket_off);
+            nim.tail[d] = ntail[(size_t)r]; nim.head[d] = nhead[(size_t)r]; nim.cost[d] = ncost[(size_t)r]; nim.orig[d] = norig[(size_t)r];
+            nim.cost64[d] = ncost[(size_t)r]; nim.state[d] = 1; nim.arcw[d] = McfArcW{ncap[(size_t)r], 0};
+            // (nim.rcache[d] stays 0: the image's potentials are those of the last upload, and mcf_reset / mcf_set_basis refresh
+            //  every reduced cost of the image before they use one)
+        }
+        for (int32_t v = 0; v < n; ++v) nim.arcw[(size_t)(m2 + v)] = im.arcw[(size_t)(m + v)];
+        if (!im.adj_off.empty()) {
+            nim.adj_off.assign((size_t)n + 1, 0);
+            for (int32_t u = 0; u <= n; ++u) nim.adj_off[(size_t)u] = mcf_topo_adj_off(im.adj_off[(size_t)u], u, ep_node.data(), k2);
+        }
+        for (int x = 0; x <= MCF_NUM_BUCKETS; ++x) nim.bucket_off[x] = im.bucket_off[x] + mcf_count_below(nkey.data(), k, (int64_t)x << 32);
+        if (h->d_dirty) {   // the header of the incremental sweeps: this rank's share of every bucket
+            dirty_head.resize(1);
+            dirty_head[0].nlb = h->price_blocks / MCF_NUM_BUCKETS;
+            for (int x = 0; x < MCF_NUM_BUCKETS; ++x) { dirty_head[0].lo[x] = (int32_t)nim.bucket_off[x]; dirty_head[0].hi[x] = (int32_t)nim.bucket_off[x + 1]; }
+        }
+        if (h->d_dx) {      // Devex: the granule table of the new bucket ranges
+            granules.resize(1);
+            std::memset(&granules[0], 0, sizeof(McfDevex));
+            mcf_devex_fill_granules(&granules[0], nim.bucket_off);
+        }
+    } catch (const std::bad_alloc&) {
+        return give_up(MCF_E_ALLOC, "host allocation of the extended image");
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) return give_up(MCF_E_HIP, "the re-layout passes failed");
+    float ms1 = 0, ms2 = 0;
+    if (hipEventElapsedTime(&ms1, h->ct_ev[0], h->ct_ev[1]) != hipSuccess) { (void)hipGetLastError(); ms1 = 0; }
+    rep.shifted_only = (int64_t)info[0];
+
+    // ---- every pass has completed: the handle takes the new arrays over (the old ones are freed at the end: a free synchronises)
+    std::vector<void*> old_arrays;
+    for (const Fresh& f : fresh) { old_arrays.push_back(*f.field); *f.field = f.ptr; }
+    fresh.clear();
+    McfView& v = h->view;
+    v.m = m2;
+    v.tail = h->d_tail; v.head = h->d_head; v.cost = h->d_cost; v.orig = h->d_orig; v.state = h->d_state;
+    if (v.weight) v.weight = h->d_weight;
+    if (v.prio) v.prio = h->d_prio;
+    v.arcw = h->d_arcw; v.node = h->d_node;
+    if (v.rcache) v.rcache = h->d_rcache;
+    if (v.vkey) v.vkey = h->d_vkey;
+    if (v.adj) { v.adj = h->d_adj; v.adj_off = h->d_adj_off; }
+    v.vk_bigm = big_m;
+    for (int x = 0; x <= MCF_NUM_BUCKETS; ++x) v.bucket_off[x] = nim.bucket_off[x];
+    for (int32_t u = 0; u < N; ++u) {   // the image's node records follow (a later mcf_reset / mcf_set_basis rewrites them anyway)
+        int32_t& pred = im.node[(size_t)u].pred;
+        if (pred < 0) continue;
+        const int64_t arc = pred >> 1;
+        pred = (int32_t)(((arc >= m ? arc + k : (int64_t)emap_h[(size_t)arc]) << 1) | (pred & 1));
+    }
+    im.tail.swap(nim.tail); im.head.swap(nim.head); im.cost.swap(nim.cost); im.orig.swap(nim.orig); im.cost64.swap(nim.cost64);
+    im.state.swap(nim.state); im.weight.swap(nim.weight); im.arcw.swap(nim.arcw);
+    if (!im.rcache.empty()) im.rcache.swap(nim.rcache);
+    if (!im.adj_off.empty()) im.adj_off.swap(nim.adj_off);
+    for (int x = 0; x <= MCF_NUM_BUCKETS; ++x) im.bucket_off[x] = nim.bucket_off[x];
+    im.m = m2; im.m_pad = m_pad2; im.big_m = big_m;
+    if (h->small) h->small_layout = L2;
+    drop_graph(h);   // (captured graphs carry the view by value)
+    h->uc_inv.clear(); h->uc_stamp.clear();   // (rebuilt for the new m on their next use)
+    // ---- device passes, part two (its own event pair): the small tables, potentials when big-M grew, the new arcs' reduced
+    // costs, the tail of mcf_update_costs.  A failure from here on is MCF_E_HIP and leaves the handle unusable (include/mcf.h).
+    ok = hip_ok(hipEventRecord(h->ct_ev[0], s));
+    if (ok && !dirty_head.empty()) ok = hip_ok(hipMemcpyAsync(h->d_dirty, dirty_head.data(), offsetof(McfDirty, flag), hipMemcpyHostToDevice, s));
+    if (ok && !granules.empty()) ok = hip_ok(hipMemcpyAsync(h->d_dx, granules.data(), offsetof(McfDevex, wlist), hipMemcpyHostToDevice, s));
+    if (ok && d_bigm != 0) {
+        int32_t depth[2] = {0, 0};
+        ok = hip_ok(hipMemsetAsync(h->d_uc_info, 0, 2 * sizeof(int32_t), s));
+        hipLaunchKernelGGL(k_uc_seed, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfNode*)h->d_node, N, m2, d_bigm, h->d_uc_jump[0], h->d_uc_info);
+        if (ok) ok = hip_ok(hipMemcpyAsync(depth, h->d_uc_info, sizeof depth, hipMemcpyDeviceToHost, s));
+        if (ok) ok = hip_ok(hipStreamSynchronize(s));   // (the depth of the tree decides the number of jump rounds)
+        if (ok) uc_jump_rounds(h, depth[0]);
+        rep.bigm_grew = 1;
+    }
+    if (ok) {
+        hipLaunchKernelGGL(k_aa_price, dim3(uc_blocks_for(k)), dim3(kAaThreads), 0, s, h->view, (const int64_t*)t_npos, k,
+                           h->rcached ? h->d_rcache : (int64_t*)nullptr, h->rcached ? h->view.vkey : (int32_t*)nullptr, t_info);
+        ok = hip_ok(hipGetLastError());
+    }
+    if (ok) ok = hip_ok(hipMemcpyAsync(info, t_info, sizeof info, hipMemcpyDeviceToHost, s));
+    rc = ok ? uc_finish(h, d_bigm != 0) : MCF_E_HIP;   // (ends with a synchronisation of the stream)
+    if (rc == MCF_OK && (hipEventRecord(h->ct_ev[1], s) != hipSuccess || hipEventSynchronize(h->ct_ev[1]) != hipSuccess)) rc = MCF_E_HIP;
+    if (rc != MCF_OK) (void)hipStreamSynchronize(s);
+    // scratch of this call, the old arrays, and the other passes' scratch whose size depends on m (allocated again on its next use)
+    for (void* p : temps) (void)hipFree(p);
+    temps.clear();
+    for (void* p : old_arrays) (void)hipFree(p);
+    lazy_release({{&h->d_ct_flow, 0}, {&h->d_ct_adj_off, 0}, {&h->d_ct_adj, 0}, {&h->d_bn_flag, 0}, {&h->d_bn_cnt, 0}, {&h->d_bn_off, 0}});
+    if (rc != MCF_OK) {
+        (void)hipGetLastError();
+        if (!ok) h->err = "mcf_add_arcs: a device pass after the re-layout failed; the handle is no longer usable";
+        return rc;
+    }
+    if (hipEventElapsedTime(&ms2, h->ct_ev[0], h->ct_ev[1]) != hipSuccess) { (void)hipGetLastError(); ms2 = 0; }
+    // per-pass accounting follows the grown shard (as upload_image sets it)
+    h->shard_arcs = im.m;
+    h->priced_per_pass = h->opt.rule == MCF_RULE_DEVEX_BLOCK ? h->shard_arcs * h->h_ctx->block_granules / MCF_GRANULES : h->shard_arcs;
+    {
+        const bool devex = h->opt.rule == MCF_RULE_DEVEX_BLOCK;
+        if (h->d_vkey && !devex) h->stats.price_bytes = 4 * h->priced_per_pass;
+        else if (h->rcached) h->stats.price_bytes = (devex ? 13 : 9) * h->priced_per_pass;
+        else h->stats.price_bytes = (devex ? 17 : 13) * h->priced_per_pass + 8 * (int64_t)im.n_nodes;
+    }
+    rep.eligible = (int64_t)info[1];
+    rep.device_ms = ms1 + ms2;
+    if (out) *out = rep;
+    return MCF_OK;
+}
+
 // ---- certificate on the device (include/mcf.h)
 int mcf_certify(mcf_handle* h, const int64_t* flow, const int64_t* potential, uint32_t checks, mcf_certificate* out) {
     if (!h || !out || (checks & ~MCF_CERT_ALL)) return MCF_E_BAD_ARG;

@@ -32,7 +32,7 @@ ABI_SYMBOLS = (
     "mcf_default_options", "mcf_create", "mcf_solve", "mcf_solve_batch", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs",
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
-    "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut",
+    "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_add_arcs",
 )
 # mcf_certify: check groups and verdicts (include/mcf.h)
 CERT_BOUNDS, CERT_CONSERVATION, CERT_DUAL, CERT_OBJECTIVES, CERT_BASIS, CERT_PRICING = 1, 2, 4, 8, 16, 32
@@ -116,6 +116,14 @@ class McfRhsReport(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class McfArcsReport(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "first_index", "m", "eligible", "bigm_grew", "shifted_only")] + [("device_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def _int128(v) -> int:
     return (int(v[0]) << 64) + (int(v[1]) & ((1 << 64) - 1))
 
@@ -175,6 +183,7 @@ def load_library():
     lib.mcf_set_basis.argtypes = [vp, i8p, i8p]
     lib.mcf_update_costs.argtypes = [vp, ctypes.c_int64, i64p, i64p]
     lib.mcf_update_rhs.argtypes = [vp, ctypes.c_int64, i64p, i64p, ctypes.c_int64, i64p, i64p, ctypes.POINTER(McfRhsReport)]
+    lib.mcf_add_arcs.argtypes = [vp, ctypes.c_int64, i32p, i32p, i64p, i64p, i8p, ctypes.POINTER(McfArcsReport)]
     lib.mcf_enqueue_price.argtypes = [vp, vp, vp]
     lib.mcf_enqueue_pivot.argtypes = [vp, vp, vp, ctypes.c_int32]
     lib.mcf_shard_info.argtypes = [vp, i32p, i32p]
@@ -422,6 +431,37 @@ class McfEngine:
                 self._rhs_private = True
             self.supply[nd] = sv           # (numpy assigns in order: the last entry wins here too)
             self.cap[ar] = cv
+        return rep.as_dict()
+
+    def add_arcs(self, tail, head, cost, cap, priority=None) -> dict:
+        """Add the arcs ``tail[i] -> head[i]`` with integer ``cost[i]`` and ``cap[i]`` (negative: uncapacitated) to the resident
+        handle (``mcf_add_arcs``); ``priority``: one byte per new arc for ``key_mode`` KEY_PRIORITY.  New arc ``i`` gets the
+        index ``m + i``.  The device-resident basis stays -- the new arcs enter non-basic at their lower bound -- and the next
+        ``solve()`` goes on pivoting from it.  Returns the fields of ``mcf_arcs_report``."""
+        t = np.ascontiguousarray(tail, dtype=np.int32).reshape(-1)
+        hd = np.ascontiguousarray(head, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(cost, dtype=np.int64).reshape(-1)
+        cp = np.ascontiguousarray(cap, dtype=np.int64).reshape(-1)
+        k = int(t.shape[0])
+        if not (hd.shape[0] == c.shape[0] == cp.shape[0] == k):
+            raise ValueError("arc arrays differ in length")
+        pr = None
+        if priority is not None:
+            pr = np.ascontiguousarray(priority, dtype=np.int8).reshape(-1)
+            if pr.shape[0] != k:
+                raise ValueError("priority needs one byte per new arc")
+        rep = McfArcsReport()
+        self._check(self._lib.mcf_add_arcs(self._h, k, _p(t, ctypes.c_int32), _p(hd, ctypes.c_int32), _p(c, ctypes.c_int64),
+                                           _p(cp, ctypes.c_int64), None if pr is None or k == 0 else _p(pr, ctypes.c_int8),
+                                           ctypes.byref(rep)))
+        if k:
+            self.tail, self.head = np.concatenate([self.tail, t]), np.concatenate([self.head, hd])
+            self.cost, self.cap = np.concatenate([self.cost, c]), np.concatenate([self.cap, cp])
+            self._cost_private = True   # (the concatenation is this object's own; supplies are untouched, and update_rhs copies
+                                        #  supplies and capacities together on their first change)
+            if self._arc_priority is not None:
+                self._arc_priority = np.concatenate([self._arc_priority, pr if pr is not None else np.zeros(k, np.int8)])
+            self.m += k
         return rep.as_dict()
 
     def last_error(self) -> str:

@@ -363,6 +363,122 @@ def map_rhs_changes(flat: FlatProblem, supplies, capacities, tolerance: float):
     return s_idx, s_int, s_val, c_idx, c_int, c_val
 
 
+def map_arc_additions(flat: FlatProblem, arcs, tolerance: float, directed: bool = True) -> dict:
+    """New arcs in the caller's terms -> the engine's arrays, by flatten's own per-arc transformation: cost and flow scales of
+    the resident instance, the lower-bound shift (simplex.py:403-428), the undirected expansion (data.py:162-223).  Pure:
+    neither ``flat`` nor ``arcs`` is modified.
+
+    * object-model problems: ``arcs`` is an iterable of the dicts ``build_problem`` takes (``tail``, ``head``, ``capacity``,
+      ``cost``, ``lower``); with ``directed=False`` every one is an undirected edge.
+    * ``SoAProblem``: ``arcs`` is ``(tail, head, cost, capacity[, lower])`` of integer arrays, 0-based nodes, a negative
+      capacity meaning none.
+
+    Returns ``tail`` / ``head`` (int32 node indices), ``cost`` / ``cap`` (int64, engine units; cap -1 = none), ``lower`` and
+    ``orig_cost`` (caller units), ``keys`` (tail id, head id) and ``supply_nodes`` / ``supply_values``: the nodes whose engine
+    supply the new lower bounds shift, with their new engine supplies.  Refusals carry the reference's wording where it has
+    one (capacity below lower bound, unknown node, self-loop), and the "not a multiple of 1/..." message of the other update
+    calls for a value off the instance's scale; nothing is returned then."""
+    n = len(flat.node_ids)
+    if flat.soa:
+        try:
+            if hasattr(arcs, "items") or not 4 <= len(arcs) <= 5:
+                raise TypeError
+            parts = [np.asarray(a).reshape(-1) for a in arcs]
+        except TypeError:
+            raise InvalidProblemError("new arcs of an SoAProblem are (tail, head, cost, capacity[, lower]) arrays") from None
+        k = parts[0].shape[0]
+        if any(a.shape[0] != k for a in parts):
+            raise InvalidProblemError("Arc arrays differ in length.")
+        if k and not all(np.issubdtype(a.dtype, np.integer) for a in parts):
+            raise InvalidProblemError("new arcs of an SoAProblem are integer arrays")
+        tail, head, cost, capacity = (a.astype(np.int64) for a in parts[:4])
+        lower = parts[4].astype(np.int64) if len(parts) == 5 else np.zeros(k, dtype=np.int64)
+        bad = (tail < 0) | (tail >= n) | (head < 0) | (head >= n)
+        if bad.any():
+            i = int(np.nonzero(bad)[0][0])
+            raise InvalidProblemError(f"Arc tail '{int(tail[i]) + 1}' or head '{int(head[i]) + 1}' not found in node set. "
+                                      f"All arc endpoints must reference existing nodes.")
+        if (tail == head).any():
+            i = int(np.nonzero(tail == head)[0][0])
+            raise InvalidProblemError(f"Self-loop detected on node '{int(tail[i]) + 1}'. Self-loops are not supported in network simplex.")
+        finite = capacity >= 0
+        width = capacity - lower
+        if (finite & (width < 0)).any():
+            i = int(np.nonzero(finite & (width < 0))[0][0])
+            raise InvalidProblemError(f"Arc capacity ({capacity[i]}) is less than lower bound ({lower[i]}) for arc "
+                                      f"{int(tail[i]) + 1} -> {int(head[i]) + 1}. Capacity must be >= lower bound.")
+        if k and (np.abs(cost).max() >= 2 ** 31 or width[finite].max(initial=0) >= 2 ** 60):
+            raise SolverConfigurationError("costs must fit int32 and capacities int60")
+        cap_i = np.where(finite, width, -1).astype(np.int64)
+        cost_i, lower_f, cost_f, shift_i = cost, lower.astype(np.float64), cost.astype(np.float64), lower
+        keys = [(str(int(t) + 1), str(int(h) + 1)) for t, h in zip(tail.tolist(), head.tolist())]
+    else:
+        from .data import Arc
+        index = {nid: i for i, nid in enumerate(flat.node_ids)}
+        made = []
+        for a in arcs:
+            cap = a.get("capacity")
+            arc = Arc(tail=str(a["tail"]), head=str(a["head"]), capacity=None if cap is None else float(cap),
+                      cost=float(a.get("cost", 0.0)), lower=float(a.get("lower", 0.0)))       # (refuses self-loops and capacity < lower)
+            for end, label in ((arc.tail, "tail"), (arc.head, "head")):
+                if end not in index:
+                    raise InvalidProblemError(f"Arc {label} '{end}' not found in node set. All arc endpoints must reference "
+                                              f"existing nodes.")
+            if not directed:                                           # data.py:162-223
+                if arc.capacity is None:
+                    raise InvalidProblemError(f"Undirected edge {arc.tail} -- {arc.head} has infinite capacity. Undirected graphs "
+                                              f"require finite capacity on all edges.")
+                c = float(arc.capacity)
+                if abs(arc.lower) > 1e-12 and not math.isclose(arc.lower, -c, rel_tol=0.0, abs_tol=1e-12):
+                    raise InvalidProblemError(f"Undirected edge {arc.tail} -- {arc.head} has custom lower bound ({arc.lower}). "
+                                              f"Undirected edges do not support custom lower bounds.")
+                arc = Arc(tail=arc.tail, head=arc.head, capacity=c, cost=arc.cost, lower=-c)
+            made.append(arc)
+        k = len(made)
+        keys = [(a.tail, a.head) for a in made]
+        tail = np.fromiter((index[a.tail] for a in made), dtype=np.int64, count=k)
+        head = np.fromiter((index[a.head] for a in made), dtype=np.int64, count=k)
+        cost_f = np.fromiter((a.cost for a in made), dtype=np.float64, count=k)
+        lower_f = np.fromiter((a.lower for a in made), dtype=np.float64, count=k)
+        upper = np.full(k, math.inf)
+        for i, a in enumerate(made):                                   # simplex.py:399-412
+            if a.capacity is not None:
+                u = float(a.capacity) - a.lower
+                if u < -tolerance:
+                    raise InvalidProblemError(f"Arc capacity ({a.capacity}) is less than lower bound ({a.lower}) for arc "
+                                              f"{a.tail} -> {a.head}. Capacity must be >= lower bound.")
+                upper[i] = max(0.0, u)
+        if not (np.all(np.isfinite(cost_f)) and np.all(np.isfinite(lower_f)) and not np.isnan(upper).any()):
+            raise InvalidProblemError("costs, capacities and lower bounds must be finite numbers")
+
+        def to_int(values, scale, what, unit):
+            scaled = values * float(scale)
+            rounded = np.round(scaled)
+            off = np.abs(scaled - rounded) > tolerance * scale
+            if off.any():
+                i = int(np.nonzero(off)[0][0])
+                raise InvalidProblemError(f"new {what} {values[i]} of arc {keys[i]} is not a multiple of 1/{scale}, the {unit} "
+                                          f"resolution this solver was built with; build a new solver for finer {what}s")
+            return rounded.astype(np.int64)
+
+        cost_i = to_int(cost_f, flat.cost_scale, "cost", "cost")
+        finite = np.isfinite(upper)
+        cap_i = np.full(k, -1, dtype=np.int64)
+        cap_i[finite] = to_int(upper[finite], flat.flow_scale, "capacity", "flow") if finite.any() else 0
+        shift_i = to_int(lower_f, flat.flow_scale, "lower bound", "flow")
+        if k and (np.abs(cost_i).max() >= 2 ** 31 or cap_i.max() >= 2 ** 60):
+            raise SolverConfigurationError("scaled costs must fit int32 and scaled capacities int60")
+    # the lower-bound shift of the supplies (simplex.py:413-415), per node
+    delta = np.zeros(n, dtype=np.int64)
+    if k and shift_i.any():
+        np.subtract.at(delta, tail, shift_i)
+        np.add.at(delta, head, shift_i)
+    nodes = np.nonzero(delta)[0].astype(np.int64)
+    return {"tail": tail.astype(np.int32), "head": head.astype(np.int32), "cost": cost_i.astype(np.int64), "cap": cap_i,
+            "lower": lower_f, "orig_cost": cost_f, "keys": keys, "supply_nodes": nodes,
+            "supply_values": (flat.supply[nodes] + delta[nodes]).astype(np.int64)}
+
+
 @dataclass
 class Certificate:
     """What ``NetworkSimplex.certify()`` returns; ``raw`` holds every field of ``mcf_certificate``."""
@@ -430,10 +546,12 @@ class NetworkSimplex:
             self.logger.info(f"Using specialized pivot strategy for {self.network_structure.network_type.value}")
         bs = self.options.block_size
         block_size = 0 if bs is None or isinstance(bs, str) else int(bs)
+        self._engine_kwargs = dict(rule=self.pricing_rule, block_size=block_size, batch_pivots=batch_pivots, use_graph=use_graph,
+                                   device=device, **(special or {}), **(engine_options or {}))
+        self._arc_order_map = None   # flat arc j -> index into problem.arcs, once add_arcs has appended arcs (None: flatten's sort)
         self.engine = _engine.McfEngine(
             len(self.flat.node_ids), self.flat.tail, self.flat.head, self.flat.cost, self.flat.cap,
-            self.flat.supply, rule=self.pricing_rule, block_size=block_size, batch_pivots=batch_pivots,
-            use_graph=use_graph, device=device, **(special or {}), **(engine_options or {}))
+            self.flat.supply, **self._engine_kwargs)
         self.stats: dict = {}
         self._pivots_seen = 0   # the engine's cumulative pivot count when the last solve() returned
 
@@ -529,8 +647,7 @@ class NetworkSimplex:
             orig_cost = f.orig_cost.copy()
             orig_cost[idx] = cost_f
             arcs = list(self.problem.arcs)
-            # flat arc j is arc order[j] of the problem (flatten_problem: a stable sort by key)
-            order = sorted(range(len(arcs)), key=lambda i: (arcs[i].tail, arcs[i].head))
+            order = self._arc_order()
             for j, c in zip(idx.tolist(), cost_f.tolist()):
                 arcs[order[j]] = replace(arcs[order[j]], cost=c)
             self.problem = replace(self.problem, nodes=dict(self.problem.nodes), arcs=arcs)
@@ -561,8 +678,7 @@ class NetworkSimplex:
                 nodes[nid] = replace(nodes[nid], supply=v)
             arcs = list(self.problem.arcs)
             if c_idx.size:
-                # flat arc j is arc order[j] of the problem (flatten_problem: a stable sort by key)
-                order = sorted(range(len(arcs)), key=lambda i: (arcs[i].tail, arcs[i].head))
+                order = self._arc_order()
                 for j, c in zip(c_idx.tolist(), c_val.tolist()):
                     arcs[order[j]] = replace(arcs[order[j]], capacity=None if math.isnan(c) else c)
             self.problem = replace(self.problem, nodes=nodes, arcs=arcs)
@@ -582,6 +698,118 @@ class NetworkSimplex:
         """Change arc capacities and keep the solved state, as ``update_supplies`` does.  ``changes``: ``{(tail, head):
         capacity or None}`` for an object-model problem, ``(indices, capacities)`` (negative: none) for an ``SoAProblem``."""
         return self._update_rhs(None, changes)
+
+    def _arc_order(self) -> list[int]:
+        """flat arc j is arc order[j] of the problem: flatten_problem's stable sort by key, then the arcs ``add_arcs`` appended."""
+        if self._arc_order_map is not None:
+            return self._arc_order_map
+        arcs = self.problem.arcs
+        return sorted(range(len(arcs)), key=lambda i: (arcs[i].tail, arcs[i].head))
+
+    def add_arcs(self, arcs) -> dict:
+        """Add arcs and keep the solved state (``mcf_add_arcs``): the new arcs enter non-basic at their lower bound, the basis
+        that is resident on the device stays, and the next ``solve()`` goes on pivoting from it.  ``arcs``: the dicts
+        ``build_problem`` takes for an object-model problem, ``(tail, head, cost, capacity[, lower])`` arrays for an
+        ``SoAProblem`` (``map_arc_additions``; on an invalid arc nothing is changed).  New arcs with a lower bound send their
+        supply shift through ``mcf_update_rhs`` in the same call.  The flat problem and ``self.problem`` (an extended copy:
+        the caller's object is left alone) grow by the new arcs, appended in the given order, so that results, ``certify()``
+        and later keyed updates see them.  Returns ``path`` (0 = resident re-layout; 2 = a new handle on the extended
+        instance warm-started from the resident basis, taken when the handle's engine path cannot hold the grown instance),
+        ``first_index``, ``count``, ``eligible`` and ``device_ms``."""
+        f = self.flat
+        add = map_arc_additions(f, arcs, self.tolerance, directed=bool(self.problem.directed))
+        k = int(add["tail"].shape[0])
+        first = len(f.keys)
+        tail, head = np.concatenate([f.tail, add["tail"]]).astype(np.int32), np.concatenate([f.head, add["head"]]).astype(np.int32)
+        cost, cap = np.concatenate([f.cost, add["cost"]]).astype(np.int64), np.concatenate([f.cap, add["cap"]]).astype(np.int64)
+        report = {"path": 0, "first_index": first, "count": k, "eligible": 0, "device_ms": 0.0}
+        try:
+            rep = self.engine.add_arcs(add["tail"], add["head"], add["cost"], add["cap"])
+            report["eligible"], report["device_ms"] = int(rep["eligible"]), float(rep["device_ms"])
+        except _engine.EngineError as exc:
+            if exc.code != -6:
+                raise
+            # the handle's engine path cannot hold the grown instance: a new handle, warm-started from the resident basis
+            self.logger.info(f"{exc}; building a new handle on the extended instance")
+            res = self.engine.result()
+            rc_new = add["cost"] + res.potential[add["tail"]] - res.potential[add["head"]]
+            kwargs = dict(self._engine_kwargs)
+            if kwargs.get("arc_priority") is not None:
+                kwargs["arc_priority"] = np.concatenate([np.asarray(kwargs["arc_priority"], np.int8), np.zeros(k, np.int8)])
+            new_engine = _engine.McfEngine(len(f.node_ids), tail, head, cost, cap, f.supply, **kwargs)
+            in_tree = np.concatenate([res.in_tree, np.zeros(k, bool)])
+            at_upper = np.concatenate([~res.in_tree & (f.cap > 0) & (res.flow == f.cap), np.zeros(k, bool)])
+            if in_tree.any():
+                new_engine.set_basis(in_tree, at_upper)
+            self.engine.close()
+            self.engine = new_engine
+            self._engine_kwargs = kwargs
+            self._pivots_seen = 0
+            report["path"], report["eligible"] = 2, int((rc_new < 0).sum())
+        # the engine holds the arcs from here on: the flat problem and the problem follow at once, the supply shift of new lower
+        # bounds after them -- should the engine refuse it, indices and keys still agree with what the engine holds
+        supply = f.supply
+        lower, orig_cost = np.concatenate([f.lower, add["lower"]]), np.concatenate([f.orig_cost, add["orig_cost"]])
+        if f.soa:
+            problem = copy.copy(self.problem)
+            p = self.problem
+            problem.tail, problem.head = tail, head
+            problem.cost = np.concatenate([p.cost, add["orig_cost"].astype(p.cost.dtype)])
+            problem.capacity = np.concatenate([p.capacity, np.where(add["cap"] < 0, -1, add["cap"] + add["lower"].astype(np.int64)).astype(p.capacity.dtype)])
+            problem.lower = np.concatenate([p.lower, add["lower"].astype(p.lower.dtype)])
+            problem._arcs = None
+            self.problem = problem
+            self.flat = replace(f, keys=_KeySeq(tail, head), tail=tail, head=head, cost=cost, cap=cap, supply=supply, lower=lower,
+                                orig_cost=orig_cost)
+        else:
+            from .data import Arc
+            old = list(self.problem.arcs)
+            self._arc_order_map = self._arc_order() + list(range(len(old), len(old) + k))
+            scale = float(f.flow_scale)
+            new = [Arc(tail=t, head=h, capacity=None if cp < 0 else cp / scale + lo, cost=c, lower=lo)
+                   for (t, h), cp, c, lo in zip(add["keys"], add["cap"].tolist(), add["orig_cost"].tolist(), add["lower"].tolist())]
+            if not self.problem.directed:      # an undirected edge is stored with its capacity alone, as the caller wrote it
+                new = [replace(a, lower=0.0) for a in new]
+            self.problem = replace(self.problem, nodes=dict(self.problem.nodes), arcs=old + new)
+            self.flat = replace(f, keys=list(f.keys) + list(add["keys"]), tail=tail, head=head, cost=cost, cap=cap, supply=supply,
+                                lower=lower, orig_cost=orig_cost)
+        self.actual_arc_count = len(self.flat.keys)
+        if add["supply_nodes"].size:
+            self.engine.update_rhs(add["supply_nodes"], add["supply_values"])
+            supply = f.supply.copy()
+            supply[add["supply_nodes"]] = add["supply_values"]
+            self.flat = replace(self.flat, supply=supply)
+        return report
+
+    def close_arcs(self, keys) -> dict:
+        """Close arcs and keep the solved state: capacity 0 through ``update_capacities`` (``mcf_update_rhs``); the arcs stay in
+        the problem and every index stays what it was.  ``keys``: ``(tail, head)`` keys for an object-model problem (of
+        parallel arcs the last one, as for every keyed update), arc indices for an ``SoAProblem``.  An arc with a positive
+        lower bound cannot be closed: ``InvalidProblemError``.  Nor can an edge of an undirected problem: it lives in the resident
+        instance as one arc with the bounds [-C, C] shifted to [0, 2C], and that shift (the lower bound -C) is fixed when the
+        arc is created, so no capacity of the shifted arc means "no flow either way"; it is refused the same way."""
+        f = self.flat
+        if f.soa:
+            idx = np.asarray(keys, dtype=np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= len(f.keys)):
+                raise InvalidProblemError(f"capacity changes: index outside [0, {len(f.keys)})")
+            changes = (idx, np.zeros(idx.shape[0], dtype=np.int64))
+        else:
+            last = {key: i for i, key in enumerate(f.keys)}
+            idx = []
+            for key in keys:
+                if tuple(key) not in last:
+                    raise InvalidProblemError(f"capacity change names arc {tuple(key)} which is not in the problem")
+                idx.append(last[tuple(key)])
+            idx = np.asarray(idx, dtype=np.int64)
+            changes = {tuple(key): 0.0 for key in keys}
+        bound = idx[f.lower[idx] != 0] if idx.size else idx
+        if bound.size:
+            t, h = f.keys[int(bound[0])]
+            lo = float(f.lower[int(bound[0])])
+            what = f"has the lower bound {lo:g}" if lo > 0 else f"is an undirected edge (bounds shifted by {-lo:g})"
+            raise InvalidProblemError(f"arc {t} -> {h} {what} and cannot be closed")
+        return self.update_capacities(changes)
 
     def certify(self) -> "Certificate":
         """Certify the state resident on the device -- conservation, bounds, complementary slackness, exact objectives,
