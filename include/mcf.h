@@ -30,6 +30,8 @@
  *       near capacity of a solution; the reference checks nothing on the dual side) ......  mcf_certify / mcf_bottlenecks
  *   UnboundedProblemError / status "infeasible" carry no witness in the reference (exceptions.py:65-93 names the entering
  *       arc, simplex.py:1600-1624 returns an empty flow): the ray and the cut that prove them ...  mcf_certify_ray / mcf_certify_cut
+ *   "what if this cost changes": the reference answers by one re-solve per what-if (examples/sensitivity_analysis_example.py,
+ *       examples/warm_start_example.py); the ranges inside which no re-solve pivots, for all arcs at once ...  mcf_cost_ranges
  *   AdaptiveTuner.adapt_block_size  simplex_adaptive.py:98-151 and the
  *       periodic Devex reset  simplex.py:1370-1400 ..........................  inside mcf_solve (MCF_RULE_DEVEX_BLOCK)
  *   specialised pivot strategies  specialized_pivots.py:69-424, 452-527 .....  mcf_options.key_mode (+ arc_priority): row scan,
@@ -583,6 +585,60 @@ typedef struct mcf_cut {
 
 int mcf_certify_cut(mcf_handle* h, const int8_t* in_S /* [n] caller's set, or NULL = compute from the resident flow */,
                     int8_t* S_out /* [n] or NULL */, mcf_cut* out);
+
+/* ---- cost ranging on the resident basis: how far may ONE arc's cost move before the basis the handle holds stops being
+ * optimal?  The question before a mcf_update_costs: an edit inside the range re-solves in zero pivots.  Answered for all arcs
+ * at once, on the device, from the arrays that are already there; nothing is tried and nothing is changed.
+ *
+ *   definition   exact signed integers.  rc[f] = cost[f] + pi[tail f] - pi[head f] is gathered from the resident potentials on
+ *                every call (the resident reduced-cost copies and key codes are not read, so handles that dropped them,
+ *                no_rcache handles and shards answer alike).  The slack of a NON-BASIC arc is s[f] = state[f] * rc[f]; the
+ *                engine prices f in exactly when s[f] < 0.
+ *                  non-basic at its lower bound (state +1):  down = s,  up = MCF_RANGE_INF
+ *                  non-basic at its capacity    (state -1):  down = MCF_RANGE_INF,  up = s
+ *                  basic arc e with child end v, S = the subtree of v: over the non-basic real arcs with exactly one end in S
+ *                      P[v] = min( s[f] : tail f in S, state -1 ;  s[f] : head f in S, state +1 )
+ *                      N[v] = min( s[f] : tail f in S, state +1 ;  s[f] : head f in S, state -1 )
+ *                    (an empty set gives MCF_RANGE_INF), and  up = N, down = P  when v is the tail of e,  up = P, down = N
+ *                    when v is its head: raising cost[e] by d moves the potentials of S by -d / +d, an arc with its tail in S
+ *                    sees rc + that shift, one with its head in S rc - it.
+ *                Artificial arcs have no range: those that left the basis are never priced and constrain nothing, those in
+ *                the tree have no caller's cost (they still lie on other arcs' paths).
+ *   contract     on an optimal handle, any single change cost[e] -> c with cost[e] - down[e] <= c <= cost[e] + up[e] leaves no
+ *                eligible arc: mcf_solve makes 0 pivots.  One unit past a finite end makes the arc(s) that attain it eligible,
+ *                with violation 1.  RANGES ARE STATED AT FIXED BIG-M: a new cost that makes mcf_update_costs raise
+ *                big-M (|c| + 1) * (n + 2) > big_m moves the potentials below artificial tree arcs as well, which this call
+ *                does not follow; report.big_m is the value the answer holds for.  The numeric domain |cost| <= INT32_MAX is
+ *                a separate limit and is not folded in either: an end may lie outside it.
+ *   negative     slacks are not clamped.  On a basis that is not optimal (mid-solve, after an edit, a planted basis) a
+ *                negative entry comes through as it is and means "this side of the range is already empty": the arc, or an
+ *                arc across its cut, prices in as things stand.  report.eligible counts the non-basic arcs with s < 0.
+ *   arc, count   caller's indices, duplicates allowed, down[i] / up[i] answer arc[i]; count < 0 with arc == NULL = all m arcs
+ *                in the caller's order.  With a list only `count` entries cross the bus.
+ *   method       binary lifting over parent pointers, O((n + m) log depth) whatever the shape of the tree and the same on
+ *                both tree layouts: the greatest depth is reduced first (one word comes back: K = max(1, bit_length) levels),
+ *                ancestor tables anc[k][v] are built level by level, every non-basic arc lowers one table cell per jump of its
+ *                two tree paths (64-bit atomic min, skipped where the cell is already low enough), and the levels are pushed
+ *                down into one value per tree arc.  Integer mins only: no launch geometry or merge order changes a bit.
+ *   read-only    exactly as mcf_certify: nothing the solver reads is written and a later mcf_solve makes the same pivots.
+ *                Valid between solves in any state of the handle, on every engine path, both tree layouts, every rule and
+ *                key_mode, handles that dropped their resident reduced costs, and handles with shard_count > 1 (the state is
+ *                replicated).  m == 0 or n == 1: MCF_OK with an empty answer.
+ *   errors       MCF_E_BAD_ARG, all checked before any device work: null handle; null down / up with entries to return; count
+ *                > 0 with a null list or count < 0 with one; an index outside [0, m).  MCF_E_ALLOC: the tables cannot be
+ *                allocated; the handle is untouched.
+ * Scratch -- the tables, 20 B x K x (n + 1), the answer, 16 B x m, the list -- is allocated on first use, released and
+ * allocated again when K or m outgrew it, and freed by mcf_destroy. */
+#define MCF_RANGE_INF INT64_MAX
+typedef struct mcf_ranges_report {
+    int64_t basic_real, basic_artificial, eligible;   /* eligible == 0 <=> no arc prices in */
+    int64_t max_depth, levels;                        /* greatest depth of the tree; K */
+    int64_t inf_down, inf_up;                         /* entries equal to MCF_RANGE_INF among those returned */
+    int64_t big_m;                                    /* the big-M the ranges are stated at */
+    double  device_ms;                                /* HIP events round the device passes (the depth pass and the rest) */
+} mcf_ranges_report;
+int mcf_cost_ranges(mcf_handle* h, int64_t count, const int64_t* arc /* caller's indices; count < 0 and NULL = all m */,
+                    int64_t* down, int64_t* up, mcf_ranges_report* out /* may be NULL */);
 
 /* ---- arc-sharded multi-GPU pivoting: one handle per rank, every rank holds the full
  * replicated state and prices only its shard (options.shard_rank / shard_count).  Per pivot:

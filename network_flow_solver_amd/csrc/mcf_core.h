@@ -2135,3 +2135,80 @@ MCF_HD int64_t mcf_topo_adj_off(int64_t old_off, int64_t u, const int64_t* ep_no
 // ... old entry p moves up by the new end points appended to lists that end at or before it (ep_end[j] = old end of the list
 // of end point j's node, ascending with j), and end point j lands at ep_end[j] + j
 MCF_HD int64_t mcf_topo_adj_index(int64_t p, const int64_t* ep_end, int64_t k2) { return p + mcf_count_upto(ep_end, k2, p); }
+
+// ====================================================================== cost ranging on the resident basis (mcf_cost_ranges, include/mcf.h)
+// How far may one arc's cost move before the basis stops being optimal?  A non-basic arc's answer is its own slack; a basic
+// arc's is a minimum over the non-basic arcs that cross its fundamental cut.  A non-basic arc f = (a, b) crosses the cut of
+// exactly the tree arcs on the two paths a -> join and b -> join, so all n answers together are "lower a value along a tree
+// path", once per non-basic arc.  With binary lifting (anc[k][v] = the ancestor 2^k above v, the root its own ancestor) a
+// path is O(log depth) jumps, each recorded by ONE min into a table cell t[k][x] that stands for the tree arcs of x and its
+// next 2^k - 1 ancestors; afterwards level k is pushed into the two halves of level k - 1 until level 0 holds one value per
+// tree arc.  Only integer mins are involved: no launch geometry and no merge order can change a bit of the result.  As for
+// the certificate, the per-arc / per-node logic lives here, shared by the kernels (mcf_passes_dev.h: k_rng_*) and the host
+// restatement of the CPU tests (csrc/mcf_ranges_host.cpp).
+#define MCF_RNG_INF INT64_MAX    // "no arc limits this side" (MCF_RANGE_INF of include/mcf.h)
+#define MCF_RNG_MAX_LEVELS 31    // depths are below 2^31
+
+struct McfRngDepthAcc { int64_t depth; };   // greatest McfNode::depth seen
+MCF_HD void mcf_acc_init(McfRngDepthAcc* a) { a->depth = 0; }
+MCF_HD void mcf_acc_merge(McfRngDepthAcc* a, const McfRngDepthAcc& b) { if (b.depth > a->depth) a->depth = b.depth; }
+
+// levels of the tables: K = max(1, bit_length(greatest depth)), so that every depth difference is a sum of jumps below 2^K
+MCF_HD int mcf_rng_levels(int64_t max_depth) {
+    int k = 0;
+    while (k < MCF_RNG_MAX_LEVELS && (max_depth >> k) != 0) ++k;
+    return k < 1 ? 1 : k;
+}
+
+// slack of a non-basic arc: the engine prices it in exactly when this is < 0 (mcf_violation is its negative).  Not clamped.
+MCF_HD int64_t mcf_rng_slack(int32_t state, int64_t rc) { return (int64_t)state * rc; }
+
+// Which minimum an arc of state `state` lowers on the tree arcs below the end point it was climbed from: 0 = P, 1 = N.
+//   P[v] = min(s[f] : tail f in S(v), state -1;  s[f] : head f in S(v), state +1)
+//   N[v] = min(s[f] : tail f in S(v), state +1;  s[f] : head f in S(v), state -1)
+MCF_HD int mcf_rng_table(int32_t state, bool tail_side) { return (state > 0) == tail_side ? 1 : 0; }
+
+// The jumps that cover the two tree paths a -> join and b -> join (da, db: depths; anc(k, x): the ancestor 2^k above x, the
+// root for anything at or past it).  emit(side, k, x): side 0 = a's path, 1 = b's.  The deeper end is lifted by the set bits
+// of the depth difference; then both ends jump together while their ancestors differ, and make one level-0 jump each.
+template <typename Anc, typename Emit>
+MCF_HD void mcf_rng_jumps(int32_t a, int32_t da, int32_t b, int32_t db, int K, Anc anc, Emit emit) {
+    if (da > db) {
+        const int32_t diff = da - db;
+        for (int k = 0; k < K; ++k) if ((diff >> k) & 1) { emit(0, k, a); a = anc(k, a); }
+    } else if (db > da) {
+        const int32_t diff = db - da;
+        for (int k = 0; k < K; ++k) if ((diff >> k) & 1) { emit(1, k, b); b = anc(k, b); }
+    }
+    if (a == b) return;
+    for (int k = K - 1; k >= 0; --k) {
+        const int32_t na = anc(k, a), nb = anc(k, b);
+        if (na == nb) continue;
+        emit(0, k, a); emit(1, k, b);
+        a = na; b = nb;
+    }
+    emit(0, 0, a); emit(1, 0, b);
+}
+
+// lower a table cell to s: the cell is read first and the atomic skipped when it already holds a value <= s (cells only ever
+// fall, so a stale read can only cost an atomic that changes nothing)
+MCF_HD void mcf_rng_lower(int64_t* cell, int64_t s) {
+    if (*cell > s) MCF_ATOMIC_MIN64(cell, s);
+}
+
+// push step, level k -> k - 1: the value of t[k][x] belongs to t[k-1][x] and to t[k-1][anc[k-1][x]]
+MCF_HD void mcf_rng_push(int64_t val, int64_t* lower_own, int64_t* lower_anc) {
+    if (val == MCF_RNG_INF) return;
+    mcf_rng_lower(lower_own, val);
+    mcf_rng_lower(lower_anc, val);
+}
+
+// the pair of a non-basic arc: at its lower bound the cost may fall by s and rise for ever, at capacity the other way round
+MCF_HD void mcf_rng_nonbasic(int32_t state, int64_t s, int64_t* down, int64_t* up) {
+    if (state > 0) { *down = s; *up = MCF_RNG_INF; } else { *down = MCF_RNG_INF; *up = s; }
+}
+// the pair of the basic arc of child end v from P[v], N[v]; child_is_tail = pred & 1.  Raising the cost by d shifts the
+// potentials of S(v) by -d when the child is the arc's tail, by +d when it is its head.
+MCF_HD void mcf_rng_basic(bool child_is_tail, int64_t P, int64_t N, int64_t* down, int64_t* up) {
+    if (child_is_tail) { *up = N; *down = P; } else { *up = P; *down = N; }
+}

@@ -2012,6 +2012,16 @@ struct mcf_handle {
     mcf_u128* d_rhs_bal = nullptr;                         // [n_nodes] balance per preorder position, then its prefix sums
     mcf_u128* d_rhs_part = nullptr;                        // per chunk of positions
     unsigned long long* d_rhs_info = nullptr;              // [RHS_COUNTERS]
+    // mcf_cost_ranges: everything allocated on first use (events are the certificate's)
+    McfRngDepthAcc* d_rng_part = nullptr;                  // [kCertMaxBlocks + 1] per-workgroup partials, then the total
+    unsigned long long* d_rng_info = nullptr;              // [RNG_COUNTERS]
+    int32_t* d_rng_anc = nullptr;                          // [levels][n_nodes] binary-lifting ancestors
+    int64_t *d_rng_p = nullptr, *d_rng_n = nullptr;        // [levels][n_nodes] the two min tables
+    int64_t rng_cells = 0;                                 // levels * n_nodes the three tables hold
+    int64_t *d_rng_down = nullptr, *d_rng_up = nullptr;    // [m] the answer in the caller's order
+    int64_t rng_arcs = 0;                                  // entries the two arrays hold
+    int64_t *d_rng_idx = nullptr, *d_rng_gdown = nullptr, *d_rng_gup = nullptr;   // an index list and its gathered answer
+    int64_t rng_list = 0;                                  // entries the three arrays hold
 };
 
 namespace {
@@ -2457,6 +2467,8 @@ void free_all(mcf_handle* h) {
     (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost); (void)hipFree(h->d_uc_jump[0]); (void)hipFree(h->d_uc_jump[1]); (void)hipFree(h->d_uc_info);
     (void)hipFree(h->d_ray_part); (void)hipFree(h->d_ray_idx); (void)hipFree(h->d_cut_mark); (void)hipFree(h->d_cut_level); (void)hipFree(h->d_cut_byte); (void)hipFree(h->d_cut_part);
     (void)hipFree(h->d_rhs_idx); (void)hipFree(h->d_rhs_val); (void)hipFree(h->d_rhs_bal); (void)hipFree(h->d_rhs_part); (void)hipFree(h->d_rhs_info);
+    (void)hipFree(h->d_rng_part); (void)hipFree(h->d_rng_info); (void)hipFree(h->d_rng_anc); (void)hipFree(h->d_rng_p); (void)hipFree(h->d_rng_n);
+    (void)hipFree(h->d_rng_down); (void)hipFree(h->d_rng_up); (void)hipFree(h->d_rng_idx); (void)hipFree(h->d_rng_gdown); (void)hipFree(h->d_rng_gup);
     if (h->h_ctx) pinned_give(reinterpret_cast<char*>(h->h_ctx));   // (h_one lives in the same slot)
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
 }

@@ -934,3 +934,137 @@ __global__ __launch_bounds__(kAaThreads) void k_aa_price(McfView v, const int64_
     const int32_t total = wave_block_sum(eligible, s);
     if (threadIdx.x == 0 && total > 0) atomicAdd(&info[1], (unsigned long long)total);
 }
+
+// ------------------------------------------------------------------ mcf_cost_ranges: cost ranging on the resident basis
+// Logic: mcf_core.h (mcf_rng_*).  Everything is indexed by node, nothing by preorder position: the dense array and the
+// blocked list need no separate code.  Bytes each pass moves (N = n + 1 nodes, m arcs, K levels, 20 B per node and level):
+//   k_rng_depth  one lane per node record (16 B): the greatest depth, reduced by block_reduce / k_final; the host reads that
+//                one word and sizes the tables with it;
+//   k_rng_anc    one launch per level: anc[k][v] = anc[k-1][anc[k-1][v]] (4 B read + 4 B gathered, 4 B written; level 0 reads
+//                the node record instead), and the level's two table rows set to "no arc" (16 B written);
+//   k_rng_arcs   one lane per engine arc, workgroup b on head bucket b % 8 like k_cert_arcs: state (1 B); for a non-basic arc
+//                tail, head, cost, orig (4 B each), two gathered potentials (8 B each), two gathered node records for the depths,
+//                its own pair written at the caller's index (16 B), and per jump one gathered ancestor (4 B), one table cell
+//                read (8 B) and an atomic min where the cell is still higher.  At most 3 K + 2 jumps per arc.  The pass is bound
+//                by its gathers, not by its streams: no non-temporal variant;
+//   k_rng_push   one launch per level K - 1 .. 1: one lane per node, both tables: 16 B read, 4 B ancestor, up to four cells
+//                read and lowered;
+//   k_rng_out    one lane per node: node record, level-0 cells (16 B), the tree arc's caller's index (4 B), 16 B written;
+//   k_rng_gather one lane per requested index: 8 B index, 16 B gathered, 16 B written.
+// Census by wave reduction, one atomic per wave and counter (rhs_count).
+constexpr int kRngThreads = kPassThreads;
+constexpr int kRngMaxBlocks = kCertMaxBlocks;                 // k_rng_arcs: at most 2 048 workgroups of 256 lanes, grid-stride beyond
+enum { RNG_ELIGIBLE = 0, RNG_BASIC_REAL = 1, RNG_BASIC_ART = 2, RNG_INF_DOWN = 3, RNG_INF_UP = 4, RNG_COUNTERS = 5 };
+
+struct RngArgs {
+    int32_t K;                // levels
+    int32_t count_inf;        // 1: the whole arrays are the answer, MCF_RNG_INF entries are counted as they are written
+    int32_t* anc;             // [K][n_nodes]
+    int64_t* tab[2];          // [K][n_nodes] each: 0 = P, 1 = N
+    int64_t *down, *up;       // [m] caller's order
+    unsigned long long* info; // [RNG_COUNTERS]
+};
+
+__global__ __launch_bounds__(kRngThreads) void k_rng_depth(const McfNode* __restrict__ node, int32_t n_nodes, McfRngDepthAcc* __restrict__ part) {
+    __shared__ McfRngDepthAcc s_wave[kPassWaves];
+    McfRngDepthAcc acc;
+    mcf_acc_init(&acc);
+    for (int32_t v = blockIdx.x * kRngThreads + threadIdx.x; v < n_nodes; v += gridDim.x * kRngThreads) {
+        const int64_t d = node[v].depth;
+        if (d > acc.depth) acc.depth = d;
+    }
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(kRngThreads) void k_rng_anc(const McfNode* __restrict__ node, int32_t n_nodes, int32_t k, RngArgs a) {
+    const int32_t root = n_nodes - 1;
+    const size_t row = (size_t)k * n_nodes;
+    const int32_t* __restrict__ below = k > 0 ? a.anc + row - n_nodes : nullptr;
+    for (int32_t v = blockIdx.x * kRngThreads + threadIdx.x; v < n_nodes; v += gridDim.x * kRngThreads) {
+        int32_t up;
+        if (k == 0) {
+            const int32_t p = node[v].parent;
+            up = (v == root || p < 0 || p >= n_nodes) ? root : p;
+        } else {
+            up = below[below[v]];
+        }
+        a.anc[row + v] = up;
+        a.tab[0][row + v] = MCF_RNG_INF;
+        a.tab[1][row + v] = MCF_RNG_INF;
+    }
+}
+
+__global__ __launch_bounds__(kRngThreads) void k_rng_arcs(McfView v, RngArgs a) {
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+    const int32_t N = v.n_nodes;
+    int32_t eligible = 0, inf_down = 0, inf_up = 0;
+    for (int64_t e = lo + lb * kRngThreads + threadIdx.x; e < hi; e += nlb * kRngThreads) {
+        const int32_t st = v.state[e];
+        if (st == 0) continue;   // basic arcs get their pair from the tables (k_rng_out); padding has none
+        const int32_t t = v.tail[e], hd = v.head[e];
+        const int64_t s = mcf_rng_slack(st, (int64_t)v.cost[e] + v.pi[t] - v.pi[hd]);
+        if (s < 0) ++eligible;
+        const int64_t o = v.orig[e];
+        int64_t dn, up;
+        mcf_rng_nonbasic(st, s, &dn, &up);
+        a.down[o] = dn; a.up[o] = up;
+        if (dn == MCF_RNG_INF) ++inf_down;
+        if (up == MCF_RNG_INF) ++inf_up;
+        mcf_rng_jumps(t, v.node[t].depth, hd, v.node[hd].depth, a.K,
+                      [&](int k, int32_t y) { return a.anc[(size_t)k * N + y]; },
+                      [&](int side, int k, int32_t y) { mcf_rng_lower(a.tab[mcf_rng_table(st, side == 0)] + (size_t)k * N + y, s); });
+    }
+    rhs_count(a.info, RNG_ELIGIBLE, eligible);
+    if (a.count_inf) { rhs_count(a.info, RNG_INF_DOWN, inf_down); rhs_count(a.info, RNG_INF_UP, inf_up); }
+}
+
+__global__ __launch_bounds__(kRngThreads) void k_rng_push(int32_t n_nodes, int32_t k, RngArgs a) {
+    const size_t row = (size_t)k * n_nodes, low = row - n_nodes;
+    for (int32_t y = blockIdx.x * kRngThreads + threadIdx.x; y < n_nodes; y += gridDim.x * kRngThreads) {
+        const int64_t p = a.tab[0][row + y], q = a.tab[1][row + y];
+        if (p == MCF_RNG_INF && q == MCF_RNG_INF) continue;
+        const int32_t up = a.anc[low + y];
+        mcf_rng_push(p, a.tab[0] + low + y, a.tab[0] + low + up);
+        mcf_rng_push(q, a.tab[1] + low + y, a.tab[1] + low + up);
+    }
+}
+
+__global__ __launch_bounds__(kRngThreads) void k_rng_out(McfView v, RngArgs a) {
+    const int32_t n = v.n_nodes - 1;
+    const int64_t m = v.m;
+    int32_t real = 0, art = 0, inf_down = 0, inf_up = 0;
+    for (int32_t u = blockIdx.x * kRngThreads + threadIdx.x; u < n; u += gridDim.x * kRngThreads) {
+        const int32_t pred = v.node[u].pred;
+        if (pred < 0) continue;
+        const int64_t arc = pred >> 1;
+        if (arc >= m) { ++art; continue; }   // an artificial tree arc has no caller's cost: the minima recorded on it are never read out
+        ++real;
+        int64_t dn, up;
+        mcf_rng_basic((pred & 1) != 0, a.tab[0][u], a.tab[1][u], &dn, &up);
+        const int64_t o = v.orig[arc];
+        a.down[o] = dn; a.up[o] = up;
+        if (dn == MCF_RNG_INF) ++inf_down;
+        if (up == MCF_RNG_INF) ++inf_up;
+    }
+    rhs_count(a.info, RNG_BASIC_REAL, real);
+    rhs_count(a.info, RNG_BASIC_ART, art);
+    if (a.count_inf) { rhs_count(a.info, RNG_INF_DOWN, inf_down); rhs_count(a.info, RNG_INF_UP, inf_up); }
+}
+
+__global__ __launch_bounds__(kRngThreads) void k_rng_gather(int64_t count, const int64_t* __restrict__ idx, const int64_t* __restrict__ down,
+                                                            const int64_t* __restrict__ up, int64_t* __restrict__ gdown, int64_t* __restrict__ gup,
+                                                            unsigned long long* __restrict__ info) {
+    int32_t inf_down = 0, inf_up = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kRngThreads + threadIdx.x; i < count; i += (int64_t)gridDim.x * kRngThreads) {
+        const int64_t o = idx[i];
+        const int64_t dn = down[o], u = up[o];
+        gdown[i] = dn; gup[i] = u;
+        if (dn == MCF_RNG_INF) ++inf_down;
+        if (u == MCF_RNG_INF) ++inf_up;
+    }
+    rhs_count(info, RNG_INF_DOWN, inf_down);
+    rhs_count(info, RNG_INF_UP, inf_up);
+}

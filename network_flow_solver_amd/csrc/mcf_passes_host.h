@@ -988,4 +988,103 @@ int mcf_certify_cut(mcf_handle* h, const int8_t* in_S, int8_t* S_out, mcf_cut* o
     return MCF_OK;
 }
 
+// ---- cost ranging on the resident basis (include/mcf.h; kernels k_rng_* above, logic mcf_core.h: mcf_rng_*)
+int mcf_cost_ranges(mcf_handle* h, int64_t count, const int64_t* arc, int64_t* down, int64_t* up, mcf_ranges_report* out) {
+    if (!h) return MCF_E_BAD_ARG;
+    const McfHostImage& im = h->im;
+    const bool all = count < 0;
+    if (all ? arc != nullptr : (count > 0 && !arc)) { h->err = "mcf_cost_ranges: count < 0 goes with a null index list, count > 0 with one"; return MCF_E_BAD_ARG; }
+    const int64_t entries = all ? im.m : count;
+    if (entries > 0 && (!down || !up)) { h->err = "mcf_cost_ranges: null output array"; return MCF_E_BAD_ARG; }
+    for (int64_t i = 0; !all && i < count; ++i)
+        if (arc[i] < 0 || arc[i] >= im.m) { h->err = "mcf_cost_ranges: arc index outside [0, m)"; return MCF_E_BAD_ARG; }
+    mcf_ranges_report rep;
+    std::memset(&rep, 0, sizeof rep);
+    rep.big_m = im.big_m;
+    if (im.m == 0 || im.n <= 1) {   // nothing to range: an empty answer
+        rep.basic_artificial = im.n;
+        rep.levels = 1;
+        rep.max_depth = im.n > 0 ? 1 : 0;
+        if (out) *out = rep;
+        return MCF_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    if ((rc = lazy_group(h, "ranging partials", {{&h->d_rng_part, kCertMaxBlocks + 1}, {&h->d_rng_info, (size_t)RNG_COUNTERS}})) != MCF_OK) return rc;
+    for (hipEvent_t& ev : h->ct_ev) if (!ev) HIP_TRY(h, hipEventCreate(&ev));
+    const int32_t N = im.n_nodes;
+    const int nb = node_grid(N);
+    hipStream_t s = h->stream;
+
+    // ---- the greatest depth decides the number of levels: one word comes back before the tables are sized
+    McfRngDepthAcc D;
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
+    hipLaunchKernelGGL(k_rng_depth, dim3(nb), dim3(kRngThreads), 0, s, (const McfNode*)h->d_node, N, h->d_rng_part);
+    hipLaunchKernelGGL(k_final<McfRngDepthAcc>, dim3(1), dim3(kPassThreads), 0, s, h->d_rng_part, nb);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(&D, h->d_rng_part + nb, sizeof D, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    float ms1 = 0, ms2 = 0;
+    HIP_TRY(h, hipEventElapsedTime(&ms1, h->ct_ev[0], h->ct_ev[1]));
+    const int K = mcf_rng_levels(D.depth);
+
+    // ---- scratch: the tables (released and allocated again when the levels outgrew them), the answer (when m outgrew it: mcf_add_arcs), the list
+    const int64_t cells = (int64_t)K * N;
+    if (cells > h->rng_cells) {
+        lazy_release({{&h->d_rng_anc, 0}, {&h->d_rng_p, 0}, {&h->d_rng_n, 0}});
+        h->rng_cells = 0;
+        if ((rc = lazy_alloc(h, "ranging tables", {{&h->d_rng_anc, 1}, {&h->d_rng_p, 1}, {&h->d_rng_n, 1}}, (size_t)cells)) != MCF_OK) return rc;
+        h->rng_cells = cells;
+    }
+    if (im.m > h->rng_arcs) {
+        lazy_release({{&h->d_rng_down, 0}, {&h->d_rng_up, 0}});
+        h->rng_arcs = 0;
+        if ((rc = lazy_alloc(h, "ranges", {{&h->d_rng_down, 1}, {&h->d_rng_up, 1}}, (size_t)im.m)) != MCF_OK) return rc;
+        h->rng_arcs = im.m;
+    }
+    if (!all && (rc = lazy_grow(h, "range indices", &h->rng_list, count, {{&h->d_rng_idx, 1}, {&h->d_rng_gdown, 1}, {&h->d_rng_gup, 1}})) != MCF_OK) return rc;
+
+    RngArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.K = K;
+    a.count_inf = all ? 1 : 0;
+    a.anc = h->d_rng_anc; a.tab[0] = h->d_rng_p; a.tab[1] = h->d_rng_n;
+    a.down = h->d_rng_down; a.up = h->d_rng_up;
+    a.info = h->d_rng_info;
+    int ab = mcf_price_blocks(im.m, 1, 0);
+    if (ab > kRngMaxBlocks) ab = kRngMaxBlocks;
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
+    if (!all && count > 0) HIP_TRY(h, hipMemcpyAsync(h->d_rng_idx, arc, (size_t)count * 8, hipMemcpyHostToDevice, s));   // (the call ends with a synchronisation)
+    HIP_TRY(h, hipMemsetAsync(h->d_rng_info, 0, RNG_COUNTERS * sizeof(unsigned long long), s));
+    for (int k = 0; k < K; ++k) hipLaunchKernelGGL(k_rng_anc, dim3(nb), dim3(kRngThreads), 0, s, (const McfNode*)h->d_node, N, k, a);
+    hipLaunchKernelGGL(k_rng_arcs, dim3(ab), dim3(kRngThreads), 0, s, h->view, a);
+    for (int k = K - 1; k >= 1; --k) hipLaunchKernelGGL(k_rng_push, dim3(nb), dim3(kRngThreads), 0, s, N, k, a);
+    hipLaunchKernelGGL(k_rng_out, dim3(nb), dim3(kRngThreads), 0, s, h->view, a);
+    if (!all && count > 0)
+        hipLaunchKernelGGL(k_rng_gather, dim3(uc_blocks_for(count)), dim3(kRngThreads), 0, s, count, (const int64_t*)h->d_rng_idx, (const int64_t*)h->d_rng_down,
+                           (const int64_t*)h->d_rng_up, h->d_rng_gdown, h->d_rng_gup, h->d_rng_info);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long info[RNG_COUNTERS] = {0, 0, 0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(info, h->d_rng_info, sizeof info, hipMemcpyDeviceToHost, s));
+    if (entries > 0) {
+        HIP_TRY(h, hipMemcpyAsync(down, all ? h->d_rng_down : h->d_rng_gdown, (size_t)entries * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(up, all ? h->d_rng_up : h->d_rng_gup, (size_t)entries * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, hipEventElapsedTime(&ms2, h->ct_ev[0], h->ct_ev[1]));
+    rep.basic_real = (int64_t)info[RNG_BASIC_REAL];
+    rep.basic_artificial = (int64_t)info[RNG_BASIC_ART];
+    rep.eligible = (int64_t)info[RNG_ELIGIBLE];
+    rep.max_depth = D.depth;
+    rep.levels = K;
+    rep.inf_down = (int64_t)info[RNG_INF_DOWN];
+    rep.inf_up = (int64_t)info[RNG_INF_UP];
+    rep.device_ms = ms1 + ms2;
+    if (out) *out = rep;
+    return MCF_OK;
+}
+
 }  // extern "C"

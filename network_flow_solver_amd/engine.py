@@ -33,7 +33,9 @@ ABI_SYMBOLS = (
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
     "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_add_arcs",
+    "mcf_cost_ranges",
 )
+RANGE_INF = (1 << 63) - 1   # MCF_RANGE_INF: no arc limits this side of a cost range
 # mcf_certify: check groups and verdicts (include/mcf.h)
 CERT_BOUNDS, CERT_CONSERVATION, CERT_DUAL, CERT_OBJECTIVES, CERT_BASIS, CERT_PRICING = 1, 2, 4, 8, 16, 32
 CERT_VERDICTS = {0: "not_proven", 1: "optimal", 2: "infeasible"}
@@ -152,6 +154,14 @@ class McfCut(ctypes.Structure):
         return d
 
 
+class McfRangesReport(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "basic_real", "basic_artificial", "eligible", "max_depth", "levels", "inf_down", "inf_up", "big_m")] + [("device_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 PROGRESS_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double)
 
 _lib = None
@@ -201,6 +211,7 @@ def load_library():
     lib.mcf_bottlenecks.argtypes = [vp, i64p, ctypes.c_int64, ctypes.c_int64, i64p, ctypes.c_int64, i64p]
     lib.mcf_certify_ray.argtypes = [vp, ctypes.c_int64, i64p, ctypes.c_int64, ctypes.POINTER(McfRay)]
     lib.mcf_certify_cut.argtypes = [vp, i8p, i8p, ctypes.POINTER(McfCut)]
+    lib.mcf_cost_ranges.argtypes = [vp, ctypes.c_int64, i64p, i64p, i64p, ctypes.POINTER(McfRangesReport)]
     lib.mcf_dimacs_scan.argtypes = [ctypes.c_char_p, i64p, i64p, ctypes.c_char_p, ctypes.c_int32]
     lib.mcf_dimacs_load.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, i32p, i32p, i64p, i64p, i64p, i64p,
                                     ctypes.c_char_p, ctypes.c_int32]
@@ -211,7 +222,7 @@ def load_library():
     for name in ("mcf_create", "mcf_solve", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs", "mcf_enqueue_price",
                  "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing", "mcf_time_copy",
                  "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load",
-                 "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut"):
+                 "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_cost_ranges"):
         getattr(lib, name).restype = ctypes.c_int
     if lib.mcf_abi_version() != ABI_VERSION:
         raise EngineUnavailableError("libmcf_hip.so ABI version mismatch")
@@ -571,6 +582,25 @@ class McfEngine:
         if want_set:
             d["S"] = s_out.astype(bool)
         return d
+
+    # -- sensitivity
+    def cost_ranges(self, arcs=None):
+        """``(down, up, report)``: how far the cost of each arc may fall / rise, one arc at a time, before the resident basis
+        stops being optimal (``mcf_cost_ranges``), computed on the device for all arcs at once.  ``arcs``: indices in this
+        engine's arc order (duplicates allowed), default all.  int64 arrays; ``RANGE_INF`` = no arc limits that side; a
+        negative entry (on a basis that is not optimal) = that side is already empty.  Ranges hold at the big-M reported.
+        Read-only.  ``report``: the fields of ``mcf_ranges_report``."""
+        rep = McfRangesReport()
+        if arcs is None:
+            count, idx = -1, None
+            entries = self.m
+        else:
+            idx = np.ascontiguousarray(arcs, dtype=np.int64).reshape(-1)
+            count = entries = int(idx.shape[0])
+        down, up = np.zeros(max(entries, 1), dtype=np.int64), np.zeros(max(entries, 1), dtype=np.int64)
+        self._check(self._lib.mcf_cost_ranges(self._h, count, None if idx is None or count == 0 else _p(idx, ctypes.c_int64),
+                                              _p(down, ctypes.c_int64), _p(up, ctypes.c_int64), ctypes.byref(rep)))
+        return down[:entries], up[:entries], rep.as_dict()
 
     # -- measurement
     def time_pricing(self, reps: int = 20, rule: int | None = None) -> float:

@@ -654,6 +654,55 @@ class NetworkSimplex:
             self.flat = replace(f, cost=new_cost, orig_cost=orig_cost)
         return int(idx.shape[0])
 
+    def cost_ranges(self, keys=None):
+        """Cost ranging on the basis resident on the device (``mcf_cost_ranges``): for every arc, the interval its cost may move
+        in -- this arc alone, all others as they are -- without the basis ceasing to be optimal, so that ``update_costs`` with
+        a cost inside it followed by ``solve()`` makes no pivot.  Computed for all arcs at once on the device; nothing is
+        re-solved.  Meaningful after a ``solve()`` that ended "optimal"; on any other state the intervals describe that
+        state's basis and may be empty (``lowest > highest``).  The intervals hold as long as the new cost does not raise the
+        engine's big-M (a cost far above every cost of the problem does).
+
+        * object-model problems: ``keys`` = ``(tail, head)`` keys (default: all; of parallel arcs the LAST one, as in
+          ``update_costs``); returns ``{(tail, head): (lowest_cost, highest_cost)}`` in the caller's cost units, ``None`` for an
+          unbounded end.
+        * ``SoAProblem``: ``keys`` = arc indices (default: all, duplicates allowed); returns ``(lowest, highest)`` arrays in the
+          order asked.  An unscaled instance -- an ``SoAProblem`` always is -- gets the exact integers, int64, with
+          ``-engine.RANGE_INF`` / ``engine.RANGE_INF`` for an unbounded end; a scaled one floats with -inf / +inf."""
+        f = self.flat
+        m = len(f.keys)
+        if f.soa:
+            idx = None
+            if keys is not None:
+                idx = np.asarray(keys).reshape(-1)
+                if idx.size and not np.issubdtype(idx.dtype, np.integer):
+                    raise InvalidProblemError("cost ranges: arc indices must be integers")
+                idx = idx.astype(np.int64)
+                if idx.size and (idx.min() < 0 or idx.max() >= m):
+                    raise InvalidProblemError(f"cost ranges: arc index outside [0, {m})")
+        else:
+            last: dict[tuple[str, str], int] = {}
+            for i, key in enumerate(f.keys):
+                last[key] = i
+            wanted = list(last) if keys is None else [tuple(k) for k in keys]
+            missing = [k for k in wanted if k not in last]
+            if missing:
+                raise InvalidProblemError(f"cost range asked for arc {missing[0]} which is not in the problem")
+            idx = np.fromiter((last[k] for k in wanted), dtype=np.int64, count=len(wanted))
+        down, up, _ = self.engine.cost_ranges(idx)
+        cost = f.cost if idx is None else f.cost[idx]
+        inf = _engine.RANGE_INF
+        if f.soa:
+            lowest = np.where(down == inf, -inf, cost - np.where(down == inf, 0, down))
+            highest = np.where(up == inf, inf, cost + np.where(up == inf, 0, up))
+            if f.cost_scale == 1:
+                return lowest, highest
+            return (np.where(down == inf, -np.inf, lowest / f.cost_scale), np.where(up == inf, np.inf, highest / f.cost_scale))
+        scale = f.cost_scale
+        out = {}
+        for k, c, d, u in zip(wanted, cost.tolist(), down.tolist(), up.tolist()):
+            out[k] = (None if d == inf else (c - d) / scale, None if u == inf else (c + u) / scale)
+        return out
+
     def _update_rhs(self, supplies, capacities) -> dict:
         f = self.flat
         s_idx, s_int, s_val, c_idx, c_int, c_val = map_rhs_changes(f, supplies, capacities, self.tolerance)
