@@ -2,8 +2,10 @@
 //
 // One pivot, by instance size (mcf_create picks; all paths share mcf_core.h and give the same pivot sequence):
 //
-//   k_solve_small   whole instance in LDS: one persistent workgroup prices, pivots (two lanes climb the cycle in
-//                   lock step) and updates until the solve ends.
+//   k_solve_small   whole instance in LDS: one persistent workgroup -- 256 lanes (one wave per SIMD) for the smaller trees,
+//                   1 024 beyond and in batches (small_threads_for) -- prices (Dantzig / candidate list: the arcs' invariant
+//                   data in registers, 10 or 3 arcs per lane by width; Devex: from LDS), pivots (the lanes stride over the
+//                   tree nodes in the cycle search, wave 0 runs the ratio tests) and updates until the solve ends.
 //   k_solve_mid     <= 1 536 nodes: one persistent workgroup over global (L2-resident) state -- prices a Devex
 //                   block / re-prices the candidate list / sweeps a small arc list, pivots, permutes, patches.
 //                   (both also as k_solve_small_batch / k_solve_mid_batch: MANY independent instances in one launch, one
@@ -1514,22 +1516,37 @@ __device__ __forceinline__ bool pivot_climb_2lanes(const McfView& v, McfCycle* o
 // Instances whose whole state fits in one CU's 160 KiB of LDS (netgen_8_08a: ~96 KiB) are
 // latency-bound, not bandwidth-bound: 27 KB per sweep is nothing, three kernel boundaries and
 // a dozen dependent global loads per pivot are everything.  This kernel copies the instance
-// into LDS once, runs pivots back to back in ONE persistent workgroup (price: all 1024 lanes
-// over LDS; pivot: the same mcf_pivot_walk / mcf_pivot_finish; apply: all lanes through the same
-// mcf_apply_one) and copies the state back.  Same arc sets, same tie rule, same core functions
-// as the three-kernel path, so the pivot sequence is identical.
+// into LDS once, runs pivots back to back in ONE persistent workgroup (price: all lanes, THREADS / 8
+// per head bucket, states and potentials from LDS, the arcs' end points, costs and ids from registers;
+// pivot: the same mcf_pivot_begin / mcf_pivot_decide / mcf_pivot_finish; apply: all lanes through the
+// same mcf_apply_one) and copies the state back.  Same arc sets, same tie rule, same core functions
+// as the three-kernel path, so the pivot sequence is identical -- at every width: the workgroup is
+// THREADS lanes wide: 256, one wave per SIMD, for the smaller trees, 1 024 beyond (small_threads_for; MCF_SMALL_THREADS).
 struct SmallLayout {
     uint32_t tail, head, cost, orig, state, weight, arcw, pi, node, order0, order1, pos0, pos1, path1, path2, ppos1, ppos2, rec1, rec2, seg, ctx, total;
 };
 
-constexpr int kSmallThreads = 1024;
 constexpr int kSmallMaxLds = 158 * 1024;   // dynamic LDS of the fused small-instance loop (160 KB per CU, a little static on top)
+constexpr int kSmallCycleMaxNodes = 1024;  // node-parallel cycle search up to this many tree nodes (strided over the lanes)
 
+// Arcs of a head bucket that one lane keeps in registers (tail, head, cost, orig: 4 VGPRs each).  THREADS / 8 lanes share a
+// bucket, so 320 (256 lanes) / 384 (1 024 lanes) arcs per bucket are register-resident -- netgen_8_08a's buckets hold
+// 256 +- 20 -- and the rest of a fuller bucket is priced from LDS.
+// A/B builds of the loop's parts (scripts/stamps_small.py before / after): -DMCF_SMALL_LDS_SWEEP prices every arc from LDS,
+// -DMCF_SMALL_SERIAL_RATIO leaves the ratio tests to lane 0.
+#if defined(MCF_SMALL_LDS_SWEEP)
+constexpr bool kRegSweep = false;
+#else
+constexpr bool kRegSweep = true;
+#endif
+template <int THREADS> struct SmallRegArcs { static constexpr int value = THREADS <= 256 ? 10 : (THREADS <= 512 ? 5 : 3); };
+
+template <int THREADS>
 __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t bytes) {
     const uint32_t n = bytes >> 2;
     const int32_t* s = static_cast<const int32_t*>(src);
     int32_t* d = static_cast<int32_t*>(dst);
-    for (uint32_t i = threadIdx.x; i < n; i += kSmallThreads) d[i] = s[i];
+    for (uint32_t i = threadIdx.x; i < n; i += THREADS) d[i] = s[i];
 }
 
 #ifdef MCF_STAMPS
@@ -1553,10 +1570,35 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t 
 // reductions for the whole cycle, whatever its length, instead of one dependent round per tree level on one or two lanes
 // (the 2-lane climb was 53 % of a pivot on netgen_8_08a).  Same path arrays, same ratio-test winners (first side: lowest
 // index among equal residuals, second side: highest), hence the same pivots.  All threads call it; one barrier inside;
-// lane 0 gets the finished McfCycle.  Requires n_nodes <= THREADS.
+// lane 0 gets the finished McfCycle.  Lane x takes the nodes x, x + THREADS, ... (netgen_8_08a has 257 tree nodes: two
+// passes at 256 lanes), so the tree need not fit the workgroup; the caller gates on kSmallCycleMaxNodes.
+// After the barrier wave 0 alone finishes: the per-wave counts are one LDS read per lane summed over scalar lane reads, and
+// each side's ratio test is one DPP min reduction per 64 path indices with the winner taken from a ballot -- two independent
+// chains in one wave, which overlap, and no second barrier as handing a side to another wave would need.
 struct SmallCycleAcc {
     int32_t c1[16], c2[16];   // one-sided ancestors per wave, first / second side
 };
+
+// Ratio test of one side over res[0 .. n), by all 64 lanes of a wave.  !LAST: strictly smaller wins, the lowest index among
+// equal residuals (d = MCF_INF, k = -1 when nothing is below MCF_INF); LAST: smaller or equal wins, the highest index.
+template <bool LAST>
+__device__ __forceinline__ void small_ratio_side(const int64_t* res, int32_t n, int64_t* d_out, int32_t* k_out) {
+    const int32_t lane = (int32_t)(threadIdx.x & 63);
+    int64_t d = MCF_INF;
+    int32_t k = -1;
+    for (int32_t base = 0; base < n; base += 64) {   // (uniform; one trip unless the path is longer than a wave)
+        const int32_t i = base + lane;
+        // lanes past the end can never hold the minimum: a residual is at most MCF_INF
+        const int64_t r = i < n ? res[i] : INT64_MAX;
+        const int64_t mn = -mcf_wave_max64(-r);
+        const uint64_t mask = __ballot(r == mn);
+        if (LAST ? mn <= d : mn < d) {
+            d = mn;
+            k = base + (LAST ? 63 - __builtin_clzll((unsigned long long)mask) : __builtin_ctzll((unsigned long long)mask));
+        }
+    }
+    *d_out = d; *k_out = k;
+}
 
 template <int THREADS>
 __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycleAcc& A, McfCycle* out) {
@@ -1567,61 +1609,144 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
     //  pass they were spilled to scratch, the only private memory this kernel used)
     const int32_t du0 = v.node[first].depth, dw0 = v.node[second].depth;
     const int32_t pu = pcur[first], pw = pcur[second];
-    const int32_t x = (int32_t)threadIdx.x, wave = x >> 6;
-    const int32_t N = v.n_nodes, nwaves = (N + 63) >> 6;
+    const int32_t wave = (int32_t)threadIdx.x >> 6;
+    const int32_t N = v.n_nodes;
     // scratch in the segment table's LDS (the finish pass only fills it afterwards): residual per path index and side, and
     // the common ancestors by depth (root .. join occupy depths 0 .. depth[join], one node each)
     int64_t* const res1 = reinterpret_cast<int64_t*>(v.seg);
     int64_t* const res2 = res1 + N;
     int32_t* const by_depth = reinterpret_cast<int32_t*>(res2 + N);
-    bool h1 = false, h2 = false;
-    if (x < N) {
-        const McfNode rec = v.node[x];
-        const int32_t px = pcur[x];
-        const bool au = (uint32_t)(pu - px) < (uint32_t)rec.size, aw = (uint32_t)(pw - px) < (uint32_t)rec.size;
-        if (au && aw) by_depth[rec.depth] = x;
-        else if (au) {
-            const McfArcW a = v.arcw[rec.pred >> 1];
-            const int32_t idx = du0 - rec.depth;
-            v.path1[idx] = x; v.rec1[idx] = rec; v.ppos1[idx] = px;
-            // first side is walked against the flow: an up arc loses flow, a down arc gains
-            res1[idx] = (rec.pred & 1) ? a.flow : (a.cap >= MCF_INF ? MCF_INF : a.cap - a.flow);
-            h1 = true;
-        } else if (aw) {
-            const McfArcW a = v.arcw[rec.pred >> 1];
-            const int32_t idx = dw0 - rec.depth;
-            v.path2[idx] = x; v.rec2[idx] = rec; v.ppos2[idx] = px;
-            res2[idx] = (rec.pred & 1) ? (a.cap >= MCF_INF ? MCF_INF : a.cap - a.flow) : a.flow;
-            h2 = true;
+    int32_t n1w = 0, n2w = 0;   // this wave's one-sided ancestors, over its passes
+    for (int32_t x0 = 0; x0 < N; x0 += THREADS) {   // (uniform: every wave makes every pass)
+        const int32_t x = x0 + (int32_t)threadIdx.x;
+        bool h1 = false, h2 = false;
+        if (x < N) {
+            const McfNode rec = v.node[x];
+            const int32_t px = pcur[x];
+            const bool au = (uint32_t)(pu - px) < (uint32_t)rec.size, aw = (uint32_t)(pw - px) < (uint32_t)rec.size;
+            if (au && aw) by_depth[rec.depth] = x;
+            else if (au) {
+                const McfArcW a = v.arcw[rec.pred >> 1];
+                const int32_t idx = du0 - rec.depth;
+                v.path1[idx] = x; v.rec1[idx] = rec; v.ppos1[idx] = px;
+                // first side is walked against the flow: an up arc loses flow, a down arc gains
+                res1[idx] = (rec.pred & 1) ? a.flow : (a.cap >= MCF_INF ? MCF_INF : a.cap - a.flow);
+                h1 = true;
+            } else if (aw) {
+                const McfArcW a = v.arcw[rec.pred >> 1];
+                const int32_t idx = dw0 - rec.depth;
+                v.path2[idx] = x; v.rec2[idx] = rec; v.ppos2[idx] = px;
+                res2[idx] = (rec.pred & 1) ? (a.cap >= MCF_INF ? MCF_INF : a.cap - a.flow) : a.flow;
+                h2 = true;
+            }
         }
+        n1w += (int32_t)__popcll(__ballot(h1));
+        n2w += (int32_t)__popcll(__ballot(h2));
     }
-    if (wave < nwaves) {
-        const int32_t n1w = (int32_t)__popcll(__ballot(h1)), n2w = (int32_t)__popcll(__ballot(h2));
-        if ((x & 63) == 0) { A.c1[wave] = n1w; A.c2[wave] = n2w; }
-    }
-    __syncthreads();
-    if (x == 0) {
+    if ((threadIdx.x & 63) == 0) { A.c1[wave] = n1w; A.c2[wave] = n2w; }
+    __syncthreads();   // path / record / residual / by_depth entries and the per-wave counts -> wave 0's ratio tests
+#if defined(MCF_SMALL_SERIAL_RATIO)   // A/B build: lane 0 sums the counts and runs both ratio tests as scalar loops
+    if (threadIdx.x == 0) {
         int32_t n1 = 0, n2 = 0;
-        for (int32_t q = 0; q < nwaves; ++q) { n1 += A.c1[q]; n2 += A.c2[q]; }
-        const int32_t jn = by_depth[du0 - n1];   // the join: the common ancestor right above the first side's path
-        const McfNode rj = v.node[jn];
-        // the ratio tests, exactly the climb's: first side -- strictly smaller wins (lowest index among equals), second side --
-        // smaller or equal wins (highest index among equals)
+        for (int32_t q = 0; q < THREADS / 64; ++q) { n1 += A.c1[q]; n2 += A.c2[q]; }
         int64_t d1 = MCF_INF, d2 = MCF_INF;
         int32_t k1 = -1, k2 = -1;
         for (int32_t i = 0; i < n1; ++i) { const int64_t r = res1[i]; if (r < d1) { d1 = r; k1 = i; } }
         for (int32_t i = 0; i < n2; ++i) { const int64_t r = res2[i]; if (r <= d2) { d2 = r; k2 = i; } }
-        out->d1 = d1; out->k1 = k1; out->d2 = d2; out->k2 = k2;
-        out->n1 = n1; out->n2 = n2;
-        out->u = jn; out->w = jn; out->ru = rj; out->rw = rj;
-        out->pu = pcur[jn]; out->pw = out->pu; out->su = out->pu; out->sw = out->pu;
-        out->p0u = pu; out->p0w = pw; out->s0u = pu; out->s0w = pw; out->r0u = v.node[first]; out->r0w = v.node[second];
-        out->small = 0;
+        const int32_t lane = 0;
+#else
+    if (wave == 0) {
+        constexpr int kWaves = THREADS / 64;
+        const int32_t lane = (int32_t)threadIdx.x;
+        const int32_t c1 = lane < kWaves ? A.c1[lane] : 0, c2 = lane < kWaves ? A.c2[lane] : 0;   // one read, then scalar lane reads
+        int32_t n1 = 0, n2 = 0;
+#pragma unroll
+        for (int q = 0; q < kWaves; ++q) { n1 += __builtin_amdgcn_readlane(c1, q); n2 += __builtin_amdgcn_readlane(c2, q); }
+        // the ratio tests, exactly the climb's: first side -- strictly smaller wins (lowest index among equals), second side --
+        // smaller or equal wins (highest index among equals)
+        int64_t d1, d2;
+        int32_t k1, k2;
+        small_ratio_side<false>(res1, n1, &d1, &k1);
+        small_ratio_side<true>(res2, n2, &d2, &k2);
+#endif
+        if (lane == 0) {
+            const int32_t jn = by_depth[du0 - n1];   // the join: the common ancestor right above the first side's path
+            const McfNode rj = v.node[jn];
+            out->d1 = d1; out->k1 = k1; out->d2 = d2; out->k2 = k2;
+            out->n1 = n1; out->n2 = n2;
+            out->u = jn; out->w = jn; out->ru = rj; out->rw = rj;
+            out->pu = pcur[jn]; out->pw = out->pu; out->su = out->pu; out->sw = out->pu;
+            out->p0u = pu; out->p0w = pw; out->s0u = pu; out->s0w = pw; out->r0u = v.node[first]; out->r0w = v.node[second];
+            out->small = 0;
+        }
     }
 }
 
-// The whole solve of one LDS-resident instance by one workgroup (k_solve_small: one instance per launch;
+// ------------------------------------------------------------------ pricing sweep of the LDS loop
+// The sweep is specialised at compile time and chosen once per launch, so that its inner loop tests neither the rule nor
+// the key mode: kSweepPlain -- Dantzig / candidate list with the plain key (the violation), kSweepDevex -- the Devex merit
+// with the direction-carrying id, kSweepGeneric -- everything else (the specialised key modes of mcf_dantzig_key).
+enum { kSweepGeneric = 0, kSweepPlain = 1, kSweepDevex = 2 };
+
+// One arc priced from the LDS arrays: state, end points, cost and id in one round trip, the two potentials in a second.
+template <int MODE>
+__device__ __forceinline__ void small_price_lds(const McfView& v, int32_t rule, bool devex, int32_t i, int64_t& key, int64_t& arc) {
+    const int32_t st = v.state[i];
+    const int32_t t = v.tail[i], h = v.head[i], o = v.orig[i];
+    const int64_t cst = v.cost[i];
+    float w = 1.0f;
+    if (MODE == kSweepDevex || (MODE == kSweepGeneric && rule == MCF_RULE_DEVEX_BLOCK)) w = v.weight[i];
+    const int64_t rc = cst + v.pi[t] - v.pi[h];
+    const int64_t viol = st > 0 ? -rc : rc;
+    if (st == 0 || viol <= 0) return;
+    int64_t kk;
+    int32_t id = o;
+    if (MODE == kSweepPlain) kk = viol;
+    else if (MODE == kSweepDevex) {
+        kk = __double_as_longlong(((double)viol * (double)viol) / (double)w);
+        id = mcf_devex_tie_id(o, st);
+    } else {
+        kk = mcf_dantzig_key(v, i, viol, st);
+        if (rule == MCF_RULE_DEVEX_BLOCK) kk = __double_as_longlong(((double)viol * (double)viol) / (double)w);
+        if (devex) id = mcf_devex_tie_id(o, st);
+    }
+    const int64_t pid = mcf_pack_arc(id, i);
+    if (mcf_cand_better(kk, pid, key, arc)) { key = kk; arc = pid; }
+}
+
+// Arg-max inside each half of a wave (32 lanes = one head bucket at 256 lanes): the first five DPP steps of
+// mcf_wave_max64 leave the max of rows 0-1 in lane 31 and of rows 2-3 in lane 63; ids as in wave_argmax.  The result is
+// uniform per half.  All 64 lanes must be active.
+__device__ __forceinline__ void half_wave_argmax(int64_t& key, int64_t& arc) {
+    int64_t x = key;
+    x = mcf_dpp_max_step<0xB1, 0xf>(x);
+    x = mcf_dpp_max_step<0x4E, 0xf>(x);
+    x = mcf_dpp_max_step<0x141, 0xf>(x);
+    x = mcf_dpp_max_step<0x140, 0xf>(x);
+    x = mcf_dpp_max_step<0x142, 0xa>(x);
+    const int64_t m0 = readlane64(x, 31), m1 = readlane64(x, 63);
+    const bool upper = (threadIdx.x & 32) != 0;
+    const int64_t mx = upper ? m1 : m0;
+    const uint64_t mask = __ballot(key == mx && key > 0);
+    int64_t best[2] = {-1, -1};
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        uint64_t mk = hf ? (mask >> 32) << 32 : mask & 0xffffffffull;
+        while (mk) {  // uniform loop: one iteration unless several lanes tie on the key
+            const int lane = __ffsll((unsigned long long)mk) - 1;
+            const int64_t a = readlane64(arc, lane);
+            if (best[hf] < 0 || a < best[hf]) best[hf] = a;
+            mk &= mk - 1;
+        }
+    }
+    const int64_t b = upper ? best[1] : best[0];
+    key = b < 0 ? 0 : mx;
+    arc = b;
+}
+
+// The whole solve of one LDS-resident instance by one workgroup of THREADS lanes (k_solve_small: one instance per launch;
 // k_solve_small_batch: one instance per workgroup of the launch)
+template <int THREADS>
 __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLayout& L, int32_t rule,
                                                  McfCand* __restrict__ list, int64_t cap, char* smem, McfCtx* host_ctx) {
 #ifdef MCF_STAMPS
@@ -1662,20 +1787,20 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
 
     // (All fourteen arrays' loads in flight together -- one fused loop, 4- or 16-byte loads -- was measured SLOWER than these
     //  plain loops: 131 / 125 us against 117 us per 20-pivot launch.)
-    copy_words(smem + L.tail, g.tail, m_pad4);
-    copy_words(smem + L.head, g.head, m_pad4);
-    copy_words(smem + L.cost, g.cost, m_pad4);
-    copy_words(smem + L.orig, g.orig, m_pad4);
-    copy_words(smem + L.state, g.state, m_padb);
-    if (g.weight) copy_words(smem + L.weight, g.weight, m_pad4);
-    copy_words(smem + L.arcw, g.arcw, arcw_b);
-    copy_words(smem + L.pi, g.pi, N * 8u);
-    copy_words(smem + L.node, g.node, N * 16u);
-    copy_words(smem + L.order0, g.order[0], N * 4u);
-    copy_words(smem + L.order1, g.order[1], N * 4u);
-    copy_words(smem + L.pos0, g.posbuf[0], N * 4u);
-    copy_words(smem + L.pos1, g.posbuf[1], N * 4u);
-    copy_words(smem + L.ctx, g.ctx, (uint32_t)sizeof(McfCtx));
+    copy_words<THREADS>(smem + L.tail, g.tail, m_pad4);
+    copy_words<THREADS>(smem + L.head, g.head, m_pad4);
+    copy_words<THREADS>(smem + L.cost, g.cost, m_pad4);
+    copy_words<THREADS>(smem + L.orig, g.orig, m_pad4);
+    copy_words<THREADS>(smem + L.state, g.state, m_padb);
+    if (g.weight) copy_words<THREADS>(smem + L.weight, g.weight, m_pad4);
+    copy_words<THREADS>(smem + L.arcw, g.arcw, arcw_b);
+    copy_words<THREADS>(smem + L.pi, g.pi, N * 8u);
+    copy_words<THREADS>(smem + L.node, g.node, N * 16u);
+    copy_words<THREADS>(smem + L.order0, g.order[0], N * 4u);
+    copy_words<THREADS>(smem + L.order1, g.order[1], N * 4u);
+    copy_words<THREADS>(smem + L.pos0, g.posbuf[0], N * 4u);
+    copy_words<THREADS>(smem + L.pos1, g.posbuf[1], N * 4u);
+    copy_words<THREADS>(smem + L.ctx, g.ctx, (uint32_t)sizeof(McfCtx));
     __syncthreads();
     STAMP(0);
 
@@ -1685,23 +1810,42 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     __shared__ int32_t s_gran[MCF_NUM_BUCKETS][MCF_GRANULES + 1];
     const bool devex = rule == MCF_RULE_DEVEX_BLOCK && g.dx;
     if (devex) {
-        for (int q = threadIdx.x; q < MCF_NUM_BUCKETS * (MCF_GRANULES + 1); q += kSmallThreads)
+        for (int q = threadIdx.x; q < MCF_NUM_BUCKETS * (MCF_GRANULES + 1); q += THREADS)
             (&s_gran[0][0])[q] = (&g.dx->gran[0][0])[q];
     } else if (threadIdx.x < MCF_NUM_BUCKETS) {
         s_gran[threadIdx.x][0] = (int32_t)g.bucket_off[threadIdx.x];
         s_gran[threadIdx.x][MCF_GRANULES] = (int32_t)g.bucket_off[threadIdx.x + 1];
     }
-    __syncthreads();
     // candidate-list rule: the list is the best arc of each head bucket (= of each of the 8 pricing
     // workgroups the three-kernel path would use at this size); minor iterations re-price just
     // those 8 arcs.  The list survives between launches in `list` (global).
     const bool listing = rule == MCF_RULE_CANDIDATE_LIST;
     __shared__ int64_t s_lk[MCF_NUM_BUCKETS], s_la[MCF_NUM_BUCKETS];
     if (listing && threadIdx.x < MCF_NUM_BUCKETS) { s_lk[threadIdx.x] = list[threadIdx.x].key; s_la[threadIdx.x] = list[threadIdx.x].arc; }
-    __syncthreads();
+    __syncthreads();   // arm_ctx, the granule table and the list -> every lane's reads below and in the loop
+
+    // ---- lane map of the sweep: THREADS / 8 lanes per head bucket, all eight buckets at once
+    constexpr int kPer = THREADS / MCF_NUM_BUCKETS;
+    constexpr int kReg = SmallRegArcs<THREADS>::value;
+    static_assert(kPer == 32 || kPer % 64 == 0, "a head bucket's lanes are half a wave or whole waves");
+    const int px = threadIdx.x / kPer, pl = threadIdx.x % kPer;
+    const int sweep = devex ? kSweepDevex : (rule != MCF_RULE_DEVEX_BLOCK && v.key_mode == MCF_KEY_PLAIN ? kSweepPlain : kSweepGeneric);
+    // Plain sweep: the arcs a lane prices are the same at every pivot (whole buckets), and tail / head / cost / orig never
+    // change during a launch: the first kReg of them live in registers from here on.  (Slots past the bucket's end price
+    // arc 0 with its state masked to 0.)
+    int32_t r_tail[kReg], r_head[kReg], r_cost[kReg], r_orig[kReg];
+    int32_t r_n = 0;   // slots in use
+    const int32_t r_lo = s_gran[px][0] + pl, r_hi = s_gran[px][MCF_GRANULES];
+#pragma unroll
+    for (int k = 0; k < kReg; ++k) {
+        const int32_t i = r_lo + k * kPer;
+        const bool on = kRegSweep && sweep == kSweepPlain && i < r_hi;
+        r_tail[k] = on ? v.tail[i] : 0; r_head[k] = on ? v.head[i] : 0; r_cost[k] = on ? v.cost[i] : 0; r_orig[k] = on ? v.orig[i] : 0;
+        r_n += on ? 1 : 0;
+    }
     for (;;) {
         // uniform control values are read BEFORE a barrier: lane 0 rewrites them later in this very
-        // iteration (mcf_pivot_walk), and a lagging wave must not see the new values
+        // iteration (mcf_pivot_begin / mcf_pivot_decide), and a lagging wave must not see the new values
         const int32_t status_now = c->status;
         const bool minor = listing && c->minor_left > 0;
         int32_t bg0 = 0, bg1 = MCF_GRANULES;  // Devex: granule range of the current block
@@ -1711,52 +1855,74 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             if (bg0 >= MCF_GRANULES) bg0 = 0;
             bg1 = bg0 + bg < MCF_GRANULES ? bg0 + bg : MCF_GRANULES;
         }
-        __syncthreads();
+        __syncthreads();   // every lane's reads of status / minor_left / block_index -> lane 0's writes below.  (Only a candidate-
+                           // list minor iteration has no other barrier in front of those writes; dropping it elsewhere was
+                           // tried and bought nothing)
         if (status_now != MCF_RUNNING) break;
         // ---- price: the arc set of k_price for shard 0 of 1
         int64_t key = 0, arc = -1;
         if (!minor) {
-            // 128 lanes per head bucket, all eight buckets at once
-            constexpr int kPer = kSmallThreads / MCF_NUM_BUCKETS;
-            const int x = threadIdx.x / kPer, l = threadIdx.x % kPer;
-            const int64_t lo = s_gran[x][bg0], hi = s_gran[x][bg1];
-            for (int64_t i = lo + l; i < hi; i += kPer) {
-                if (!v.state[i]) continue;
-                const int64_t viol = mcf_violation(v, i);
-                if (viol <= 0) continue;
-                int64_t kk = mcf_dantzig_key(v, i, viol, (int32_t)v.state[i]);
-                if (rule == MCF_RULE_DEVEX_BLOCK) {
-                    const double merit = ((double)viol * (double)viol) / (double)v.weight[i];
-                    kk = __double_as_longlong(merit);
+            if (sweep == kSweepPlain && kRegSweep) {
+                // one LDS round trip for the whole lane: states and potentials of all its register arcs, then selects
+                int32_t st[kReg];
+                int64_t pt[kReg], ph[kReg];
+#pragma unroll
+                for (int k = 0; k < kReg; ++k) {
+                    st[k] = v.state[k < r_n ? r_lo + k * kPer : 0];
+                    pt[k] = v.pi[r_tail[k]];
+                    ph[k] = v.pi[r_head[k]];
                 }
-                const int64_t id = mcf_pack_arc(devex ? mcf_devex_tie_id(v.orig[i], v.state[i]) : v.orig[i], i);
-                if (mcf_cand_better(kk, id, key, arc)) { key = kk; arc = id; }
+#pragma unroll
+                for (int k = 0; k < kReg; ++k) {
+                    const int64_t rc = (int64_t)r_cost[k] + pt[k] - ph[k];
+                    const int32_t s = k < r_n ? st[k] : 0;
+                    const int64_t viol = s > 0 ? -rc : rc;
+                    const int64_t pid = mcf_pack_arc(r_orig[k], r_lo + k * kPer);
+                    if (s != 0 && viol > 0 && mcf_cand_better(viol, pid, key, arc)) { key = viol; arc = pid; }
+                }
+                for (int32_t i = r_lo + kReg * kPer; i < r_hi; i += kPer) small_price_lds<kSweepPlain>(v, rule, devex, i, key, arc);
+            } else {
+                const int32_t lo = s_gran[px][bg0], hi = s_gran[px][bg1];
+                if (sweep == kSweepDevex) for (int32_t i = lo + pl; i < hi; i += kPer) small_price_lds<kSweepDevex>(v, rule, devex, i, key, arc);
+                else if (sweep == kSweepPlain) for (int32_t i = lo + pl; i < hi; i += kPer) small_price_lds<kSweepPlain>(v, rule, devex, i, key, arc);
+                else for (int32_t i = lo + pl; i < hi; i += kPer) small_price_lds<kSweepGeneric>(v, rule, devex, i, key, arc);
             }
         }
         STAMP(1);
         if (listing) {
-            __shared__ int64_t s_wk[kSmallThreads / 64], s_wa[kSmallThreads / 64];
-            if (!minor) {
-                wave_argmax(key, arc);
-                if ((threadIdx.x & 63) == 0) { s_wk[threadIdx.x >> 6] = key; s_wa[threadIdx.x >> 6] = arc; }
-                __syncthreads();
-                if (threadIdx.x < MCF_NUM_BUCKETS) {  // two waves per bucket
-                    const int w = 2 * threadIdx.x;
-                    const bool second = mcf_cand_better(s_wk[w + 1], s_wa[w + 1], s_wk[w], s_wa[w]);
-                    s_lk[threadIdx.x] = second ? s_wk[w + 1] : s_wk[w];
-                    s_la[threadIdx.x] = second ? s_wa[w + 1] : s_wa[w];
+            if (!minor) {   // the list: each head bucket's best
+                if constexpr (kPer >= 64) {
+                    constexpr int kWpb = kPer / 64;   // waves per bucket
+                    __shared__ int64_t s_wk[THREADS / 64], s_wa[THREADS / 64];
+                    wave_argmax(key, arc);
+                    if ((threadIdx.x & 63) == 0) { s_wk[threadIdx.x >> 6] = key; s_wa[threadIdx.x >> 6] = arc; }
+                    __syncthreads();   // per-wave candidates -> the bucket's lane
+                    if (threadIdx.x < MCF_NUM_BUCKETS) {
+                        const int w = kWpb * threadIdx.x;
+                        int64_t bk = s_wk[w], ba = s_wa[w];
+                        for (int q = 1; q < kWpb; ++q)
+                            if (mcf_cand_better(s_wk[w + q], s_wa[w + q], bk, ba)) { bk = s_wk[w + q]; ba = s_wa[w + q]; }
+                        s_lk[threadIdx.x] = bk; s_la[threadIdx.x] = ba;
+                    }
+                } else {
+                    half_wave_argmax(key, arc);
+                    if (pl == 0) { s_lk[px] = key; s_la[px] = arc; }
                 }
-                __syncthreads();
+                __syncthreads();   // the new list -> wave 0's arg-max over it
             }
-            if (threadIdx.x == 0) {
+            // lanes 0-7 take one listed arc each (a minor iteration re-prices it), wave 0 reduces: mcf_cand_better is a
+            // total order, so the winner is the one the lane-by-lane scan found
+            if (threadIdx.x < 64) {
                 key = 0; arc = -1;
-                for (int x = 0; x < MCF_NUM_BUCKETS; ++x) {
-                    const int64_t kk = minor ? mcf_minor_key(v, s_la[x]) : s_lk[x];
-                    if (mcf_cand_better(kk, s_la[x], key, arc)) { key = kk; arc = s_la[x]; }
+                if (threadIdx.x < MCF_NUM_BUCKETS) {
+                    arc = s_la[threadIdx.x];
+                    key = minor ? mcf_minor_key(v, arc) : s_lk[threadIdx.x];
+                    if (key <= 0) { key = 0; arc = -1; }
                 }
+                wave_argmax(key, arc);
             }
         } else {
-            block_argmax<kSmallThreads>(key, arc);
+            block_argmax<THREADS>(key, arc);
         }
         STAMP(2);
         // ---- pivot: one lane walks, everything it touches is in LDS
@@ -1767,7 +1933,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
                 c->arcs_priced += minor ? MCF_NUM_BUCKETS : priced;
             }
         }
-        // Cycle search: every lane is a node (small_cycle_parallel) when the tree fits the workgroup; else lanes 0 and 1 climb
+        // Cycle search: every lane takes nodes (small_cycle_parallel) while the tree is small enough; else lanes 0 and 1 climb
         // one side each (pivot_climb_2lanes).  Lane 0 does the scalar rest.
         __shared__ int s_go, s_deep;
         __shared__ McfCycle s_cy;
@@ -1778,16 +1944,16 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             if (s_go) { const int32_t du = v.node[c->pv_first].depth, dw = v.node[c->pv_second].depth; s_deep = du > dw ? du : dw; }
             MCF_PSTAMP(13);
         }
-        __syncthreads();
+        __syncthreads();   // lane 0's s_go / s_deep / pv_first / pv_second (and apply = 0, stage = 0) -> every lane
         if (s_go) {
             // (end points that hang close to the root -- the first pivots of a cold start -- are climbed: a level or two of
             //  LDS round trips beat the parallel search's fixed cost: 144 K vs 126 K pivots/s over the first 25 pivots)
 #if defined(MCF_SMALL_CLIMB)   // A/B build: always the two-lane climb
             if (false) {
 #else
-            if (v.n_nodes <= kSmallThreads && s_deep > 3) {
+            if (v.n_nodes <= kSmallCycleMaxNodes && s_deep > 3) {
 #endif
-                small_cycle_parallel<kSmallThreads>(v, s_acc, &s_cy);
+                small_cycle_parallel<THREADS>(v, s_acc, &s_cy);
                 if (threadIdx.x == 0) { MCF_PSTAMP(15); mcf_pivot_decide(v, mcf_view_paths(v), s_cy); MCF_PSTAMP(16); }
             } else if (threadIdx.x < 2) {
                 const bool ok = pivot_climb_2lanes(v, &s_cy);
@@ -1798,22 +1964,27 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             }
         }
         STAMP(3);
-        __syncthreads();
-        mcf_pivot_finish(v, mcf_view_paths(v), threadIdx.x, kSmallThreads);
-        __syncthreads();
+        __syncthreads();   // lane 0's decision (stage, pv_*, the apply descriptor) and the recorded paths -> the finish pass
+        mcf_pivot_finish(v, mcf_view_paths(v), threadIdx.x, THREADS);
+        __syncthreads();   // the finish pass's segment table and node records -> the apply pass
         STAMP(4);
         // ---- apply: block permutation of the preorder array + potential shift
-        if (c->status == MCF_RUNNING || c->apply) {
-            if (c->apply) {  // the descriptor stays in LDS (broadcast reads); a private copy would spill
-                const int32_t lo = c->lo, hi = c->hi, plo = c->prev_lo, phi = c->prev_hi;
-                for (int32_t j = lo + threadIdx.x; j < hi; j += kSmallThreads) mcf_apply_one(v, *c, j);
-                for (int32_t j = plo + threadIdx.x; j < phi; j += kSmallThreads)
-                    if (j < lo || j >= hi) mcf_apply_one(v, *c, j);
-            }
+        if (c->apply) {
+            // the descriptor's fields once per lane into registers: every element used to read them from LDS again, since its
+            // own stores may alias them (a private copy spilled under the 1 024-lane register cap; it does not any more)
+            McfCtx d;
+            d.cur = c->cur; d.lo = c->lo; d.hi = c->hi; d.t2_new = c->t2_new; d.t2_size = c->t2_size; d.t2_old = c->t2_old;
+            d.nseg = c->nseg; d.pv_dd0 = c->pv_dd0; d.sigma = c->sigma;
+            const int32_t lo = d.lo, hi = d.hi, plo = c->prev_lo, phi = c->prev_hi;
+            for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one(v, d, j);
+            for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
+                if (j < lo || j >= hi) mcf_apply_one(v, d, j);
         }
-        __syncthreads();
+        __syncthreads();   // every lane's read of c->apply and the apply pass's order / position / potential / depth stores
+                           // -> lane 0's store below and the next iteration's reads
         if (threadIdx.x == 0) c->apply = 0;
-        __syncthreads();
+        __syncthreads();   // apply = 0 -> the next iteration's reads and the copy-out (mcf_pivot_begin would clear it too, but
+                           // leaving it to that was tried and bought nothing)
         STAMP(5);
     }
 
@@ -1823,25 +1994,25 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         if (threadIdx.x == 0) s_any = 0;
         __syncthreads();
         int any = 0;
-        for (int64_t i = threadIdx.x; i < g.m && !any; i += kSmallThreads)
+        for (int64_t i = threadIdx.x; i < g.m && !any; i += THREADS)
             if (v.state[i] && mcf_violation(v, i) > 0) any = 1;
         if (any) s_any = 1;
         __syncthreads();
         if (threadIdx.x == 0) { if (s_any) c->limit_checked = 1; else c->status = MCF_OPTIMAL; }
         __syncthreads();
     }
-    copy_words(g.state, smem + L.state, m_padb);
-    if (g.weight) copy_words(g.weight, smem + L.weight, m_pad4);
-    copy_words(g.arcw, smem + L.arcw, arcw_b);
-    copy_words(g.pi, smem + L.pi, N * 8u);
-    copy_words(g.node, smem + L.node, N * 16u);
-    copy_words(g.order[0], smem + L.order0, N * 4u);
-    copy_words(g.order[1], smem + L.order1, N * 4u);
-    copy_words(g.posbuf[0], smem + L.pos0, N * 4u);
-    copy_words(g.posbuf[1], smem + L.pos1, N * 4u);
-    copy_words(g.ctx, smem + L.ctx, (uint32_t)sizeof(McfCtx));
+    copy_words<THREADS>(g.state, smem + L.state, m_padb);
+    if (g.weight) copy_words<THREADS>(g.weight, smem + L.weight, m_pad4);
+    copy_words<THREADS>(g.arcw, smem + L.arcw, arcw_b);
+    copy_words<THREADS>(g.pi, smem + L.pi, N * 8u);
+    copy_words<THREADS>(g.node, smem + L.node, N * 16u);
+    copy_words<THREADS>(g.order[0], smem + L.order0, N * 4u);
+    copy_words<THREADS>(g.order[1], smem + L.order1, N * 4u);
+    copy_words<THREADS>(g.posbuf[0], smem + L.pos0, N * 4u);
+    copy_words<THREADS>(g.posbuf[1], smem + L.pos1, N * 4u);
+    copy_words<THREADS>(g.ctx, smem + L.ctx, (uint32_t)sizeof(McfCtx));
     // ... and straight into the host's pinned copy: the host then only waits for the stream, no read-back copy
-    if (host_ctx) copy_words(host_ctx, smem + L.ctx, (uint32_t)sizeof(McfCtx));
+    if (host_ctx) copy_words<THREADS>(host_ctx, smem + L.ctx, (uint32_t)sizeof(McfCtx));
     if (listing && threadIdx.x < MCF_NUM_BUCKETS) list[threadIdx.x] = McfCand{s_lk[threadIdx.x], s_la[threadIdx.x]};
 #ifdef MCF_STAMPS
     STAMP(6);
@@ -1853,10 +2024,13 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
 #endif
 }
 
-__global__ __launch_bounds__(kSmallThreads) void k_solve_small(McfView g, SmallLayout L, int32_t rule,
-                                                                McfCand* __restrict__ list, int64_t cap, McfCtx* host_ctx) {
+// (waves per SIMD stated: one workgroup per CU -- the LDS image allows no second -- so 256 lanes are ONE wave per SIMD and may
+//  use its whole register file; left to guess, the compiler kept room for two and put 20 B per lane into scratch)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS / 256, THREADS / 256))) void k_solve_small(McfView g, SmallLayout L, int32_t rule,
+                                                          McfCand* __restrict__ list, int64_t cap, McfCtx* host_ctx) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    solve_small_body(g, L, rule, list, cap, smem, host_ctx);
+    solve_small_body<THREADS>(g, L, rule, list, cap, smem, host_ctx);
 }
 
 // Many independent small instances side by side: workgroup b solves jobs[b] from start to finish in its own CU's LDS.
@@ -1872,10 +2046,11 @@ struct SmallJob {
     McfCtx* host_ctx;   // pinned: the final control block goes straight to the host
 };
 
-__global__ __launch_bounds__(kSmallThreads) void k_solve_small_batch(const SmallJob* __restrict__ jobs) {
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS / 256, THREADS / 256))) void k_solve_small_batch(const SmallJob* __restrict__ jobs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const SmallJob& J = jobs[blockIdx.x];   // uniform per workgroup: scalar loads
-    solve_small_body(J.g, J.L, J.rule, J.list, J.cap, smem, J.host_ctx);
+    solve_small_body<THREADS>(J.g, J.L, J.rule, J.list, J.cap, smem, J.host_ctx);
 }
 
 // ------------------------------------------------------------------ k_ctl: (re)arm the control block
@@ -1940,6 +2115,7 @@ struct mcf_handle {
     int apply_blocks = 1;
     int32_t climb_budget = INT32_MAX;  // round trips the cycle climb may take before the scan takes over
     bool small = false;       // whole instance fits in LDS: fused single-workgroup pivot loop
+    int small_threads = 0;    // ... and the width of that workgroup (small_threads_for at mcf_create)
     bool mid = false;         // mid-size instance: persistent single-workgroup pivot loop over global memory (k_solve_mid)
     SmallLayout small_layout{};
     int64_t shard = 0, shards = 1;
@@ -2495,6 +2671,23 @@ bool small_plan(int64_t m_pad, size_t arcw_count, int32_t n_nodes, bool devex, S
     return true;
 }
 
+// Width of the fused loop's workgroup, from the measured table in DESIGN.md (k_solve_small).  One wave per SIMD (256 lanes)
+// reduces over 4 waves instead of 16 and meets 4 arrivals at each barrier; four waves per SIMD (1 024 lanes) hide the LDS round
+// trips of a sweep that reads its arcs from LDS (Devex) and of the passes over a larger tree.  256 lanes won at 65 and 257 tree
+// nodes under Dantzig and the candidate list and at 65 under Devex; 1 024 won at 514 nodes, and under Devex at 257.
+// MCF_SMALL_THREADS = 256 / 1024 forces a width, for mcf_solve (read at mcf_create) and for mcf_solve_batch (read at the call).
+int small_threads_forced() {   // 0: no valid MCF_SMALL_THREADS
+    if (const char* st = std::getenv("MCF_SMALL_THREADS")) {
+        const int w = std::atoi(st);
+        if (w == 256 || w == 1024) return w;
+    }
+    return 0;
+}
+int small_threads_for(int32_t n_nodes, int32_t rule) {
+    if (const int w = small_threads_forced()) return w;
+    return n_nodes <= (rule == MCF_RULE_DEVEX_BLOCK ? 128 : 384) ? 256 : 1024;
+}
+
 // The dynamic-LDS limit of the fused kernels covers `total` bytes on this device.  (The limit is a property of the kernel,
 // not of the handle: it only ever grows, so that handles of different sizes can be alive together -- and share one batched launch.)
 bool small_reserve(int device, uint32_t total) {
@@ -2503,8 +2696,11 @@ bool small_reserve(int device, uint32_t total) {
     int& lds_limit = lds_limits[device & 63];
     std::lock_guard<std::mutex> lock(lds_mu);
     if ((int)total <= lds_limit) return true;
-    hipError_t fe = hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
-    if (fe == hipSuccess) fe = hipFuncSetAttribute(reinterpret_cast<const void*>(k_solve_small_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
+    const void* const fns[] = {reinterpret_cast<const void*>(k_solve_small<256>), reinterpret_cast<const void*>(k_solve_small<1024>),
+                               reinterpret_cast<const void*>(k_solve_small_batch<256>), reinterpret_cast<const void*>(k_solve_small_batch<1024>)};
+    hipError_t fe = hipSuccess;
+    for (const void* fn : fns)
+        if (fe == hipSuccess) fe = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
     if (fe != hipSuccess) { (void)hipGetLastError(); return false; }   // (the refusal must not surface later as some launch's error)
     lds_limit = (int)total;
     return true;
@@ -2673,6 +2869,7 @@ int mcf_create(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, c
     h->small = !h->bpl && !opt.no_fused && !opt.profile && h->shards == 1 &&
                small_plan(im.m_pad, im.arcw.size(), im.n_nodes, opt.rule == MCF_RULE_DEVEX_BLOCK, &h->small_layout) &&
                small_reserve(h->device, h->small_layout.total);
+    if (h->small) h->small_threads = small_threads_for(im.n_nodes, opt.rule);
     // position-space subtree sizes for the cycle scan: every handle but the LDS-resident ones
     const bool scan_ok = opt.cycle_scan >= 0 && im.n_nodes <= kScanMaxNodes && !h->small;  // -1: never scan
     v.bmeta[0] = v.bmeta[1] = nullptr; v.bext[0] = v.bext[1] = nullptr; v.blk_shift = 0; v.blk_cap = 0; v.ncandx = 0; v.candx = nullptr;
@@ -2930,8 +3127,12 @@ int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user,
                 HIP_TRY(h, hipEventRecord(h->loop_ev[0], h->stream));
             }
             if (h->small) {
-                hipLaunchKernelGGL(k_solve_small, dim3(1), dim3(kSmallThreads), h->small_layout.total, h->stream, h->view,
-                                   h->small_layout, h->opt.rule, h->d_cand, cap, h->h_ctx);
+                if (h->small_threads == 1024)
+                    hipLaunchKernelGGL(k_solve_small<1024>, dim3(1), dim3(1024), h->small_layout.total, h->stream, h->view,
+                                       h->small_layout, h->opt.rule, h->d_cand, cap, h->h_ctx);
+                else
+                    hipLaunchKernelGGL(k_solve_small<256>, dim3(1), dim3(256), h->small_layout.total, h->stream, h->view,
+                                       h->small_layout, h->opt.rule, h->d_cand, cap, h->h_ctx);
             }
             else {
                 // eager launches need not run past the cap (a replayed graph has a fixed length: its surplus slots early-exit)
@@ -3115,8 +3316,15 @@ int mcf_solve_batch(mcf_handle* const* handles, int32_t count, const int64_t* ma
     if (!pool.ev[0] && ((e = hipEventCreate(&pool.ev[0])) != hipSuccess || (e = hipEventCreate(&pool.ev[1])) != hipSuccess)) return bail("hipEventCreate", e);
     hipEvent_t* ev = pool.ev;
     if ((e = hipEventRecord(ev[0], s)) != hipSuccess) return bail("hipEventRecord", e);
-    if (!small_jobs.empty())
-        hipLaunchKernelGGL(k_solve_small_batch, dim3((unsigned)small_jobs.size()), dim3(kSmallThreads), lds, s, (const SmallJob*)d_small);
+    if (!small_jobs.empty()) {
+        // Any handle runs at either width: the width belongs to the launch.  A batch keeps 1 024 lanes -- with every CU busy the
+        // narrow workgroup's single wave per SIMD has nothing to hide its LDS latency behind (scripts/batch_small.py per width:
+        // DESIGN.md) -- unless MCF_SMALL_THREADS forces 256.
+        if (small_threads_forced() == 256)
+            hipLaunchKernelGGL(k_solve_small_batch<256>, dim3((unsigned)small_jobs.size()), dim3(256), lds, s, (const SmallJob*)d_small);
+        else
+            hipLaunchKernelGGL(k_solve_small_batch<1024>, dim3((unsigned)small_jobs.size()), dim3(1024), lds, s, (const SmallJob*)d_small);
+    }
     {
         // Two narrow workgroups per CU pay when there are more instances than CUs and the per-pivot passes are short
         // (measured, 512 instances: 1 024 nodes 1.4x, 4 096 nodes 1.06x; with <= 256 instances a narrow workgroup only has
