@@ -88,6 +88,47 @@ extern "C" {
 #define MCF_RULE_CANDIDATE_LIST 2 /* full Dantzig sweep keeps one candidate per pricing workgroup; the following
                                      pivots re-price only that list (simplex_pricing.py:375-542, 419-456) */
 
+/* State of the pricing rules -- what decides WHICH arc enters next, complete enough to implement from (DESIGN.md section 4 has
+ * the same text with its reasons; tests/rule_reference.py is written from it and shares no code with the engine).
+ *
+ * Engine arc order.  Arcs are bucketed by head: bucket x = head / ceil(n / 8), x = 0 .. 7; inside a bucket they are ordered by
+ *   tail, equal tails in the caller's order.  bucket_off[x] = engine index of the first arc of bucket x.
+ * Violation.  viol = -state * (cost + pi[tail] - pi[head]), state +1 at the lower bound (a FORWARD candidate), -1 at capacity
+ *   (BACKWARD), 0 basic; an arc is eligible when viol > 0.
+ *
+ * MCF_RULE_DEVEX_BLOCK
+ *   Granules: granule g of bucket x = the engine arcs bucket_off[x] + len_x * g / 64 .. bucket_off[x] + len_x * (g + 1) / 64 (integer
+ *     division, len_x = arcs of the bucket), g = 0 .. 63.  A block of bg granules, block k, = granules k * bg .. min(k * bg + bg, 64)
+ *     of EVERY bucket; num_blocks = ceil(64 / bg).  mcf_stats.arcs_priced grows by the arcs of the block at every pass.
+ *   Start: block 0, every weight 1, bg = clamp((bs * 64 + m / 2) / m, 1, 64) with bs = block_size when given, else the automatic
+ *     m / 4 (m < 1 000), m / 8 (m < 10 000), m / 16, at least 1.  The tuner is on exactly when the size is automatic
+ *     (devex_tuner 1 / -1: on / off whatever block_size says); its cap is max(bg, min(64, 16 384 * 64 / m)) granules.
+ *   A pass prices the current block: merit = (double)viol * (double)viol / (double)w in IEEE double, w the arc's float32 weight.
+ *     The largest merit enters; among equal merits a backward arc before a forward one (forward wins only when strictly greater),
+ *     then the lowest caller's index.  No eligible arc: empty_blocks += 1, next block (cyclically), and optimal once
+ *     empty_blocks >= num_blocks.  Otherwise empty_blocks = 0 and -- unless devex_stay -- the block index advances (cyclically)
+ *     before the pivot is made.
+ *   After the pivot, in this order:
+ *     (1) a basis swap (the leaving arc is not the entering arc) with 64 swaps counted: RESET, count = 0 (that swap is not
+ *         counted); any other swap: count += 1.  Bound flips never count;
+ *     (2) no reset so far: with 1 024 weights set since the last reset (an arc counts every time it enters): RESET (early; the swap
+ *         count stays); else the entering arc's weight = the tree arcs on its cycle (at least 1), the other weights stay;
+ *     (3) RESET = every weight reads 1.0 again from this pivot on (the entering arc's included), the block index is 0;
+ *     (4) tuner, when on: the pivot counts, and counts as degenerate when it moved no flow OR was a bound flip.  With at least 50
+ *         pivots since the last adaptation: more than 30 % degenerate: bg = max(bg, min(max(bg * 3 / 2, bg + 1), cap)); fewer than
+ *         10 %: bg = max(bg * 3 / 4, 1); the counts start over either way.  A changed bg changes num_blocks; a block index that
+ *         is no longer below num_blocks wraps to 0.
+ * MCF_RULE_CANDIDATE_LIST
+ *   The pricing grid has 8 * k workgroups, k = clamp(ceil(price_blocks / 8), 1, 256) (automatic: k = ceil(m / 8 / 2 048), same
+ *     clamp); engine arc e of bucket x belongs to workgroup (((e >> 2) - (bucket_off[x] >> 2)) >> 8) mod k of that bucket: runs of
+ *     1 024 arcs dealt out in turn.  minor_cap = clamp(k, 3, 32).  The fused LDS loop has no grid: there k = 1 whatever
+ *     price_blocks says.
+ *   A full sweep (arcs_priced += m) keeps, per workgroup, its eligible arc of the largest violation, ties to the lowest caller's
+ *     index; the best of these -- same order -- enters.  None: optimal; only a full sweep ever says so.  Then up to minor_cap
+ *     minor pivots: each re-prices the 8 * k list entries (arcs_priced += 8 * k) under the current potentials and states -- an
+ *     entry that has become basic or is no longer eligible counts as absent, one that is eligible again takes part -- and the best
+ *     enters.  A list without an eligible arc ends the period early, without a pivot; the next pass is a full sweep. */
+
 /* "uncapacitated" marker accepted in cap[] (besides any value >= 2^60) */
 #define MCF_CAP_INF (-1)
 

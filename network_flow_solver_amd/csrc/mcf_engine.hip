@@ -2379,7 +2379,9 @@ int upload_image(mcf_handle* h) {
         if (h->opt.devex_tuner > 0) c.auto_tune = 1; else if (h->opt.devex_tuner < 0) c.auto_tune = 0;
         if (h->opt.devex_stay > 0) c.devex_cyclic = 0;
     }
-    c.minor_cap = mcf_minor_cap(h->price_blocks);
+    // (the fused LDS loop has no pricing grid: its candidate list is one entry per head bucket whatever price_blocks asks for,
+    //  and the minor pivots per sweep follow the length of the list that is really kept)
+    c.minor_cap = mcf_minor_cap(h->small ? MCF_NUM_BUCKETS : h->price_blocks);
     c.climb_budget = h->climb_budget;
     // shallow end points are climbed outright: one round trip per level beats the scan's fixed passes up to ~3 levels at
     // mid size (one plain round) and ~8 levels where the coarse index is used (two passes over up to 16 K words first)

@@ -210,13 +210,21 @@ void apply_all(Emul& e) {
     }
 }
 
+int asked_price_blocks() {
+    const char* s = std::getenv("MCF_EMUL_PRICE_BLOCKS");
+    const int asked = s ? std::atoi(s) : 0;
+    return asked > 0 ? asked : 0;
+}
+
 void init_blocks(Emul& e, int64_t block_size) {
     McfCtx& c = e.ctx;
     const int64_t m = e.im.m;
     mcf_init_block_state(&c, e.rule, m, block_size);
     if (std::getenv("MCF_DEVEX_CYCLIC")) c.devex_cyclic = std::atoi(std::getenv("MCF_DEVEX_CYCLIC"));
     if (std::getenv("MCF_DEVEX_NOTUNE")) c.auto_tune = 0;
-    e.price_blocks = mcf_price_blocks(m, 1, 0);
+    if (std::getenv("MCF_DEVEX_TUNE") && e.rule == MCF_RULE_DEVEX_BLOCK) c.auto_tune = 1;   // mcf_options.devex_tuner = 1
+    // mcf_options.price_blocks: the pricing workgroups a caller asks for (the candidate list's length and minor_cap follow)
+    e.price_blocks = mcf_price_blocks(m, 1, asked_price_blocks());
     c.minor_cap = mcf_minor_cap(e.price_blocks);
 }
 
@@ -353,7 +361,7 @@ void emul_price(void* h, int64_t r, int64_t G, int64_t* key_arc /*[2]*/) {
 // sized for m / G arcs, and a sweep leaves one candidate per (virtual) pricing workgroup.
 void emul_set_shards(void* h, int64_t G) {
     Emul* e = static_cast<Emul*>(h);
-    e->price_blocks = mcf_price_blocks(e->im.m, G, 0);
+    e->price_blocks = mcf_price_blocks(e->im.m, G, asked_price_blocks());
     e->ctx.minor_cap = mcf_minor_cap(e->price_blocks);
 }
 int32_t emul_list_len(void* h) { return static_cast<Emul*>(h)->price_blocks; }

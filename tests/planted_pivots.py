@@ -341,6 +341,15 @@ def pivot_plant(stem: int, t2: int, other: int, above: int = 0, direction: str =
                       stem + above + other + 2, max(dl[u], dl[w]), a + 1, (w + 1) if w < n else 0, args)
 
 
+def cold_plant(inst) -> Planted:
+    """The start basis the engine builds by itself: no real arc basic or at capacity, every node hung on the root by its
+    artificial arc, which carries the node's supply (node -> root) or demand (root -> node; a node of supply 0 points up)."""
+    n, m = inst.n, inst.m
+    none = np.zeros(m, bool)
+    return Planted(inst, none, none.copy(), np.zeros(m, np.int64), np.asarray(inst.supply, np.int64).copy(), np.full(n, n, np.int32),
+                   m + np.arange(n, dtype=np.int64), none.copy(), args=dict(cold=True))
+
+
 # ------------------------------------------------------------------ the reference
 class RefSimplex:
     """Network simplex over a planted state, see the module docstring.  After every ``step()``: ``in_tree``, ``state``, ``flow``,
@@ -419,13 +428,22 @@ class RefSimplex:
         gains = upx == gains_if_up
         return e, ((MCF_INF if cap >= MCF_INF else cap - f) if gains else f), gains
 
-    def step(self) -> bool:
-        """One pivot; False (and status "optimal" / "infeasible") when no arc is eligible."""
+    def select(self) -> int:
+        """The entering arc by Dantzig's rule (caller's index), -1 when no arc is eligible."""
         viol = -self.state * self.reduced_costs()
         e = int(np.argmax(viol)) if self.m else -1          # (the first of the largest: the lowest caller's index)
-        if e < 0 or viol[e] <= 0:
+        return e if e >= 0 and viol[e] > 0 else -1
+
+    def step(self) -> bool:
+        """One pivot; False (and status "optimal" / "infeasible") when no arc is eligible."""
+        e = self.select()
+        if e < 0:
             self.status = "infeasible" if self.art_flow.sum() > 0 else "optimal"
             return False
+        return self.pivot(e)
+
+    def pivot(self, e: int) -> bool:
+        """The pivot on the eligible non-basic arc e: cycle, ratio test, flows, basis, tree arrays.  Always True."""
         fwd = self.state[e] > 0
         first, second = (int(self.tail[e]), int(self.head[e])) if fwd else (int(self.head[e]), int(self.tail[e]))
         par, dep = self.parent, self.depth
