@@ -1355,15 +1355,18 @@ MCF_HD void mcf_pivot_decide(const McfView& v, const McfPaths& pp, const McfCycl
 
     const int32_t S = rq.size, a0 = (result == 1 ? pp.ppos1 : pp.ppos2)[k];
     // v_in is the entering arc's end point on the other side: its record and position were read at the start
-    const McfNode rvin = result == 1 ? cy.r0w : cy.r0u;
+    // (selects between loaded fields, not a record loaded through a selected address: a cycle held in registers -- the LDS
+    //  loop's -- must not be forced into private memory)
+    const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth, zu0 = cy.r0u.size, zw0 = cy.r0w.size;
+    const int32_t vin_depth = result == 1 ? dw0 : du0, vin_size = result == 1 ? zw0 : zu0;
     const int32_t pvin = result == 1 ? cy.p0w : cy.p0u;
-    c->pv_vin_depth = rvin.depth;
+    c->pv_vin_depth = vin_depth;
     // depth change of the first piece of the re-rooted subtree (u_in and what hangs below it): with k == 0 that piece is all
     // of T2 and the segment table is {t2_new, t2_old, S, this} -- the apply pass then needs no look-up in it (mcf_apply_source)
-    c->pv_dd0 = rvin.depth + 1 - (result == 1 ? cy.r0u : cy.r0w).depth;
+    c->pv_dd0 = vin_depth + 1 - (result == 1 ? du0 : dw0);
     // insertion point in OLD coordinates: directly behind v_in, or at the end of
     // v_in's block -- whichever moves fewer array elements
-    const int32_t tA = pvin + 1, tB = pvin + rvin.size;
+    const int32_t tA = pvin + 1, tB = pvin + vin_size;
     const int32_t costA = tA <= a0 ? a0 - tA : tA - (a0 + S);
     const int32_t costB = tB <= a0 ? a0 - tB : tB - (a0 + S);
     const int32_t t = costA <= costB ? tA : tB;

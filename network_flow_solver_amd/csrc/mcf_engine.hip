@@ -2,10 +2,11 @@
 //
 // One pivot, by instance size (mcf_create picks; all paths share mcf_core.h and give the same pivot sequence):
 //
-//   k_solve_small   whole instance in LDS: one persistent workgroup -- 256 lanes (one wave per SIMD) for the smaller trees,
-//                   1 024 beyond and in batches (small_threads_for) -- prices (Dantzig / candidate list: the arcs' invariant
+//   k_solve_small   whole instance in LDS: one persistent workgroup -- 256 lanes (one wave per SIMD), 1 024 when
+//                   MCF_SMALL_THREADS asks (small_threads_for) -- prices (Dantzig / candidate list: the arcs' invariant
 //                   data in registers, 10 or 3 arcs per lane by width; Devex: from LDS), pivots (the lanes stride over the
-//                   tree nodes in the cycle search, wave 0 runs the ratio tests) and updates until the solve ends.
+//                   tree nodes in the cycle search; every wave runs the ratio tests and takes the pivot's scalar decisions
+//                   itself, the control block in its registers) and updates until the solve ends.
 //   k_solve_mid     <= 1 536 nodes: one persistent workgroup over global (L2-resident) state -- prices a Devex
 //                   block / re-prices the candidate list / sweeps a small arc list, pivots, permutes, patches.
 //                   (both also as k_solve_small_batch / k_solve_mid_batch: MANY independent instances in one launch, one
@@ -113,6 +114,41 @@ __device__ __forceinline__ void block_argmax(int64_t& key, int64_t& arc) {
         arc = has ? s_arc[has ? lane : 0] : -1;
         wave_argmax(key, arc);
     }
+}
+
+// Block-wide arg-max whose result EVERY wave holds, uniformly (scalar registers): after the one barrier each wave reads all
+// the per-wave candidates and reduces them itself, so nobody waits for wave 0 to publish the winner.  The caller keeps a
+// barrier between this call and the next (the per-wave slots are rewritten then).
+template <int THREADS>
+__device__ __forceinline__ void block_argmax_all(int64_t& key, int64_t& arc) {
+    __shared__ int64_t s_key[THREADS / 64];
+    __shared__ int64_t s_arc[THREADS / 64];
+    wave_argmax(key, arc);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { s_key[wave] = key; s_arc[wave] = arc; }
+    __syncthreads();   // per-wave candidates -> every wave's reduction over them
+    const bool has = lane < THREADS / 64;
+    key = has ? s_key[has ? lane : 0] : 0;
+    arc = has ? s_arc[has ? lane : 0] : -1;
+    wave_argmax(key, arc);
+}
+
+// A value every lane of the wave holds alike.  SCALAR: moved to scalar registers (64-bit values in two halves) -- branches on
+// it are scalar branches, and it costs no vector register across the loop; !SCALAR: left where the compiler has it.
+// (Which of the two the fused LDS loop asks for depends on its width, see SmallScalarControl.)
+template <bool SCALAR> __device__ __forceinline__ int32_t uni32(int32_t x) {
+    if constexpr (SCALAR) return __builtin_amdgcn_readfirstlane(x);
+    else return x;
+}
+template <bool SCALAR> __device__ __forceinline__ int64_t uni64(int64_t x) {
+    if constexpr (SCALAR) {
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+        return (int64_t)(((uint64_t)hi << 32) | lo);
+    } else return x;
+}
+template <bool SCALAR> __device__ __forceinline__ McfNode uni_node(const McfNode& r) {
+    return McfNode{uni32<SCALAR>(r.parent), uni32<SCALAR>(r.pred), uni32<SCALAR>(r.size), uni32<SCALAR>(r.depth)};
 }
 
 // Candidate cache (McfView::candx): the record of this pricing workgroup's candidate -- end points, state and exact
@@ -1521,12 +1557,12 @@ __device__ __forceinline__ bool pivot_climb_2lanes(const McfView& v, McfCycle* o
 // pivot: the same mcf_pivot_begin / mcf_pivot_decide / mcf_pivot_finish; apply: all lanes through the
 // same mcf_apply_one) and copies the state back.  Same arc sets, same tie rule, same core functions
 // as the three-kernel path, so the pivot sequence is identical -- at every width: the workgroup is
-// THREADS lanes wide: 256, one wave per SIMD, for the smaller trees, 1 024 beyond (small_threads_for; MCF_SMALL_THREADS).
+// THREADS lanes wide: 256, one wave per SIMD, or 1 024 when forced (small_threads_for; MCF_SMALL_THREADS).
 struct SmallLayout {
-    uint32_t tail, head, cost, orig, state, weight, arcw, pi, node, order0, order1, pos0, pos1, path1, path2, ppos1, ppos2, rec1, rec2, seg, ctx, total;
+    uint32_t tail, head, cost, orig, state, weight, arcw, pi, node, order0, order1, pos0, pos1, path1, path2, ppos1, ppos2, rec1, rec2, seg, scratch, ctx, total;
 };
 
-constexpr int kSmallMaxLds = 158 * 1024;   // dynamic LDS of the fused small-instance loop (160 KB per CU, a little static on top)
+constexpr int kSmallMaxLds = 156 * 1024;   // dynamic LDS of the fused small-instance loop (160 KB per CU, under 4 KB static on top)
 constexpr int kSmallCycleMaxNodes = 1024;  // node-parallel cycle search up to this many tree nodes (strided over the lanes)
 
 // Arcs of a head bucket that one lane keeps in registers (tail, head, cost, orig: 4 VGPRs each).  THREADS / 8 lanes share a
@@ -1539,6 +1575,13 @@ constexpr bool kRegSweep = false;
 #else
 constexpr bool kRegSweep = true;
 #endif
+// Where every wave keeps its copy of the control block: one wave per SIMD (256 lanes) has 512 vector registers to itself and
+// leaves the control block where the compiler puts it; forced into the ~100 scalar registers, control block, pivot
+// descriptor and the view's pointers do not fit, and their spills (v_writelane / v_readlane inside the loop) cost more than
+// the mailbox did: 5.60 us per pivot against 4.80, the parent's 5.60.  Four waves per SIMD (1 024 lanes) have
+// 128 vector registers each, nearly all in use: there the control block goes to scalar registers, or it would spill to
+// scratch memory.
+template <int THREADS> struct SmallScalarControl { static constexpr bool value = THREADS > 256; };
 template <int THREADS> struct SmallRegArcs { static constexpr int value = THREADS <= 256 ? 10 : (THREADS <= 512 ? 5 : 3); };
 
 template <int THREADS>
@@ -1570,11 +1613,16 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t 
 // reductions for the whole cycle, whatever its length, instead of one dependent round per tree level on one or two lanes
 // (the 2-lane climb was 53 % of a pivot on netgen_8_08a).  Same path arrays, same ratio-test winners (first side: lowest
 // index among equal residuals, second side: highest), hence the same pivots.  All threads call it; one barrier inside;
-// lane 0 gets the finished McfCycle.  Lane x takes the nodes x, x + THREADS, ... (netgen_8_08a has 257 tree nodes: two
+// every wave gets the finished McfCycle.  Lane x takes the nodes x, x + THREADS, ... (netgen_8_08a has 257 tree nodes: two
 // passes at 256 lanes), so the tree need not fit the workgroup; the caller gates on kSmallCycleMaxNodes.
-// After the barrier wave 0 alone finishes: the per-wave counts are one LDS read per lane summed over scalar lane reads, and
-// each side's ratio test is one DPP min reduction per 64 path indices with the winner taken from a ballot -- two independent
-// chains in one wave, which overlap, and no second barrier as handing a side to another wave would need.
+// After the barrier EVERY wave finishes for itself, uniformly: the per-wave counts are one LDS read per lane summed over scalar
+// lane reads, each side's ratio test is one DPP min reduction per 64 path indices with the winner taken from a ballot -- two
+// independent chains, which overlap -- and the join is two broadcast reads.  The finished cycle is then in every wave's scalar
+// registers: no McfCycle goes through LDS, and nobody waits for wave 0 to publish it.
+// The end points' positions, depths and records come from the caller's registers (mcf_pivot_begin_t<true> read them): the
+// finish pass of a faster wave may already be rewriting node[u_in] when a slower one gets here.  For the same reason the
+// residuals and the by-depth table have LDS of their own (SmallLayout::scratch, 20 B per tree node) and not the segment
+// table's, which the finish pass fills.
 struct SmallCycleAcc {
     int32_t c1[16], c2[16];   // one-sided ancestors per wave, first / second side
 };
@@ -1600,20 +1648,19 @@ __device__ __forceinline__ void small_ratio_side(const int64_t* res, int32_t n, 
     *d_out = d; *k_out = k;
 }
 
+// `cy` as mcf_pivot_begin_t<true> left it (in registers, uniform); on return the finished cycle, uniform in every wave.
 template <int THREADS>
-__device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycleAcc& A, McfCycle* out) {
-    const McfCtx* c = v.ctx;
+__device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycleAcc& A, int64_t* scratch, McfCycle& cy) {
+    constexpr bool kScalar = SmallScalarControl<THREADS>::value;
+    const McfCtx* c = v.ctx;   // (the caller's registers)
     const int32_t* pcur = c->cur ? v.posbuf[1] : v.posbuf[0];
-    const int32_t first = c->pv_first, second = c->pv_second;      // (uniform: LDS broadcast reads)
-    // (only the depths are carried through the pass; lane 0 reads the whole records again at the end -- kept alive across the
-    //  pass they were spilled to scratch, the only private memory this kernel used)
-    const int32_t du0 = v.node[first].depth, dw0 = v.node[second].depth;
-    const int32_t pu = pcur[first], pw = pcur[second];
+    const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth;
+    const int32_t pu = cy.p0u, pw = cy.p0w;
     const int32_t wave = (int32_t)threadIdx.x >> 6;
     const int32_t N = v.n_nodes;
-    // scratch in the segment table's LDS (the finish pass only fills it afterwards): residual per path index and side, and
-    // the common ancestors by depth (root .. join occupy depths 0 .. depth[join], one node each)
-    int64_t* const res1 = reinterpret_cast<int64_t*>(v.seg);
+    // scratch: residual per path index and side, and the common ancestors by depth (root .. join occupy depths
+    // 0 .. depth[join], one node each)
+    int64_t* const res1 = scratch;
     int64_t* const res2 = res1 + N;
     int32_t* const by_depth = reinterpret_cast<int32_t*>(res2 + N);
     int32_t n1w = 0, n2w = 0;   // this wave's one-sided ancestors, over its passes
@@ -1644,42 +1691,37 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         n2w += (int32_t)__popcll(__ballot(h2));
     }
     if ((threadIdx.x & 63) == 0) { A.c1[wave] = n1w; A.c2[wave] = n2w; }
-    __syncthreads();   // path / record / residual / by_depth entries and the per-wave counts -> wave 0's ratio tests
-#if defined(MCF_SMALL_SERIAL_RATIO)   // A/B build: lane 0 sums the counts and runs both ratio tests as scalar loops
-    if (threadIdx.x == 0) {
-        int32_t n1 = 0, n2 = 0;
-        for (int32_t q = 0; q < THREADS / 64; ++q) { n1 += A.c1[q]; n2 += A.c2[q]; }
-        int64_t d1 = MCF_INF, d2 = MCF_INF;
-        int32_t k1 = -1, k2 = -1;
-        for (int32_t i = 0; i < n1; ++i) { const int64_t r = res1[i]; if (r < d1) { d1 = r; k1 = i; } }
-        for (int32_t i = 0; i < n2; ++i) { const int64_t r = res2[i]; if (r <= d2) { d2 = r; k2 = i; } }
-        const int32_t lane = 0;
+    __syncthreads();   // path / record / residual / by_depth entries and the per-wave counts -> every wave's ratio tests, its
+                       // decision and the finish pass
+    int32_t n1 = 0, n2 = 0;
+    int64_t d1, d2;
+    int32_t k1, k2;
+#if defined(MCF_SMALL_SERIAL_RATIO)   // A/B build: the counts and both ratio tests as scalar loops (every lane alike)
+    for (int32_t q = 0; q < THREADS / 64; ++q) { n1 += A.c1[q]; n2 += A.c2[q]; }
+    d1 = MCF_INF; d2 = MCF_INF; k1 = -1; k2 = -1;
+    for (int32_t i = 0; i < n1; ++i) { const int64_t r = res1[i]; if (r < d1) { d1 = r; k1 = i; } }
+    for (int32_t i = 0; i < n2; ++i) { const int64_t r = res2[i]; if (r <= d2) { d2 = r; k2 = i; } }
 #else
-    if (wave == 0) {
+    {
         constexpr int kWaves = THREADS / 64;
-        const int32_t lane = (int32_t)threadIdx.x;
+        const int32_t lane = (int32_t)(threadIdx.x & 63);
         const int32_t c1 = lane < kWaves ? A.c1[lane] : 0, c2 = lane < kWaves ? A.c2[lane] : 0;   // one read, then scalar lane reads
-        int32_t n1 = 0, n2 = 0;
 #pragma unroll
         for (int q = 0; q < kWaves; ++q) { n1 += __builtin_amdgcn_readlane(c1, q); n2 += __builtin_amdgcn_readlane(c2, q); }
         // the ratio tests, exactly the climb's: first side -- strictly smaller wins (lowest index among equals), second side --
         // smaller or equal wins (highest index among equals)
-        int64_t d1, d2;
-        int32_t k1, k2;
         small_ratio_side<false>(res1, n1, &d1, &k1);
         small_ratio_side<true>(res2, n2, &d2, &k2);
-#endif
-        if (lane == 0) {
-            const int32_t jn = by_depth[du0 - n1];   // the join: the common ancestor right above the first side's path
-            const McfNode rj = v.node[jn];
-            out->d1 = d1; out->k1 = k1; out->d2 = d2; out->k2 = k2;
-            out->n1 = n1; out->n2 = n2;
-            out->u = jn; out->w = jn; out->ru = rj; out->rw = rj;
-            out->pu = pcur[jn]; out->pw = out->pu; out->su = out->pu; out->sw = out->pu;
-            out->p0u = pu; out->p0w = pw; out->s0u = pu; out->s0w = pw; out->r0u = v.node[first]; out->r0w = v.node[second];
-            out->small = 0;
-        }
     }
+#endif
+    const int32_t jn = uni32<kScalar>(by_depth[du0 - n1]);   // the join: the common ancestor right above the first side's path
+    const McfNode rj = uni_node<kScalar>(v.node[jn]);        // (the finish pass leaves the join's record alone)
+    const int32_t pj = uni32<kScalar>(pcur[jn]);
+    cy.d1 = uni64<kScalar>(d1); cy.k1 = uni32<kScalar>(k1); cy.d2 = uni64<kScalar>(d2); cy.k2 = uni32<kScalar>(k2);
+    cy.n1 = n1; cy.n2 = n2;
+    cy.u = jn; cy.w = jn; cy.ru = rj; cy.rw = rj;
+    cy.pu = pj; cy.pw = pj; cy.su = pj; cy.sw = pj;
+    // (p0u / p0w / s0u / s0w / r0u / r0w stay what mcf_pivot_begin_t<true> read)
 }
 
 // ------------------------------------------------------------------ pricing sweep of the LDS loop
@@ -1744,6 +1786,64 @@ __device__ __forceinline__ void half_wave_argmax(int64_t& key, int64_t& arc) {
     arc = b;
 }
 
+// ---- the control block in registers (LDS loop), on a dense view without resident reduced costs.
+// Control state: every McfCtx field that mcf_pivot_begin_t, mcf_pivot_decide or the loop itself changes AND a later pivot
+// reads -- carried in scalar registers across the loop, written back once after it (small_ctx_store).
+#define MCF_SMALL_CTL_32(F)                                                                                                   \
+    F(status) F(unbounded_arc) F(empty_blocks) F(num_blocks) F(block_granules) F(tn_total) F(tn_degenerate)                   \
+    F(swaps_since_reset) F(wlist_n) F(wreset) F(minor_left) F(cur) F(pending_flip) F(prev_lo) F(prev_hi) F(apply) F(lo) F(hi) \
+    F(nchg) F(stage) F(arena) F(rebuild)
+#define MCF_SMALL_CTL_64(F)                                                                                                   \
+    F(pivots) F(degenerate) F(bound_flips) F(arcs_priced) F(nodes_moved) F(subtree_nodes) F(cycle_arcs) F(block_size)         \
+    F(block_index) F(tn_last_adapt) F(minor_pivots) F(major_sweeps)
+// The descriptor of ONE pivot: written by begin / decide, read by that pivot's finish and apply passes, dead afterwards.  In
+// registers only while the pivot lasts; lane 0 copies it into the LDS image as the pivot is decided (small_desc_store: stores
+// nobody waits for), so that the control block a launch leaves behind is the one the other paths leave.
+#define MCF_SMALL_DESC_BEGIN_32(F) F(pv_e) F(pv_s) F(pv_first) F(pv_second) F(pv_t2n)
+#define MCF_SMALL_DESC_BEGIN_64(F) F(pv_rc) F(pv_cap) F(pv_flow)
+#define MCF_SMALL_DESC_DECIDE_32(F) F(pv_n1) F(pv_n2) F(pv_result)
+#define MCF_SMALL_DESC_DECIDE_64(F) F(pv_delta)
+#define MCF_SMALL_DESC_SWAP_32(F)                                                                                             \
+    F(pv_k) F(pv_vin) F(pv_leave) F(pv_leave_state) F(pv_tail_in_t2) F(pv_vin_depth) F(pv_dd0) F(t2_old) F(t2_new) F(t2_size)  \
+    F(nseg)
+#define MCF_SMALL_DESC_SWAP_64(F) F(sigma)
+template <bool SCALAR> __device__ __forceinline__ void small_ctx_uniform(McfCtx& x) {
+#define MCF_F32(f) x.f = uni32<SCALAR>(x.f);
+#define MCF_F64(f) x.f = uni64<SCALAR>(x.f);
+    MCF_SMALL_CTL_32(MCF_F32) MCF_SMALL_CTL_64(MCF_F64)
+    MCF_SMALL_DESC_BEGIN_32(MCF_F32) MCF_SMALL_DESC_BEGIN_64(MCF_F64)
+    MCF_SMALL_DESC_DECIDE_32(MCF_F32) MCF_SMALL_DESC_DECIDE_64(MCF_F64)
+    MCF_SMALL_DESC_SWAP_32(MCF_F32) MCF_SMALL_DESC_SWAP_64(MCF_F64)
+    x.pv_t2node = uni32<SCALAR>(x.pv_t2node);
+#undef MCF_F32
+#undef MCF_F64
+}
+#define MCF_FST(f) c->f = x.f;
+__device__ __forceinline__ void small_ctx_store(McfCtx* c, const McfCtx& x) {
+    MCF_SMALL_CTL_32(MCF_FST) MCF_SMALL_CTL_64(MCF_FST)
+}
+// What mcf_pivot_begin_t (on a candidate) and mcf_pivot_decide store, under the conditions they store it: decide leaves at
+// once on an unbounded cycle (the status then says so), writes the swap's fields for a basis swap only, and the preview of a
+// one-node T2 (with the first end point's adjacency range -- here never fetched: the launch's constant) only for such a T2.
+__device__ __forceinline__ void small_desc_store(McfCtx* c, const McfCtx& x, int64_t adj2, int64_t adj3) {
+    MCF_SMALL_DESC_BEGIN_32(MCF_FST) MCF_SMALL_DESC_BEGIN_64(MCF_FST)
+    if (x.status != MCF_RUNNING) return;
+    MCF_SMALL_DESC_DECIDE_32(MCF_FST) MCF_SMALL_DESC_DECIDE_64(MCF_FST)
+    if (x.stage != 2) return;
+    MCF_SMALL_DESC_SWAP_32(MCF_FST) MCF_SMALL_DESC_SWAP_64(MCF_FST)
+    if (x.pv_t2n) {
+        c->pv_t2node = x.pv_t2node;
+        if (x.pv_result != 1) { c->pv_adj[0] = adj2; c->pv_adj[1] = adj3; }
+    }
+}
+#undef MCF_FST
+template <bool SCALAR> __device__ __forceinline__ void uni_cycle(McfCycle& y) {
+    y.d1 = uni64<SCALAR>(y.d1); y.d2 = uni64<SCALAR>(y.d2); y.k1 = uni32<SCALAR>(y.k1); y.k2 = uni32<SCALAR>(y.k2); y.n1 = uni32<SCALAR>(y.n1); y.n2 = uni32<SCALAR>(y.n2);
+    y.u = uni32<SCALAR>(y.u); y.w = uni32<SCALAR>(y.w); y.pu = uni32<SCALAR>(y.pu); y.pw = uni32<SCALAR>(y.pw); y.su = uni32<SCALAR>(y.su); y.sw = uni32<SCALAR>(y.sw);
+    y.ru = uni_node<SCALAR>(y.ru); y.rw = uni_node<SCALAR>(y.rw); y.p0u = uni32<SCALAR>(y.p0u); y.p0w = uni32<SCALAR>(y.p0w); y.s0u = uni32<SCALAR>(y.s0u); y.s0w = uni32<SCALAR>(y.s0w);
+    y.r0u = uni_node<SCALAR>(y.r0u); y.r0w = uni_node<SCALAR>(y.r0w); y.small = uni32<SCALAR>(y.small);
+}
+
 // The whole solve of one LDS-resident instance by one workgroup of THREADS lanes (k_solve_small: one instance per launch;
 // k_solve_small_batch: one instance per workgroup of the launch)
 template <int THREADS>
@@ -1784,6 +1884,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     v.psz[1] = nullptr;
     v.reach = nullptr;
     v.bmeta[0] = nullptr; v.bmeta[1] = nullptr; v.candx = nullptr; v.dirty = nullptr; v.dirty_hdr = nullptr;   // (folds the blocked list etc. away)
+    v.rcache = nullptr; v.adj_off = nullptr;   // (a handle on this path keeps no resident reduced costs, mcf_create: folds their branches away)
 
     // (All fourteen arrays' loads in flight together -- one fused loop, 4- or 16-byte loads -- was measured SLOWER than these
     //  plain loops: 131 / 125 us against 117 us per 20-pivot launch.)
@@ -1804,7 +1905,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     __syncthreads();
     STAMP(0);
 
-    McfCtx* c = v.ctx;
+    McfCtx* const c = v.ctx;   // the LDS image of the control block: read once below, written once after the loop
     if (threadIdx.x == 0) arm_ctx(c, cap);  // (what k_ctl does for the other paths; visible after the barrier below)
     // Devex: the host-made granule table in LDS (blocks move and resize under the tuner); other rules: whole buckets
     __shared__ int32_t s_gran[MCF_NUM_BUCKETS][MCF_GRANULES + 1];
@@ -1823,6 +1924,17 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     __shared__ int64_t s_lk[MCF_NUM_BUCKETS], s_la[MCF_NUM_BUCKETS];
     if (listing && threadIdx.x < MCF_NUM_BUCKETS) { s_lk[threadIdx.x] = list[threadIdx.x].key; s_la[threadIdx.x] = list[threadIdx.x].arc; }
     __syncthreads();   // arm_ctx, the granule table and the list -> every lane's reads below and in the loop
+    // arcs one sweep prices: over the eight buckets, the arcs below each granule boundary (Devex: the block's share follows from
+    // two entries; other rules sweep whole buckets: a constant of the launch)
+    __shared__ int32_t s_gsum[MCF_GRANULES + 1];
+    if (threadIdx.x <= MCF_GRANULES && (devex || threadIdx.x == 0 || threadIdx.x == MCF_GRANULES)) {
+        int32_t sum = 0;
+        for (int x = 0; x < MCF_NUM_BUCKETS; ++x) sum += s_gran[x][threadIdx.x];
+        s_gsum[threadIdx.x] = sum;
+    }
+    __syncthreads();   // the sums -> every wave's reads (once here, and per sweep under Devex)
+    constexpr bool kScalar = SmallScalarControl<THREADS>::value;
+    const int64_t priced_all = uni32<kScalar>(s_gsum[MCF_GRANULES] - s_gsum[0]);
 
     // ---- lane map of the sweep: THREADS / 8 lanes per head bucket, all eight buckets at once
     constexpr int kPer = THREADS / MCF_NUM_BUCKETS;
@@ -1843,22 +1955,43 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         r_tail[k] = on ? v.tail[i] : 0; r_head[k] = on ? v.head[i] : 0; r_cost[k] = on ? v.cost[i] : 0; r_orig[k] = on ? v.orig[i] : 0;
         r_n += on ? 1 : 0;
     }
+    // ---- control in registers.  Every wave carries the control block itself -- a private McfCtx whose fields live in scalar
+    // registers -- and takes every scalar decision of a pivot itself, from broadcast LDS reads: mcf_pivot_begin_t,
+    // mcf_pivot_decide, mcf_pivot_finish and mcf_apply_one run on that private copy (v.ctx points to it), the very functions
+    // of the other paths.  Nothing goes through an LDS mailbox, no wave waits for lane 0, and the barriers that only ordered
+    // "lane 0 wrote, everybody reads" are gone.  The LDS image is written once after the loop.
+    // THE RULE that replaces those barriers: between two barriers no wave reads an LDS location that a faster wave can write
+    // before the next barrier.  Its instances here:
+    //   * the parallel search's residual / by-depth scratch has LDS of its own, not the segment table's (the finish pass
+    //     of a faster wave fills that table while a slower one still runs its ratio tests);
+    //   * the end points' records and positions (r0u / r0w / p0u / p0w) are begin's reads, taken before the search barrier:
+    //     the finish pass rewrites node[u_in];
+    //   * begin reads arcw[e].flow and state[e], finish writes them: all of begin's reads precede the search barrier;
+    //   * an iteration that pivots on nothing (empty Devex block, exhausted list, budget, optimal) takes one barrier before
+    //     it continues: the next iteration rewrites the per-wave arg-max slots and the candidate list.
+    // Rule-specific bookkeeping in memory -- the entering arc's Devex weight and the list of touched weights -- is stored by
+    // mcf_pivot_decide with the same value from every lane; nothing reads it before the next barrier.  A tuner step
+    // (block_granules / num_blocks) is computed in every wave alike.
+    McfCtx cx = *c;            // (broadcast reads; the fields the loop never touches are dead after this)
+    small_ctx_uniform<kScalar>(cx);
+    cx.max_pivots = uni64<kScalar>(cx.max_pivots); cx.minor_cap = uni32<kScalar>(cx.minor_cap); cx.auto_tune = uni32<kScalar>(cx.auto_tune);
+    cx.devex_cyclic = uni32<kScalar>(cx.devex_cyclic); cx.max_granules = uni32<kScalar>(cx.max_granules);
+    v.ctx = &cx;
+    const int64_t adj2 = uni64<kScalar>(cx.pv_adj[2]), adj3 = uni64<kScalar>(cx.pv_adj[3]);   // (never fetched on this path: whatever the image holds)
+    int64_t* const scratch = reinterpret_cast<int64_t*>(smem + L.scratch);
+    __shared__ McfCycle s_cy;   // the two-lane climb's result (the rare path: shallow end points, trees above kSmallCycleMaxNodes)
+    __shared__ int s_ok;
+    __shared__ SmallCycleAcc s_acc;
     for (;;) {
-        // uniform control values are read BEFORE a barrier: lane 0 rewrites them later in this very
-        // iteration (mcf_pivot_begin / mcf_pivot_decide), and a lagging wave must not see the new values
-        const int32_t status_now = c->status;
-        const bool minor = listing && c->minor_left > 0;
+        if (cx.status != MCF_RUNNING) break;   // (uniform: every wave leaves together)
+        const bool minor = listing && cx.minor_left > 0;
         int32_t bg0 = 0, bg1 = MCF_GRANULES;  // Devex: granule range of the current block
         if (devex) {
-            const int32_t bg = c->block_granules;
-            bg0 = (int32_t)c->block_index * bg;
+            const int32_t bg = cx.block_granules;
+            bg0 = (int32_t)cx.block_index * bg;
             if (bg0 >= MCF_GRANULES) bg0 = 0;
             bg1 = bg0 + bg < MCF_GRANULES ? bg0 + bg : MCF_GRANULES;
         }
-        __syncthreads();   // every lane's reads of status / minor_left / block_index -> lane 0's writes below.  (Only a candidate-
-                           // list minor iteration has no other barrier in front of those writes; dropping it elsewhere was
-                           // tried and bought nothing)
-        if (status_now != MCF_RUNNING) break;
         // ---- price: the arc set of k_price for shard 0 of 1
         int64_t key = 0, arc = -1;
         if (!minor) {
@@ -1889,6 +2022,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             }
         }
         STAMP(1);
+        // ---- arg-max: (key, arc) uniform in every wave afterwards
         if (listing) {
             if (!minor) {   // the list: each head bucket's best
                 if constexpr (kPer >= 64) {
@@ -1908,85 +2042,93 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
                     half_wave_argmax(key, arc);
                     if (pl == 0) { s_lk[px] = key; s_la[px] = arc; }
                 }
-                __syncthreads();   // the new list -> wave 0's arg-max over it
+                __syncthreads();   // the new list -> every wave's arg-max over it
             }
-            // lanes 0-7 take one listed arc each (a minor iteration re-prices it), wave 0 reduces: mcf_cand_better is a
-            // total order, so the winner is the one the lane-by-lane scan found
-            if (threadIdx.x < 64) {
-                key = 0; arc = -1;
-                if (threadIdx.x < MCF_NUM_BUCKETS) {
-                    arc = s_la[threadIdx.x];
-                    key = minor ? mcf_minor_key(v, arc) : s_lk[threadIdx.x];
-                    if (key <= 0) { key = 0; arc = -1; }
-                }
-                wave_argmax(key, arc);
+            // lanes 0-7 of every wave take one listed arc each (a minor iteration re-prices it), the wave reduces:
+            // mcf_cand_better is a total order, so the winner is the one the lane-by-lane scan found
+            const int32_t l = (int32_t)(threadIdx.x & 63);
+            key = 0; arc = -1;
+            if (l < MCF_NUM_BUCKETS) {
+                arc = s_la[l];
+                key = minor ? mcf_minor_key(v, arc) : s_lk[l];
+                if (key <= 0) { key = 0; arc = -1; }
             }
+            wave_argmax(key, arc);
         } else {
-            block_argmax<THREADS>(key, arc);
+            block_argmax_all<THREADS>(key, arc);
         }
         STAMP(2);
-        // ---- pivot: one lane walks, everything it touches is in LDS
-        if (threadIdx.x == 0) {
-            if (c->pivots < c->max_pivots) {
-                int64_t priced = 0;
-                for (int x = 0; x < MCF_NUM_BUCKETS; ++x) priced += s_gran[x][bg1] - s_gran[x][bg0];
-                c->arcs_priced += minor ? MCF_NUM_BUCKETS : priced;
-            }
+        // ---- pivot: every wave decides, everything it touches is in LDS or in its registers
+        if (cx.pivots < cx.max_pivots)
+            cx.arcs_priced += minor ? (int64_t)MCF_NUM_BUCKETS : (devex ? (int64_t)uni32<kScalar>(s_gsum[bg1] - s_gsum[bg0]) : priced_all);
+        MCF_PSTAMP(12);
+        // begin: the arc's record, then its end points' records, positions and potentials -- two broadcast round trips; the
+        // records the decision will need are fetched here (WITH_CY)
+        McfCycle cy;
+        const bool go = mcf_pivot_begin_t<true>(v, key, arc, rule, nullptr, &cy);
+        small_ctx_uniform<kScalar>(cx);
+        MCF_PSTAMP(13);
+        if (!go) {   // nothing to pivot on: uniform, every wave takes this way
+            STAMP(3);
+            __syncthreads();   // this iteration's reads of the per-wave arg-max slots and of the list -> the next one's writes
+            STAMP(5);
+            continue;
         }
+        cy.r0u = uni_node<kScalar>(cy.r0u); cy.r0w = uni_node<kScalar>(cy.r0w);
+        cy.ru = cy.r0u; cy.rw = cy.r0w;
+        cy.p0u = uni32<kScalar>(cy.p0u); cy.p0w = uni32<kScalar>(cy.p0w);
+        cy.s0u = cy.p0u; cy.s0w = cy.p0w; cy.pu = cy.p0u; cy.pw = cy.p0w; cy.su = cy.p0u; cy.sw = cy.p0w;
+        const int32_t deep = cy.r0u.depth > cy.r0w.depth ? cy.r0u.depth : cy.r0w.depth;
         // Cycle search: every lane takes nodes (small_cycle_parallel) while the tree is small enough; else lanes 0 and 1 climb
-        // one side each (pivot_climb_2lanes).  Lane 0 does the scalar rest.
-        __shared__ int s_go, s_deep;
-        __shared__ McfCycle s_cy;
-        __shared__ SmallCycleAcc s_acc;
-        if (threadIdx.x == 0) {
-            MCF_PSTAMP(12);
-            s_go = mcf_pivot_begin(v, key, arc, rule) ? 1 : 0;
-            if (s_go) { const int32_t du = v.node[c->pv_first].depth, dw = v.node[c->pv_second].depth; s_deep = du > dw ? du : dw; }
-            MCF_PSTAMP(13);
-        }
-        __syncthreads();   // lane 0's s_go / s_deep / pv_first / pv_second (and apply = 0, stage = 0) -> every lane
-        if (s_go) {
-            // (end points that hang close to the root -- the first pivots of a cold start -- are climbed: a level or two of
-            //  LDS round trips beat the parallel search's fixed cost: 144 K vs 126 K pivots/s over the first 25 pivots)
+        // one side each (pivot_climb_2lanes) and every wave reads their result.
+        // (end points that hang close to the root -- the first pivots of a cold start -- are climbed: a level or two of
+        //  LDS round trips beat the parallel search's fixed cost: 144 K vs 126 K pivots/s over the first 25 pivots)
 #if defined(MCF_SMALL_CLIMB)   // A/B build: always the two-lane climb
-            if (false) {
+        if (false) {
 #else
-            if (v.n_nodes <= kSmallCycleMaxNodes && s_deep > 3) {
+        if (v.n_nodes <= kSmallCycleMaxNodes && deep > 3) {
 #endif
-                small_cycle_parallel<THREADS>(v, s_acc, &s_cy);
-                if (threadIdx.x == 0) { MCF_PSTAMP(15); mcf_pivot_decide(v, mcf_view_paths(v), s_cy); MCF_PSTAMP(16); }
-            } else if (threadIdx.x < 2) {
+            small_cycle_parallel<THREADS>(v, s_acc, scratch, cy);   // (one barrier inside)
+            MCF_PSTAMP(15);
+            mcf_pivot_decide(v, mcf_view_paths(v), cy);
+        } else {
+            if (threadIdx.x < 2) {
                 const bool ok = pivot_climb_2lanes(v, &s_cy);
-                if (threadIdx.x == 0) {
-                    if (ok) mcf_pivot_decide(v, mcf_view_paths(v), s_cy);
-                    else c->status = MCF_INTERNAL_ERROR;
-                }
+                if (threadIdx.x == 0) s_ok = ok ? 1 : 0;
+            }
+            __syncthreads();   // the climbed paths, s_cy and s_ok -> every wave's decision and the finish pass
+            if (uni32<kScalar>(s_ok)) {
+                cy = s_cy;
+                uni_cycle<kScalar>(cy);
+                mcf_pivot_decide(v, mcf_view_paths(v), cy);
+            } else {
+                cx.status = MCF_INTERNAL_ERROR;
             }
         }
+        small_ctx_uniform<kScalar>(cx);
+        if (threadIdx.x == 0) small_desc_store(c, cx, adj2, adj3);
+        MCF_PSTAMP(16);
         STAMP(3);
-        __syncthreads();   // lane 0's decision (stage, pv_*, the apply descriptor) and the recorded paths -> the finish pass
+        // (no barrier: the finish pass reads the recorded paths, which the search barrier ordered, and the descriptor in registers)
         mcf_pivot_finish(v, mcf_view_paths(v), threadIdx.x, THREADS);
         __syncthreads();   // the finish pass's segment table and node records -> the apply pass
         STAMP(4);
-        // ---- apply: block permutation of the preorder array + potential shift
-        if (c->apply) {
-            // the descriptor's fields once per lane into registers: every element used to read them from LDS again, since its
-            // own stores may alias them (a private copy spilled under the 1 024-lane register cap; it does not any more)
-            McfCtx d;
-            d.cur = c->cur; d.lo = c->lo; d.hi = c->hi; d.t2_new = c->t2_new; d.t2_size = c->t2_size; d.t2_old = c->t2_old;
-            d.nseg = c->nseg; d.pv_dd0 = c->pv_dd0; d.sigma = c->sigma;
-            const int32_t lo = d.lo, hi = d.hi, plo = c->prev_lo, phi = c->prev_hi;
-            for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one(v, d, j);
+        // ---- apply: block permutation of the preorder array + potential shift, the descriptor straight from registers
+        if (cx.apply) {
+            const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
+            for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one(v, cx, j);
             for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
-                if (j < lo || j >= hi) mcf_apply_one(v, d, j);
+                if (j < lo || j >= hi) mcf_apply_one(v, cx, j);
         }
-        __syncthreads();   // every lane's read of c->apply and the apply pass's order / position / potential / depth stores
-                           // -> lane 0's store below and the next iteration's reads
-        if (threadIdx.x == 0) c->apply = 0;
-        __syncthreads();   // apply = 0 -> the next iteration's reads and the copy-out (mcf_pivot_begin would clear it too, but
-                           // leaving it to that was tried and bought nothing)
+        __syncthreads();   // the apply pass's order / position / potential / depth stores and the finish pass's flows and states
+                           // -> the next iteration's sweep, begin and search
+        cx.apply = 0;
         STAMP(5);
     }
+    // the control state goes back into the LDS image, once
+    if (threadIdx.x == 0) small_ctx_store(c, cx);
+    v.ctx = c;
+    __syncthreads();   // the LDS control block -> the budget check and the copy-out
 
     // at the budget: is any arc still eligible?  (simplex.py:1678-1699; saves the host a pricing pass + three syncs)
     if (c->status == MCF_PIVOT_LIMIT && !c->limit_checked) {
@@ -2666,7 +2808,10 @@ bool small_plan(int64_t m_pad, size_t arcw_count, int32_t n_nodes, bool devex, S
     L.order0 = take(Nn * 4); L.order1 = take(Nn * 4); L.pos0 = take(Nn * 4); L.pos1 = take(Nn * 4);
     L.path1 = take(Nn * 4); L.path2 = take(Nn * 4); L.ppos1 = take(Nn * 4); L.ppos2 = take(Nn * 4);
     L.rec1 = take(Nn * 16); L.rec2 = take(Nn * 16);
-    L.seg = take((2 * Nn + 2) * sizeof(McfSeg)); L.ctx = take(sizeof(McfCtx));
+    L.seg = take((2 * Nn + 2) * sizeof(McfSeg));
+    // scratch of the node-parallel cycle search (two residuals and one by-depth entry per tree node); a larger tree is climbed
+    L.scratch = take(n_nodes <= kSmallCycleMaxNodes ? Nn * 20 : 0);
+    L.ctx = take(sizeof(McfCtx));
     L.total = off;
     if (L.total > kSmallMaxLds) return false;
     *out = L;
@@ -2675,8 +2820,9 @@ bool small_plan(int64_t m_pad, size_t arcw_count, int32_t n_nodes, bool devex, S
 
 // Width of the fused loop's workgroup, from the measured table in DESIGN.md (k_solve_small).  One wave per SIMD (256 lanes)
 // reduces over 4 waves instead of 16 and meets 4 arrivals at each barrier; four waves per SIMD (1 024 lanes) hide the LDS round
-// trips of a sweep that reads its arcs from LDS (Devex) and of the passes over a larger tree.  256 lanes won at 65 and 257 tree
-// nodes under Dantzig and the candidate list and at 65 under Devex; 1 024 won at 514 nodes, and under Devex at 257.
+// trips of a sweep that reads its arcs from LDS (Devex) and of the passes over a larger tree -- but since every wave takes the
+// scalar decisions of a pivot itself, sixteen waves repeat them on four SIMDs and keep the control block in scalar registers
+// that spill (SmallScalarControl): 256 lanes won at 65, 257 and 514 tree nodes under every rule, by 0.5 to 1.8 us per pivot.
 // MCF_SMALL_THREADS = 256 / 1024 forces a width, for mcf_solve (read at mcf_create) and for mcf_solve_batch (read at the call).
 int small_threads_forced() {   // 0: no valid MCF_SMALL_THREADS
     if (const char* st = std::getenv("MCF_SMALL_THREADS")) {
@@ -2687,7 +2833,8 @@ int small_threads_forced() {   // 0: no valid MCF_SMALL_THREADS
 }
 int small_threads_for(int32_t n_nodes, int32_t rule) {
     if (const int w = small_threads_forced()) return w;
-    return n_nodes <= (rule == MCF_RULE_DEVEX_BLOCK ? 128 : 384) ? 256 : 1024;
+    (void)n_nodes; (void)rule;   // (no measured size or rule at which 1 024 lanes win any more)
+    return 256;
 }
 
 // The dynamic-LDS limit of the fused kernels covers `total` bytes on this device.  (The limit is a property of the kernel,
@@ -3319,13 +3466,13 @@ int mcf_solve_batch(mcf_handle* const* handles, int32_t count, const int64_t* ma
     hipEvent_t* ev = pool.ev;
     if ((e = hipEventRecord(ev[0], s)) != hipSuccess) return bail("hipEventRecord", e);
     if (!small_jobs.empty()) {
-        // Any handle runs at either width: the width belongs to the launch.  A batch keeps 1 024 lanes -- with every CU busy the
-        // narrow workgroup's single wave per SIMD has nothing to hide its LDS latency behind (scripts/batch_small.py per width:
-        // DESIGN.md) -- unless MCF_SMALL_THREADS forces 256.
-        if (small_threads_forced() == 256)
-            hipLaunchKernelGGL(k_solve_small_batch<256>, dim3((unsigned)small_jobs.size()), dim3(256), lds, s, (const SmallJob*)d_small);
-        else
+        // Any handle runs at either width: the width belongs to the launch.  A batch runs at 256 lanes like a single solve
+        // (scripts/batch_small.py per width, DESIGN.md: 43.7 M pivots/s over 1 024 instances against 33.1 M at 1 024 lanes)
+        // unless MCF_SMALL_THREADS forces 1 024.
+        if (small_threads_forced() == 1024)
             hipLaunchKernelGGL(k_solve_small_batch<1024>, dim3((unsigned)small_jobs.size()), dim3(1024), lds, s, (const SmallJob*)d_small);
+        else
+            hipLaunchKernelGGL(k_solve_small_batch<256>, dim3((unsigned)small_jobs.size()), dim3(256), lds, s, (const SmallJob*)d_small);
     }
     {
         // Two narrow workgroups per CU pay when there are more instances than CUs and the per-pivot passes are short

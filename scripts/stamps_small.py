@@ -2,12 +2,12 @@
 import ctypes, os, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
-os.environ["MCF_HIP_LIB"] = str(ROOT / "scripts" / "libmcf_stamps.so")
+os.environ.setdefault("MCF_HIP_LIB", str(ROOT / "scripts" / "libmcf_stamps.so"))   # (a -DMCF_STAMPS build; preset it for A/B builds)
 sys.path.insert(0, str(ROOT))
 import numpy as np
 from network_flow_solver_amd import engine, generators
 inst = generators.named_instance("netgen_8_08a")
-for rule in (0, 1):
+for rule in (0, 1, 2):
     eng = engine.McfEngine(inst.n, inst.tail, inst.head, inst.cost, inst.cap, inst.supply, rule=rule)
     eng.solve()
     st = eng.stats()
