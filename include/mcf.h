@@ -239,7 +239,17 @@ typedef struct mcf_stats {
     int64_t rc_dropped_at;    /* pivot count at which the handle gave up its resident reduced costs (mcf_options.rc_drop), 0 = it has not */
     int64_t run_pairs;        /* (k_pivot_run, k_update_bpl) pairs per list period right now (mcf_options.pivot_run), 0 = one k_pivot per slot */
     int64_t run_left_at;      /* pivot count at which the handle went back to one k_pivot per slot, 0 = it has not */
+    int64_t small_narrow;     /* fused LDS loop (pricing_mode 2): 1 = the handle's last launch was told that every reduced cost of the
+                                 instance fits 32 bits (mcf_small_narrow_ok with the big-M of that moment; its Dantzig / candidate-list
+                                 sweep then prices with 32-bit keys), 0 = 64-bit keys (the range does not fit, or MCF_SMALL_NARROW=0),
+                                 or no launch of that loop yet.  Same pivots either way. */
 } mcf_stats;
+
+/* The range test behind mcf_stats.small_narrow, a pure function of the instance: with big-M = big_m and max|cost| =
+ * max_abs_cost (big_m >= (max_abs_cost + 1) * (n + 2), as mcf_create forms it), every reduced cost, violation and potential
+ * shift of a solve stays within *bound (may be NULL) = 4 * big_m - 5 * max_abs_cost - 1 in magnitude (derivation:
+ * csrc/mcf_host.h); returns 1 when that fits int32, else 0.  Needs no device. */
+int mcf_small_narrow_ok(int64_t big_m, int64_t max_abs_cost, int64_t* bound);
 
 /* Called from mcf_solve every cb_interval pivots (simplex.py:1143-1154).
  * Return non-zero to stop the solve (status becomes MCF_ST_ITERATION_LIMIT). */

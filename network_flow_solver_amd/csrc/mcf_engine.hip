@@ -6,7 +6,9 @@
 //                   MCF_SMALL_THREADS asks (small_threads_for) -- prices (Dantzig / candidate list: the arcs' invariant
 //                   data in registers, 10 or 3 arcs per lane by width; Devex: from LDS), pivots (the lanes stride over the
 //                   tree nodes in the cycle search; every wave runs the ratio tests and takes the pivot's scalar decisions
-//                   itself, the control block in its registers) and updates until the solve ends.
+//                   itself, the control block in its registers) and updates until the solve ends.  Dantzig with the plain key
+//                   on an instance whose reduced costs fit 32 bits (mcf_small_narrow_fits) runs the front kernel,
+//                   k_solve_small<.., true>: 32-bit keys, and the arg-max hands the winner's record to the pivot's begin.
 //   k_solve_mid     <= 1 536 nodes: one persistent workgroup over global (L2-resident) state -- prices a Devex
 //                   block / re-prices the candidate list / sweeps a small arc list, pivots, permutes, patches.
 //                   (both also as k_solve_small_batch / k_solve_mid_batch: MANY independent instances in one launch, one
@@ -1786,6 +1788,57 @@ __device__ __forceinline__ void half_wave_argmax(int64_t& key, int64_t& arc) {
     arc = b;
 }
 
+// ---- the front of a pivot on the plain register sweep: 32-bit keys, and an arg-max that hands the candidate over.
+// A/B builds (scripts/stamps_small.py): -DMCF_SMALL_NO_NARROW never takes the 32-bit sweep, -DMCF_SMALL_NO_HANDOVER keeps
+// block_argmax_all and begin's look-ups, -DMCF_SMALL_NO_WX hands the record over but lets begin look the arc up all the same.
+#if defined(MCF_SMALL_NO_NARROW)
+constexpr bool kNarrowSweep = false;
+#else
+constexpr bool kNarrowSweep = true;
+#endif
+#if defined(MCF_SMALL_NO_HANDOVER)
+constexpr bool kHandover = false;
+#else
+constexpr bool kHandover = true;
+#endif
+#if defined(MCF_SMALL_NO_WX)
+constexpr bool kBeginWx = false;
+#else
+constexpr bool kBeginWx = true;
+#endif
+// What a lane remembers of its best arc besides the key: end points and slot in one word -- tail | head << 11 | slot << 22,
+// slot q = the lane's q-th arc, engine index r_lo + q * kPer -- the invariant part precomputed per register arc; bit 31 is
+// the state's sign (set: -1, the arc sits at capacity).  11 bits per node and 9 per slot cover every instance of the LDS plan
+// (small_plan: fewer than 1 371 tree nodes and 7 314 padded arcs, so at most 229 arcs per lane); small_info_fits is the
+// host's check of exactly that.
+__device__ __forceinline__ uint32_t small_info(int32_t tail, int32_t head, int32_t q) { return (uint32_t)tail | ((uint32_t)head << 11) | ((uint32_t)q << 22); }
+// the candidate record of the winner: its key is the violation (plain sweep), so rc = -state * violation, exactly
+__device__ __forceinline__ McfCandX small_record(uint32_t info, int64_t viol, int32_t orig, int32_t e) {
+    McfCandX x;
+    x.state = (info >> 31) ? -1 : 1;
+    x.rc = x.state > 0 ? -viol : viol;
+    x.arc = mcf_pack_arc(orig, e);
+    x.tail = (int32_t)(info & 0x7ff); x.head = (int32_t)((info >> 11) & 0x7ff); x.pad = 0;
+    return x;
+}
+// One arc beyond the register slots priced from LDS with the packed 32-bit key; q as in small_info
+__device__ __forceinline__ void small_price_lds_narrow(const McfView& v, int32_t i, int32_t q, uint64_t& best, uint32_t& info) {
+    const int32_t st = v.state[i];
+    const int32_t t = v.tail[i], h = v.head[i], o = v.orig[i];
+    const int32_t* pi32 = reinterpret_cast<const int32_t*>(v.pi);   // low words: exact in 32 bits under mcf_small_narrow_fits
+    const int32_t rc = (int32_t)((uint32_t)v.cost[i] + (uint32_t)pi32[2 * t] - (uint32_t)pi32[2 * h]);
+    const int32_t viol = st > 0 ? -rc : rc;
+    const uint64_t p = ((uint64_t)(uint32_t)((st != 0 && viol > 0) ? viol : 0) << 32) | (uint32_t)~o;
+    if (p > best) { best = p; info = small_info(t, h, q) | ((uint32_t)st & 0x80000000u); }
+}
+// Per-wave slot of the handing-over arg-max, one 16-byte read: the wave's best packed key (high word 0: none), the winner's
+// engine index and its info word.  Violation, id, end points, state and the exact reduced cost all unpack from these.
+struct alignas(16) SmallWaveSlot {
+    uint64_t key;
+    int32_t e;
+    uint32_t info;
+};
+
 // ---- the control block in registers (LDS loop), on a dense view without resident reduced costs.
 // Control state: every McfCtx field that mcf_pivot_begin_t, mcf_pivot_decide or the loop itself changes AND a later pivot
 // reads -- carried in scalar registers across the loop, written back once after it (small_ctx_store).
@@ -1846,9 +1899,15 @@ template <bool SCALAR> __device__ __forceinline__ void uni_cycle(McfCycle& y) {
 
 // The whole solve of one LDS-resident instance by one workgroup of THREADS lanes (k_solve_small: one instance per launch;
 // k_solve_small_batch: one instance per workgroup of the launch)
-template <int THREADS>
-__device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLayout& L, int32_t rule,
+// FRONT: the kernel of a Dantzig solve with the plain key whose reduced costs fit 32 bits (small_front_for on the host) -- the
+// narrow register sweep, the arg-max that hands the winner over, begin in one round trip; rule, sweep and key width are
+// compile-time constants there.  !FRONT: every other rule, key mode and range, with 64-bit keys.  Two kernels, not one kernel
+// with a per-launch switch: with both fronts in one loop the 64-bit path, Devex and the candidate list all lost 2 - 5 %
+// (profiles/small_loop_front_stamps.txt).
+template <int THREADS, bool FRONT>
+__device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLayout& L, int32_t rule_in,
                                                  McfCand* __restrict__ list, int64_t cap, char* smem, McfCtx* host_ctx) {
+    const int32_t rule = FRONT ? (int32_t)MCF_RULE_DANTZIG : rule_in;
 #ifdef MCF_STAMPS
     unsigned long long stamps_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long last_ = __builtin_amdgcn_s_memtime();
@@ -1909,7 +1968,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     if (threadIdx.x == 0) arm_ctx(c, cap);  // (what k_ctl does for the other paths; visible after the barrier below)
     // Devex: the host-made granule table in LDS (blocks move and resize under the tuner); other rules: whole buckets
     __shared__ int32_t s_gran[MCF_NUM_BUCKETS][MCF_GRANULES + 1];
-    const bool devex = rule == MCF_RULE_DEVEX_BLOCK && g.dx;
+    const bool devex = !FRONT && rule == MCF_RULE_DEVEX_BLOCK && g.dx;
     if (devex) {
         for (int q = threadIdx.x; q < MCF_NUM_BUCKETS * (MCF_GRANULES + 1); q += THREADS)
             (&s_gran[0][0])[q] = (&g.dx->gran[0][0])[q];
@@ -1920,7 +1979,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     // candidate-list rule: the list is the best arc of each head bucket (= of each of the 8 pricing
     // workgroups the three-kernel path would use at this size); minor iterations re-price just
     // those 8 arcs.  The list survives between launches in `list` (global).
-    const bool listing = rule == MCF_RULE_CANDIDATE_LIST;
+    const bool listing = !FRONT && rule == MCF_RULE_CANDIDATE_LIST;
     __shared__ int64_t s_lk[MCF_NUM_BUCKETS], s_la[MCF_NUM_BUCKETS];
     if (listing && threadIdx.x < MCF_NUM_BUCKETS) { s_lk[threadIdx.x] = list[threadIdx.x].key; s_la[threadIdx.x] = list[threadIdx.x].arc; }
     __syncthreads();   // arm_ctx, the granule table and the list -> every lane's reads below and in the loop
@@ -1941,11 +2000,13 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     constexpr int kReg = SmallRegArcs<THREADS>::value;
     static_assert(kPer == 32 || kPer % 64 == 0, "a head bucket's lanes are half a wave or whole waves");
     const int px = threadIdx.x / kPer, pl = threadIdx.x % kPer;
-    const int sweep = devex ? kSweepDevex : (rule != MCF_RULE_DEVEX_BLOCK && v.key_mode == MCF_KEY_PLAIN ? kSweepPlain : kSweepGeneric);
+    const int sweep = FRONT ? (int)kSweepPlain
+                            : (devex ? kSweepDevex : (rule != MCF_RULE_DEVEX_BLOCK && v.key_mode == MCF_KEY_PLAIN ? kSweepPlain : kSweepGeneric));
     // Plain sweep: the arcs a lane prices are the same at every pivot (whole buckets), and tail / head / cost / orig never
     // change during a launch: the first kReg of them live in registers from here on.  (Slots past the bucket's end price
     // arc 0 with its state masked to 0.)
     int32_t r_tail[kReg], r_head[kReg], r_cost[kReg], r_orig[kReg];
+    uint32_t r_info[kReg];   // (small_info: what the arg-max hands over to begin)
     int32_t r_n = 0;   // slots in use
     const int32_t r_lo = s_gran[px][0] + pl, r_hi = s_gran[px][MCF_GRANULES];
 #pragma unroll
@@ -1953,8 +2014,15 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         const int32_t i = r_lo + k * kPer;
         const bool on = kRegSweep && sweep == kSweepPlain && i < r_hi;
         r_tail[k] = on ? v.tail[i] : 0; r_head[k] = on ? v.head[i] : 0; r_cost[k] = on ? v.cost[i] : 0; r_orig[k] = on ? v.orig[i] : 0;
+        r_info[k] = small_info(r_tail[k], r_head[k], k);
         r_n += on ? 1 : 0;
     }
+    // The front (compile-time): 32-bit keys on the plain register sweep, and with them the arg-max that hands the winner's
+    // record to begin.  64-bit keys price, reduce and begin as before.
+    const bool reg_plain = kRegSweep && sweep == kSweepPlain;
+    constexpr bool nar = FRONT;
+    constexpr bool hand = FRONT && kHandover;
+    const int32_t* const pi32 = reinterpret_cast<const int32_t*>(v.pi);   // low words of the potentials
     // ---- control in registers.  Every wave carries the control block itself -- a private McfCtx whose fields live in scalar
     // registers -- and takes every scalar decision of a pivot itself, from broadcast LDS reads: mcf_pivot_begin_t,
     // mcf_pivot_decide, mcf_pivot_finish and mcf_apply_one run on that private copy (v.ctx points to it), the very functions
@@ -1968,7 +2036,10 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     //     the finish pass rewrites node[u_in];
     //   * begin reads arcw[e].flow and state[e], finish writes them: all of begin's reads precede the search barrier;
     //   * an iteration that pivots on nothing (empty Devex block, exhausted list, budget, optimal) takes one barrier before
-    //     it continues: the next iteration rewrites the per-wave arg-max slots and the candidate list.
+    //     it continues: the next iteration rewrites the per-wave arg-max slots and the candidate list;
+    //   * the front kernel's per-wave slots (key + the winner's record) are written before the arg-max barrier, read right
+    //     behind it by every wave, and rewritten only by the next iteration's arg-max: the apply barrier, or the barrier of an
+    //     iteration that pivots on nothing, lies between.
     // Rule-specific bookkeeping in memory -- the entering arc's Devex weight and the list of touched weights -- is stored by
     // mcf_pivot_decide with the same value from every lane; nothing reads it before the next barrier.  A tuner step
     // (block_granules / num_blocks) is computed in every wave alike.
@@ -1994,8 +2065,34 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         }
         // ---- price: the arc set of k_price for shard 0 of 1
         int64_t key = 0, arc = -1;
+        McfCandX wx;   // the winner's record (hand)
+        wx.rc = 0; wx.arc = -1; wx.tail = 0; wx.head = 0; wx.state = 0; wx.pad = 0;
+        uint64_t nbest = 0xffffffffull;   // narrow: (violation << 32) | ~orig of the lane's best; high word 0: nothing eligible
+        uint32_t info = 0;                // ... and its end points, slot and state (small_info)
         if (!minor) {
-            if (sweep == kSweepPlain && kRegSweep) {
+            if (nar) {
+                // 32-bit keys: the low words of the potentials, one compare and two selects per arc.  The plain maximum of
+                // (violation << 32) | ~orig is mcf_cand_better's winner -- larger violation, then lower id -- and never ties.
+                int32_t st[kReg], pt[kReg], ph[kReg];
+#pragma unroll
+                for (int k = 0; k < kReg; ++k) {
+                    st[k] = v.state[k < r_n ? r_lo + k * kPer : 0];
+                    pt[k] = pi32[2 * r_tail[k]];
+                    ph[k] = pi32[2 * r_head[k]];
+                }
+#pragma unroll
+                for (int k = 0; k < kReg; ++k) {
+                    const int32_t rc = (int32_t)((uint32_t)r_cost[k] + (uint32_t)pt[k] - (uint32_t)ph[k]);
+                    const int32_t s = k < r_n ? st[k] : 0;
+                    const int32_t viol = s > 0 ? -rc : rc;
+                    const uint64_t p = ((uint64_t)(uint32_t)((s != 0 && viol > 0) ? viol : 0) << 32) | (uint32_t)~r_orig[k];
+                    if (p > nbest) { nbest = p; info = r_info[k] | ((uint32_t)s & 0x80000000u); }
+                }
+                int32_t q = kReg;
+                for (int32_t i = r_lo + kReg * kPer; i < r_hi; i += kPer, ++q) small_price_lds_narrow(v, i, q, nbest, info);
+                // the present form, for the candidate list's entries and for the record
+                if (nbest >> 32) { key = (int64_t)(nbest >> 32); arc = mcf_pack_arc((int32_t)~(uint32_t)nbest, r_lo + (int32_t)((info >> 22) & 0x1ff) * kPer); }
+            } else if (reg_plain) {
                 // one LDS round trip for the whole lane: states and potentials of all its register arcs, then selects
                 int32_t st[kReg];
                 int64_t pt[kReg], ph[kReg];
@@ -2054,6 +2151,42 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
                 if (key <= 0) { key = 0; arc = -1; }
             }
             wave_argmax(key, arc);
+        } else if (hand) {
+            // 32-bit keys: one 64-bit max per wave, no tie loop; the winning lane writes the wave's slot -- packed key, engine
+            // index, info word: 16 bytes.  After the one barrier every wave reads the slots by broadcast and picks the winner
+            // itself with plain compares -- no second reduction -- and unpacks the candidate record (wx) begin would otherwise
+            // look up.  The slots are rewritten by the next iteration's arg-max, which the apply barrier (or the barrier of an
+            // iteration that pivots on nothing) orders behind these reads.
+            constexpr int kWaves = THREADS / 64;
+            __shared__ SmallWaveSlot s_slot[kWaves];
+            const int32_t lane = (int32_t)(threadIdx.x & 63), wave = (int32_t)(threadIdx.x >> 6);
+            const uint64_t mx = (uint64_t)mcf_wave_max64((int64_t)nbest);
+            const bool any = (mx >> 32) != 0;
+            if (any ? nbest == mx : lane == 0) s_slot[wave] = SmallWaveSlot{any ? mx : 0, (int32_t)(arc & 0xffffffff), info};
+            __syncthreads();   // per-wave slots -> every wave's pick
+            SmallWaveSlot b;
+            if constexpr (kWaves <= 4) {   // one round trip, kWaves reads
+                SmallWaveSlot sl[kWaves];
+#pragma unroll
+                for (int q = 0; q < kWaves; ++q) sl[q] = s_slot[q];
+                b = sl[0];
+#pragma unroll
+                for (int q = 1; q < kWaves; ++q) if (sl[q].key > b.key) b = sl[q];
+            } else {   // sixteen waves: lane q takes slot q, one more max names the winning lane, scalar lane reads fetch the rest
+                const SmallWaveSlot mine = s_slot[lane < kWaves ? lane : 0];
+                const uint64_t k = lane < kWaves ? mine.key : 0;
+                b.key = (uint64_t)mcf_wave_max64((int64_t)k);
+                const int32_t w = (int32_t)__builtin_ctzll((unsigned long long)__ballot(k == b.key));
+                b.e = __builtin_amdgcn_readlane(mine.e, w);
+                b.info = (uint32_t)__builtin_amdgcn_readlane((int32_t)mine.info, w);
+            }
+            key = (int64_t)(b.key >> 32);
+            if (key > 0) {
+                wx = small_record(b.info, key, (int32_t)~(uint32_t)b.key, b.e);
+                arc = wx.arc;
+            } else { key = 0; arc = -1; }
+            key = uni64<kScalar>(key); arc = uni64<kScalar>(arc);
+            wx.rc = uni64<kScalar>(wx.rc); wx.tail = uni32<kScalar>(wx.tail); wx.head = uni32<kScalar>(wx.head); wx.state = uni32<kScalar>(wx.state);
         } else {
             block_argmax_all<THREADS>(key, arc);
         }
@@ -2062,10 +2195,13 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         if (cx.pivots < cx.max_pivots)
             cx.arcs_priced += minor ? (int64_t)MCF_NUM_BUCKETS : (devex ? (int64_t)uni32<kScalar>(s_gsum[bg1] - s_gsum[bg0]) : priced_all);
         MCF_PSTAMP(12);
-        // begin: the arc's record, then its end points' records, positions and potentials -- two broadcast round trips; the
-        // records the decision will need are fetched here (WITH_CY)
+        // begin: with the winner's record in registers (wx), the arc's capacity and flow and its end points' records and
+        // positions all hang on values known here -- one broadcast round trip; without it the arc's record first, then its end
+        // points' records, positions and potentials -- two.  The records the decision will need are fetched here (WITH_CY).
         McfCycle cy;
-        const bool go = mcf_pivot_begin_t<true>(v, key, arc, rule, nullptr, &cy);
+        bool go;
+        if constexpr (hand && kBeginWx) go = mcf_pivot_begin_t<true>(v, key, arc, rule, &wx, &cy);
+        else go = mcf_pivot_begin_t<true>(v, key, arc, rule, nullptr, &cy);
         small_ctx_uniform<kScalar>(cx);
         MCF_PSTAMP(13);
         if (!go) {   // nothing to pivot on: uniform, every wave takes this way
@@ -2168,11 +2304,11 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
 
 // (waves per SIMD stated: one workgroup per CU -- the LDS image allows no second -- so 256 lanes are ONE wave per SIMD and may
 //  use its whole register file; left to guess, the compiler kept room for two and put 20 B per lane into scratch)
-template <int THREADS>
+template <int THREADS, bool FRONT>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS / 256, THREADS / 256))) void k_solve_small(McfView g, SmallLayout L, int32_t rule,
                                                           McfCand* __restrict__ list, int64_t cap, McfCtx* host_ctx) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    solve_small_body<THREADS>(g, L, rule, list, cap, smem, host_ctx);
+    solve_small_body<THREADS, FRONT>(g, L, rule, list, cap, smem, host_ctx);
 }
 
 // Many independent small instances side by side: workgroup b solves jobs[b] from start to finish in its own CU's LDS.
@@ -2182,17 +2318,17 @@ struct SmallJob {
     McfView g;
     SmallLayout L;
     int32_t rule;
-    int32_t pad;
+    int32_t narrow;     // the job's reduced costs fit 32 bits (small_narrow_for); the host sorts the jobs by front (small_front_for)
     McfCand* list;
     int64_t cap;
     McfCtx* host_ctx;   // pinned: the final control block goes straight to the host
 };
 
-template <int THREADS>
+template <int THREADS, bool FRONT>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS / 256, THREADS / 256))) void k_solve_small_batch(const SmallJob* __restrict__ jobs) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const SmallJob& J = jobs[blockIdx.x];   // uniform per workgroup: scalar loads
-    solve_small_body<THREADS>(J.g, J.L, J.rule, J.list, J.cap, smem, J.host_ctx);
+    solve_small_body<THREADS, FRONT>(J.g, J.L, J.rule, J.list, J.cap, smem, J.host_ctx);
 }
 
 // ------------------------------------------------------------------ k_ctl: (re)arm the control block
@@ -2258,6 +2394,7 @@ struct mcf_handle {
     int32_t climb_budget = INT32_MAX;  // round trips the cycle climb may take before the scan takes over
     bool small = false;       // whole instance fits in LDS: fused single-workgroup pivot loop
     int small_threads = 0;    // ... and the width of that workgroup (small_threads_for at mcf_create)
+    bool small_narrow_ok = true;   // MCF_SMALL_NARROW as read at mcf_create (small_narrow_allowed)
     bool mid = false;         // mid-size instance: persistent single-workgroup pivot loop over global memory (k_solve_mid)
     SmallLayout small_layout{};
     int64_t shard = 0, shards = 1;
@@ -2837,6 +2974,26 @@ int small_threads_for(int32_t n_nodes, int32_t rule) {
     return 256;
 }
 
+// 32-bit pricing keys in the fused loop (the narrow sweep of solve_small_body): MCF_SMALL_NARROW=0 forces the 64-bit path -- read
+// where MCF_SMALL_THREADS is read, at mcf_create for mcf_solve and at the call for mcf_solve_batch -- otherwise the instance
+// decides, at every launch: big-M grows on a resident handle (mcf_update_costs, mcf_add_arcs).  max|cost| is taken from the
+// invariant big-M >= (max|cost| + 1)(n + 2), which is exact on a fresh handle and an upper bound after costs came down.
+bool small_narrow_allowed() {
+    const char* sn = std::getenv("MCF_SMALL_NARROW");
+    return !(sn && sn[0] == '0' && sn[1] == '\0');
+}
+// the bit fields of small_info (device): 11 bits per node, 9 per slot of a lane at the narrowest bucket share (32 lanes)
+bool small_info_fits(int32_t n_nodes, int64_t m_pad) { return n_nodes <= 2048 && m_pad / 32 < 512; }
+int32_t small_narrow_for(const McfHostImage& im, bool allowed) {
+    const int64_t max_abs = im.big_m / ((int64_t)im.n + 2) - 1;
+    return allowed && small_info_fits(im.n_nodes, im.m_pad) && mcf_small_narrow_fits(im.big_m, max_abs) ? 1 : 0;
+}
+
+// Which kernel: the front kernel (k_solve_small<.., true>) for Dantzig with the plain key on a range that fits
+bool small_front_for(int32_t narrow, int32_t rule, int32_t key_mode) {
+    return kNarrowSweep && kRegSweep && narrow != 0 && rule == MCF_RULE_DANTZIG && key_mode == MCF_KEY_PLAIN;
+}
+
 // The dynamic-LDS limit of the fused kernels covers `total` bytes on this device.  (The limit is a property of the kernel,
 // not of the handle: it only ever grows, so that handles of different sizes can be alive together -- and share one batched launch.)
 bool small_reserve(int device, uint32_t total) {
@@ -2845,8 +3002,10 @@ bool small_reserve(int device, uint32_t total) {
     int& lds_limit = lds_limits[device & 63];
     std::lock_guard<std::mutex> lock(lds_mu);
     if ((int)total <= lds_limit) return true;
-    const void* const fns[] = {reinterpret_cast<const void*>(k_solve_small<256>), reinterpret_cast<const void*>(k_solve_small<1024>),
-                               reinterpret_cast<const void*>(k_solve_small_batch<256>), reinterpret_cast<const void*>(k_solve_small_batch<1024>)};
+    const void* const fns[] = {reinterpret_cast<const void*>(k_solve_small<256, false>), reinterpret_cast<const void*>(k_solve_small<1024, false>),
+                               reinterpret_cast<const void*>(k_solve_small<256, true>), reinterpret_cast<const void*>(k_solve_small<1024, true>),
+                               reinterpret_cast<const void*>(k_solve_small_batch<256, false>), reinterpret_cast<const void*>(k_solve_small_batch<1024, false>),
+                               reinterpret_cast<const void*>(k_solve_small_batch<256, true>), reinterpret_cast<const void*>(k_solve_small_batch<1024, true>)};
     hipError_t fe = hipSuccess;
     for (const void* fn : fns)
         if (fe == hipSuccess) fe = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
@@ -2863,6 +3022,11 @@ bool small_reserve(int device, uint32_t total) {
 extern "C" {
 
 int mcf_abi_version(void) { return MCF_ABI_VERSION; }
+
+int mcf_small_narrow_ok(int64_t big_m, int64_t max_abs_cost, int64_t* bound) {
+    if (bound) *bound = mcf_small_rc_bound(big_m, max_abs_cost);
+    return mcf_small_narrow_fits(big_m, max_abs_cost) ? 1 : 0;
+}
 
 int mcf_device_count(void) { return usable_devices(); }
 
@@ -3018,7 +3182,7 @@ int mcf_create(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, c
     h->small = !h->bpl && !opt.no_fused && !opt.profile && h->shards == 1 &&
                small_plan(im.m_pad, im.arcw.size(), im.n_nodes, opt.rule == MCF_RULE_DEVEX_BLOCK, &h->small_layout) &&
                small_reserve(h->device, h->small_layout.total);
-    if (h->small) h->small_threads = small_threads_for(im.n_nodes, opt.rule);
+    if (h->small) { h->small_threads = small_threads_for(im.n_nodes, opt.rule); h->small_narrow_ok = small_narrow_allowed(); }
     // position-space subtree sizes for the cycle scan: every handle but the LDS-resident ones
     const bool scan_ok = opt.cycle_scan >= 0 && im.n_nodes <= kScanMaxNodes && !h->small;  // -1: never scan
     v.bmeta[0] = v.bmeta[1] = nullptr; v.bext[0] = v.bext[1] = nullptr; v.blk_shift = 0; v.blk_cap = 0; v.ncandx = 0; v.candx = nullptr;
@@ -3276,12 +3440,14 @@ int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user,
                 HIP_TRY(h, hipEventRecord(h->loop_ev[0], h->stream));
             }
             if (h->small) {
-                if (h->small_threads == 1024)
-                    hipLaunchKernelGGL(k_solve_small<1024>, dim3(1), dim3(1024), h->small_layout.total, h->stream, h->view,
-                                       h->small_layout, h->opt.rule, h->d_cand, cap, h->h_ctx);
-                else
-                    hipLaunchKernelGGL(k_solve_small<256>, dim3(1), dim3(256), h->small_layout.total, h->stream, h->view,
-                                       h->small_layout, h->opt.rule, h->d_cand, cap, h->h_ctx);
+                const int32_t narrow = small_narrow_for(h->im, h->small_narrow_ok);   // (per launch: big-M may have grown)
+                h->stats.small_narrow = narrow;
+                auto kernel = k_solve_small<256, false>;
+                const bool front = small_front_for(narrow, h->opt.rule, h->view.key_mode);
+                if (h->small_threads == 1024) kernel = front ? k_solve_small<1024, true> : k_solve_small<1024, false>;
+                else if (front) kernel = k_solve_small<256, true>;
+                hipLaunchKernelGGL(kernel, dim3(1), dim3(h->small_threads == 1024 ? 1024 : 256), h->small_layout.total, h->stream, h->view,
+                                   h->small_layout, h->opt.rule, h->d_cand, cap, h->h_ctx);
             }
             else {
                 // eager launches need not run past the cap (a replayed graph has a fixed length: its surplus slots early-exit)
@@ -3403,6 +3569,7 @@ int mcf_solve_batch(mcf_handle* const* handles, int32_t count, const int64_t* ma
     std::vector<SmallJob> small_jobs;
     std::vector<MidJob> mid_jobs;
     uint32_t lds = 0;
+    const bool batch_narrow_ok = small_narrow_allowed();
     for (int32_t i = 0; i < count; ++i) {
         mcf_handle* h = handles[i];
         int rc = sync_ctx(h, h->stream);   // (also drains whatever the handle's own stream still holds)
@@ -3414,7 +3581,9 @@ int mcf_solve_batch(mcf_handle* const* handles, int32_t count, const int64_t* ma
         const int64_t cap = h->h_ctx->pivots + mp;
         if (h->small) {
             SmallJob J;
-            J.g = h->view; J.L = h->small_layout; J.rule = h->opt.rule; J.pad = 0; J.list = h->d_cand; J.cap = cap; J.host_ctx = h->h_ctx;
+            J.g = h->view; J.L = h->small_layout; J.rule = h->opt.rule; J.narrow = small_narrow_for(h->im, batch_narrow_ok);
+            J.list = h->d_cand; J.cap = cap; J.host_ctx = h->h_ctx;
+            h->stats.small_narrow = J.narrow;
             small_jobs.push_back(J);
             if (h->small_layout.total > lds) lds = h->small_layout.total;
         } else {
@@ -3425,6 +3594,11 @@ int mcf_solve_batch(mcf_handle* const* handles, int32_t count, const int64_t* ma
     }
     // candidate-list jobs last (their own launch)
     std::stable_partition(mid_jobs.begin(), mid_jobs.end(), [](const MidJob& J) { return J.rule != MCF_RULE_CANDIDATE_LIST; });
+    // ... and the LDS jobs of the front kernel behind the others (small_front_for: a launch each)
+    auto job_front = [](const SmallJob& J) { return small_front_for(J.narrow, J.rule, J.g.key_mode); };
+    std::stable_partition(small_jobs.begin(), small_jobs.end(), [&](const SmallJob& J) { return !job_front(J); });
+    size_t n_front = 0;
+    for (const SmallJob& J : small_jobs) n_front += job_front(J) ? 1 : 0;
     size_t n_listing = 0;
     for (const MidJob& J : mid_jobs) n_listing += J.rule == MCF_RULE_CANDIDATE_LIST ? 1 : 0;
     // job arrays and the two timing events come from a per-device pool that only ever grows (a call used to pay two
@@ -3469,10 +3643,14 @@ int mcf_solve_batch(mcf_handle* const* handles, int32_t count, const int64_t* ma
         // Any handle runs at either width: the width belongs to the launch.  A batch runs at 256 lanes like a single solve
         // (scripts/batch_small.py per width, DESIGN.md: 43.7 M pivots/s over 1 024 instances against 33.1 M at 1 024 lanes)
         // unless MCF_SMALL_THREADS forces 1 024.
-        if (small_threads_forced() == 1024)
-            hipLaunchKernelGGL(k_solve_small_batch<1024>, dim3((unsigned)small_jobs.size()), dim3(1024), lds, s, (const SmallJob*)d_small);
-        else
-            hipLaunchKernelGGL(k_solve_small_batch<256>, dim3((unsigned)small_jobs.size()), dim3(256), lds, s, (const SmallJob*)d_small);
+        const bool w1024 = small_threads_forced() == 1024;
+        const unsigned n_rest = (unsigned)(small_jobs.size() - n_front);
+        const SmallJob* rest = d_small;
+        const SmallJob* fronts = d_small + n_rest;
+        auto k_rest = w1024 ? k_solve_small_batch<1024, false> : k_solve_small_batch<256, false>;
+        auto k_front = w1024 ? k_solve_small_batch<1024, true> : k_solve_small_batch<256, true>;
+        if (n_rest) hipLaunchKernelGGL(k_rest, dim3(n_rest), dim3(w1024 ? 1024 : 256), lds, s, rest);
+        if (n_front) hipLaunchKernelGGL(k_front, dim3((unsigned)n_front), dim3(w1024 ? 1024 : 256), lds, s, fronts);
     }
     {
         // Two narrow workgroups per CU pay when there are more instances than CUs and the per-pivot passes are short

@@ -41,6 +41,26 @@ struct McfHostImage {
     std::vector<int64_t> adj;               // [2m]
 };
 
+// ---- 32-bit pricing range of the fused LDS loop (k_solve_small's narrow sweep).
+// With B = big-M and C = max|cost| of the instance as it stands, a bound on every reduced cost, violation and potential
+// shift sigma that a solve can meet:
+//   * the root's potential is 0 and every potential is a tree potential: pi[child] - pi[parent] = +-cost(pred arc);
+//   * only artificial arcs touch the root, and a simple tree path from the root cannot come back to it: it holds exactly
+//     one artificial arc (cost B) and at most n - 1 real ones, so |pi[v]| <= B + (n - 1) C;
+//   * a real arc:        |cost + pi[t] - pi[h]| <= C + 2 (B + (n - 1) C) = 2 B + (2 n - 1) C =: R;
+//     an artificial arc: |B + pi[v] - 0|        <= 2 B + (n - 1) C <= R;
+//   * a violation is |rc| of an eligible arc and sigma is +-rc of the entering arc: both <= R.
+// big-M is kept >= (C + 1)(n + 2) by mcf_build_image, mcf_update_costs and mcf_add_arcs (it grows with the costs and never
+// shrinks), hence (n + 2) C <= B - (n + 2) and
+//   R = 2 B + 2 (n + 2) C - 5 C <= 4 B - 5 C - 2 (n + 2) < 4 B - 5 C.
+// (The 4 B + C of a first estimate holds too; it counts the tree path's real arcs as a second big-M per end point.)
+// mcf_small_rc_bound is that strict upper bound minus one, from B and C alone; the narrow sweep is exact in 32-bit
+// arithmetic -- low words of the potentials, wrap-around included -- whenever it fits int32.
+inline int64_t mcf_small_rc_bound(int64_t big_m, int64_t max_abs_cost) { return 4 * big_m - 5 * max_abs_cost - 1; }
+inline bool mcf_small_narrow_fits(int64_t big_m, int64_t max_abs_cost) {
+    return big_m > 0 && max_abs_cost >= 0 && big_m < ((int64_t)1 << 44) && mcf_small_rc_bound(big_m, max_abs_cost) <= (int64_t)INT32_MAX;
+}
+
 // The all-artificial start basis (_initialize_tree, simplex.py:619-730): every real arc non-basic at its
 // lower bound, one artificial arc per node, all of them basic, carrying the node's supply to / from the root.
 inline void mcf_init_cold_basis(McfHostImage& im) {

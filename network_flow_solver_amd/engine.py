@@ -33,7 +33,7 @@ ABI_SYMBOLS = (
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
     "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_add_arcs",
-    "mcf_cost_ranges",
+    "mcf_cost_ranges", "mcf_small_narrow_ok",
 )
 RANGE_INF = (1 << 63) - 1   # MCF_RANGE_INF: no arc limits this side of a cost range
 # mcf_certify: check groups and verdicts (include/mcf.h)
@@ -79,7 +79,7 @@ class McfStats(ctypes.Structure):
         ("cycle_scans", ctypes.c_int64), ("scan_rounds", ctypes.c_int64), ("arcs_swept", ctypes.c_int64),
         ("loop_ms", ctypes.c_double), ("loop_launches", ctypes.c_int64), ("sweep_variant", ctypes.c_int64),
         ("tree_blocks", ctypes.c_int64), ("tree_rebuilds", ctypes.c_int64), ("rc_dropped_at", ctypes.c_int64),
-        ("run_pairs", ctypes.c_int64), ("run_left_at", ctypes.c_int64),
+        ("run_pairs", ctypes.c_int64), ("run_left_at", ctypes.c_int64), ("small_narrow", ctypes.c_int64),
     ]
 
     def as_dict(self) -> dict:
@@ -212,6 +212,9 @@ def load_library():
     lib.mcf_certify_ray.argtypes = [vp, ctypes.c_int64, i64p, ctypes.c_int64, ctypes.POINTER(McfRay)]
     lib.mcf_certify_cut.argtypes = [vp, i8p, i8p, ctypes.POINTER(McfCut)]
     lib.mcf_cost_ranges.argtypes = [vp, ctypes.c_int64, i64p, i64p, i64p, ctypes.POINTER(McfRangesReport)]
+    if hasattr(lib, "mcf_small_narrow_ok"):   # (an A/B library built from an earlier commit lacks it: MCF_HIP_LIB)
+        lib.mcf_small_narrow_ok.argtypes = [ctypes.c_int64, ctypes.c_int64, i64p]
+        lib.mcf_small_narrow_ok.restype = ctypes.c_int
     lib.mcf_dimacs_scan.argtypes = [ctypes.c_char_p, i64p, i64p, ctypes.c_char_p, ctypes.c_int32]
     lib.mcf_dimacs_load.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, i32p, i32p, i64p, i64p, i64p, i64p,
                                     ctypes.c_char_p, ctypes.c_int32]
@@ -232,6 +235,13 @@ def load_library():
 
 def device_count() -> int:
     return int(load_library().mcf_device_count())
+
+
+def small_narrow_ok(big_m: int, max_abs_cost: int) -> tuple[bool, int]:
+    """mcf_small_narrow_ok: (every reduced cost of such an instance fits int32, the bound on their magnitude).  No device needed."""
+    bound = ctypes.c_int64()
+    ok = load_library().mcf_small_narrow_ok(int(big_m), int(max_abs_cost), ctypes.byref(bound))
+    return bool(ok), int(bound.value)
 
 
 def _p(a: np.ndarray, t):
