@@ -32,6 +32,9 @@
  *       arc, simplex.py:1600-1624 returns an empty flow): the ray and the cut that prove them ...  mcf_certify_ray / mcf_certify_cut
  *   "what if this cost changes": the reference answers by one re-solve per what-if (examples/sensitivity_analysis_example.py,
  *       examples/warm_start_example.py); the ranges inside which no re-solve pivots, for all arcs at once ...  mcf_cost_ranges
+ *   "what if this supply / capacity changes": the reference predicts the objective from the duals and re-solves to see whether
+ *       the prediction held (examples/sensitivity_analysis_example.py), and lists saturated arcs without a price or a range
+ *       (utils.py:250-312); how far the prediction holds, and its exact rate ...  mcf_supply_ranges / mcf_capacity_ranges
  *   AdaptiveTuner.adapt_block_size  simplex_adaptive.py:98-151 and the
  *       periodic Devex reset  simplex.py:1370-1400 ..........................  inside mcf_solve (MCF_RULE_DEVEX_BLOCK)
  *   specialised pivot strategies  specialized_pivots.py:69-424, 452-527 .....  mcf_options.key_mode (+ arc_priority): row scan,
@@ -374,6 +377,7 @@ int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int
  *                artificial tree arc whose flow changed sign turns round (art_flips); only then do potentials (below it, by
  *                -+2 big-M), reduced costs and key codes change, rebuilt as mcf_update_costs rebuilds them.  A handle that
  *                was optimal and takes path 0 without a flip is optimal again: the next mcf_solve makes 0 pivots.
+ *                mcf_supply_ranges / mcf_capacity_ranges say in advance which single edits take this path (their contract below).
  *   path 1       otherwise the states and the node records (not the flows) come down and the basis is repaired on the
  *                host at mcf_set_basis cost: every tree arc whose flow left its bounds becomes non-basic at the bound it
  *                violated, every wrong-way arc at the bound it sits on; each such subtree hangs on the root by its
@@ -690,6 +694,82 @@ typedef struct mcf_ranges_report {
 } mcf_ranges_report;
 int mcf_cost_ranges(mcf_handle* h, int64_t count, const int64_t* arc /* caller's indices; count < 0 and NULL = all m */,
                     int64_t* down, int64_t* up, mcf_ranges_report* out /* may be NULL */);
+
+/* ---- flow ranging on the resident basis: how far may ONE supply shift or ONE arc's capacity move before a tree flow leaves
+ * its bounds, and what does the objective do until then?  The question before a mcf_update_rhs: an edit inside the range takes
+ * path 0 -- the basis stays, nothing pivots -- and costs exactly rate * d.  The primal mirror image of mcf_cost_ranges, from
+ * the same resident arrays; nothing is tried and nothing is changed.
+ *
+ *   definition   exact signed integers, the state as mcf_certify reads it.  The tree arc of node v (pred >> 1; it points child
+ *                -> parent when pred & 1) has two residuals:
+ *                                   push along the arc                     push against it
+ *                  capped           cap - flow                             flow
+ *                  uncapacitated    MCF_RANGE_INF                          flow
+ *                  artificial       MCF_RANGE_INF (the push raises         flow (past it mcf_update_rhs turns the arc round and
+ *                                   artificial flow: see art_rising)       the potentials below it move by 2 big-M)
+ *                U[v] is the residual for a push child -> parent, D[v] for parent -> child.  push(x -> y) = the largest amount
+ *                the tree carries from x to y = min(U over the tree arcs from x up to the join, D over those from the join
+ *                down to y); MCF_RANGE_INF and no arc for x == y.  limit_arc is the FIRST arc in push order (x up to the join,
+ *                then the join down to y) that attains the limit, as a caller's index, m + v for the artificial arc of node v
+ *                as in mcf_get_tree, -1 when the limit is MCF_RANGE_INF.  No launch geometry enters that rule.  art_rising is
+ *                the number of artificial arcs on the path whose flow the push raises.  Residuals are not clamped: a state
+ *                that is out of bounds reports what is there (a negative limit: the range is already empty).
+ *   supply       pair i asks for the edit supply[from[i]] += d, supply[to[i]] -= d:  limit = push(from -> to),  rate =
+ *                pi[to] - pi[from] = the signed cost of the tree path, the exact change of the big-M objective per unit.
+ *   capacity     by how much may the capacity of one arc fall (down) or rise (up); rate = objective per unit of capacity ADDED
+ *                  uncapacitated                        down INF           up INF           rate 0    no arcs
+ *                  capped, non-basic at lower bound     down cap           up INF           rate 0    no arcs
+ *                  capped, basic                        down cap - flow    up INF           rate 0    down_arc = the arc itself
+ *                  non-basic at capacity, t -> hd       down min(push(t -> hd), cap)   up push(hd -> t)   rate rc = cost + pi[t] - pi[hd]
+ *                an arc at capacity carries its capacity: more of it sends more t -> hd, which the tree returns hd -> t; less
+ *                of it the other way round.  down_arc / up_arc come from the push; down_arc is the arc itself when cap is
+ *                strictly the smaller of the two.
+ *   contract     the handle holds a basis with wrong_way == 0 (an optimal one does), the edit is one supply shift or one
+ *                capacity change of size d through mcf_update_rhs (in rate * d a capacity that FALLS by d counts as -d):
+ *                  0 < d < limit    path 0 with tree_violations == 0 and art_flips == 0; on an optimal handle the next
+ *                                   mcf_solve makes 0 pivots and mcf_certify gives primal + bigm_term = the old value + rate * d;
+ *                  d == limit       tree_violations == 0; the path may be 1, because the arc that reached its bound can point
+ *                                   the wrong way; after mcf_solve the objective is still the old value + rate * d;
+ *                  d == limit + 1   tree_violations >= 1 when 0 <= limit_arc < m, art_flips >= 1 when limit_arc >= m (a capacity
+ *                                   cannot fall below 0: where down == cap there is no such edit);
+ *                  art_rising > 0   any d > 0 leaves artificial flow: on a handle that was optimal the edited instance is infeasible.
+ *                Ranges for several edits at once, for capping an uncapacitated arc and beyond the flip of an artificial arc
+ *                are not given.
+ *   lists        from / to: node indices, arc: caller's arc indices; duplicates allowed, entry i answers pair / arc i; for
+ *                capacities count < 0 with arc == NULL = all m arcs in the caller's order.  Every output array may be NULL.
+ *   method       k_rng_depth and the ancestor tables of mcf_cost_ranges; two more tables hold min U / min D over the tree arcs
+ *                of v and its next 2^k - 1 ancestors together with the attaining node (ties: the lower half upwards, the upper
+ *                half downwards), built level by level; every query reads one cell per jump of its two tree paths, at most
+ *                3 K + 2 jumps, and an arc at capacity asks both directions in one enumeration.  Gather only, no atomics.
+ *   report       basic_real / basic_artificial: the tree arcs; at_capacity: the non-basic arcs at capacity (capacity call; 0
+ *                from the supply call); inf_count / zero_count: returned sides (limit; down and up) equal to MCF_RANGE_INF / 0;
+ *                art_rising_count: pairs returned with art_rising > 0 (supply call), pushes of arcs at capacity -- two per
+ *                arc, all arcs of the handle -- that raise artificial flow (capacity call).
+ *   read-only    exactly as mcf_certify and mcf_cost_ranges: nothing the solver reads is written and a later mcf_solve makes
+ *                the same pivots.  Valid between solves in any state of the handle, on every engine path, both tree layouts,
+ *                every rule and key_mode, handles that dropped their reduced costs and handles with shard_count > 1.
+ *                count == 0, n == 1, and for capacities m == 0: MCF_OK without device work (pairs of the one node with itself
+ *                get MCF_RANGE_INF, no arc, rate 0).
+ *   errors       MCF_E_BAD_ARG, all checked before any device work: null handle; a node outside [0, n) or an arc outside
+ *                [0, m); null lists with count > 0; a list together with count < 0 (capacities), count < 0 (supplies).
+ *                MCF_E_ALLOC: scratch cannot be allocated; the handle is untouched.
+ * Scratch -- the tables of mcf_cost_ranges plus 8 B x K x (n + 1), the answers 40 B x m / 28 B x count, the lists -- is allocated
+ * on first use, shared with mcf_cost_ranges where it is the same, and freed by mcf_destroy. */
+typedef struct mcf_flow_ranges_report {
+    int64_t basic_real, basic_artificial, at_capacity;
+    int64_t max_depth, levels;                        /* greatest depth of the tree; K */
+    int64_t inf_count, zero_count;                    /* returned sides equal to MCF_RANGE_INF / to 0 */
+    int64_t art_rising_count;
+    int64_t big_m;                                    /* the big-M the rates are stated at */
+    double  device_ms;                                /* HIP events round the device passes (the depth pass and the rest; the
+                                                         upload of the lists is not counted) */
+} mcf_flow_ranges_report;
+int mcf_supply_ranges(mcf_handle* h, int64_t count, const int32_t* from, const int32_t* to,
+                      int64_t* limit, int64_t* limit_arc, int64_t* rate, int32_t* art_rising /* each may be NULL */,
+                      mcf_flow_ranges_report* out /* may be NULL */);
+int mcf_capacity_ranges(mcf_handle* h, int64_t count, const int64_t* arc /* count < 0 and NULL = all m */,
+                        int64_t* down, int64_t* up, int64_t* down_arc, int64_t* up_arc, int64_t* rate /* each may be NULL */,
+                        mcf_flow_ranges_report* out /* may be NULL */);
 
 /* ---- arc-sharded multi-GPU pivoting: one handle per rank, every rank holds the full
  * replicated state and prices only its shard (options.shard_rank / shard_count).  Per pivot:

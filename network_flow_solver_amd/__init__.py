@@ -19,6 +19,7 @@ from .data import (
     ProgressInfo,
     SoAProblem,
     SolverOptions,
+    SupplyRange,
     build_problem,
 )
 from .dimacs import parse_dimacs_file, parse_dimacs_soa, parse_dimacs_string
@@ -42,7 +43,7 @@ __all__ = [
     "SolverConfigurationError", "UnboundedProblemError", "NetworkSimplex", "load_problem", "save_result",
     "solve_many",
     "solve_min_cost_flow",
-    "BottleneckArc", "ValidationResult", "compute_bottleneck_arcs", "validate_flow", "InfeasibleCut", "UnboundedRay",
+    "BottleneckArc", "ValidationResult", "compute_bottleneck_arcs", "validate_flow", "InfeasibleCut", "UnboundedRay", "SupplyRange",
 ]
 
 __version__ = "0.1.0"

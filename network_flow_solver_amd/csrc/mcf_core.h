@@ -2215,3 +2215,97 @@ MCF_HD void mcf_rng_nonbasic(int32_t state, int64_t s, int64_t* down, int64_t* u
 MCF_HD void mcf_rng_basic(bool child_is_tail, int64_t P, int64_t N, int64_t* down, int64_t* up) {
     if (child_is_tail) { *up = N; *down = P; } else { *up = P; *down = N; }
 }
+
+// ====================================================================== flow ranging on the resident basis (mcf_supply_ranges, mcf_capacity_ranges)
+// The primal mirror image of cost ranging.  push(x -> y) is the largest amount the tree can carry from node x to node y with
+// every tree flow inside its bounds: the minimum of the residuals of the tree arcs on the path, "upward" residuals U from x to
+// the join, "downward" residuals D from the join to y.  Cost ranging SCATTERS a value of every non-basic arc onto the tree
+// arcs of its path; this GATHERS a minimum over them, with the same ancestors and the same enumeration of a path
+// (mcf_rng_jumps): table cell X[k][v] stands for the tree arcs of v and its next 2^k - 1 ancestors, level k is combined from
+// the two halves at level k - 1, and a query reads one cell per jump.  Every cell carries the node whose tree arc attains
+// its value, chosen by a rule that depends on nothing but the path: the FIRST attaining arc in push order.  Upwards that is
+// the lower one (the half nearer v wins ties), downwards the upper one (the far half wins ties), and the x side wins over
+// the y side.  As before the logic lives here, shared by the kernels (mcf_passes_dev.h: k_frng_*) and by the host restatement
+// of the CPU tests (csrc/mcf_flow_ranges_host.cpp).
+struct McfFrngMin { int64_t val; int32_t id; };   // a residual and the node whose tree arc attains it (-1: none)
+
+// level-0 ancestor: the parent, and the root for the root itself and for a record that names no node
+MCF_HD int32_t mcf_rng_anc0(int32_t v, int32_t parent, int32_t n_nodes) {
+    const int32_t root = n_nodes - 1;
+    return (v == root || parent < 0 || parent >= n_nodes) ? root : parent;
+}
+
+// Residuals of the tree arc of a node: pred = (arc << 1) | up, up = the arc points child -> parent; arcs >= m are artificial.
+//   with the arc:     cap - flow when capped, MCF_RNG_INF when uncapacitated or artificial (an artificial arc takes any amount:
+//                     that the push raises artificial flow is counted separately, mcf_frng_rising)
+//   against the arc:  flow (past it an artificial arc would turn round: mcf_update_rhs counts an art_flip)
+// U: residual of a push child -> parent, D: parent -> child.  Nothing is clamped: a state out of bounds reports what is there.
+MCF_HD void mcf_frng_residuals(int32_t pred, int64_t m, int64_t cap, int64_t flow, int64_t* U, int64_t* D) {
+    const bool up = (pred & 1) != 0;
+    const int64_t with = ((int64_t)(pred >> 1) >= m || cap >= MCF_INF) ? MCF_RNG_INF : cap - flow;
+    *U = up ? with : flow;
+    *D = up ? flow : with;
+}
+// does a push over the tree arc of a node (upward = child -> parent) raise the flow of an artificial arc?
+MCF_HD bool mcf_frng_rising(int32_t pred, int64_t m, bool upward) {
+    return pred >= 0 && (int64_t)(pred >> 1) >= m && ((pred & 1) != 0) == upward;
+}
+
+// combine two stretches of a path, `near` the one next to the node the cell belongs to, `far` the one above it
+MCF_HD McfFrngMin mcf_frng_up(McfFrngMin near, McfFrngMin far) { return far.val < near.val ? far : near; }      // pushed bottom-up: near comes first
+MCF_HD McfFrngMin mcf_frng_down(McfFrngMin near, McfFrngMin far) { return far.val <= near.val ? far : near; }   // pushed top-down: far comes first
+
+// One push while its path is enumerated.  The cells of either side arrive bottom-up (mcf_rng_jumps emits them so), those of
+// the two sides in any interleaving.
+struct McfFrngPush { McfFrngMin up, dn; int32_t rising; };
+MCF_HD void mcf_frng_begin(McfFrngPush* p) { p->up.val = p->dn.val = MCF_RNG_INF; p->up.id = p->dn.id = -1; p->rising = 0; }
+MCF_HD void mcf_frng_climb(McfFrngPush* p, McfFrngMin cell) { p->up = mcf_frng_up(p->up, cell); }      // a cell of the x side, table U
+MCF_HD void mcf_frng_descend(McfFrngPush* p, McfFrngMin cell) { p->dn = mcf_frng_down(p->dn, cell); }  // a cell of the y side, table D
+MCF_HD McfFrngMin mcf_frng_end(const McfFrngPush& p) {
+    McfFrngMin r = p.dn.val < p.up.val ? p.dn : p.up;   // the x side is pushed first
+    if (r.val == MCF_RNG_INF) r.id = -1;
+    return r;
+}
+
+// push(x -> y) through the tables.  anc(k, v): the ancestors; cell(w, k, v): table w (0 = U, 1 = D); depth(v), pred(v): the node records.
+template <typename Anc, typename Cell, typename Depth, typename Pred>
+MCF_HD void mcf_frng_push(int32_t x, int32_t y, int K, int64_t m, Anc anc, Cell cell, Depth depth, Pred pred, McfFrngPush* p) {
+    mcf_frng_begin(p);
+    if (x == y) return;
+    mcf_rng_jumps(x, depth(x), y, depth(y), K, anc, [&](int side, int k, int32_t v) {
+        if (side == 0) mcf_frng_climb(p, cell(0, k, v)); else mcf_frng_descend(p, cell(1, k, v));
+        if (k == 0 && mcf_frng_rising(pred(v), m, side == 0)) ++p->rising;   // artificial arcs touch the root: never inside a longer jump
+    });
+}
+// both pushes between the end points of one arc in ONE enumeration: fwd = push(t -> hd), back = push(hd -> t)
+template <typename Anc, typename Cell, typename Depth, typename Pred>
+MCF_HD void mcf_frng_push_both(int32_t t, int32_t hd, int K, int64_t m, Anc anc, Cell cell, Depth depth, Pred pred, McfFrngPush* fwd, McfFrngPush* back) {
+    mcf_frng_begin(fwd);
+    mcf_frng_begin(back);
+    if (t == hd) return;
+    mcf_rng_jumps(t, depth(t), hd, depth(hd), K, anc, [&](int side, int k, int32_t v) {
+        const McfFrngMin u = cell(0, k, v), d = cell(1, k, v);
+        if (side == 0) { mcf_frng_climb(fwd, u); mcf_frng_descend(back, d); } else { mcf_frng_descend(fwd, d); mcf_frng_climb(back, u); }
+        if (k == 0) {
+            const int32_t pr = pred(v);
+            if (mcf_frng_rising(pr, m, side == 0)) ++fwd->rising;
+            if (mcf_frng_rising(pr, m, side != 0)) ++back->rising;
+        }
+    });
+}
+
+// The capacity range of one arc (include/mcf.h has the table).  `self`: the arc's own caller's index; fwd / back: the two pushes
+// of an arc at capacity, their ids already turned into caller's indices (unused for the other rows).
+struct McfFrngArc { int64_t down, up, down_arc, up_arc, rate; };
+MCF_HD bool mcf_frng_needs_push(int32_t state, int64_t cap) { return state < 0 && cap < MCF_INF; }
+MCF_HD McfFrngArc mcf_frng_arc(int32_t state, int64_t cap, int64_t flow, int64_t rc, int64_t self, int64_t fwd, int64_t fwd_arc, int64_t back, int64_t back_arc) {
+    McfFrngArc r = {MCF_RNG_INF, MCF_RNG_INF, -1, -1, 0};
+    if (cap >= MCF_INF) return r;                                   // uncapacitated: no capacity to change
+    if (state > 0) { r.down = cap; return r; }                      // non-basic at its lower bound: the capacity is not in use
+    if (state == 0) { r.down = cap - flow; r.down_arc = self; return r; }   // basic: down to its own flow
+    // non-basic at capacity: less capacity sends the difference t -> hd through the tree, more capacity brings it back hd -> t
+    if (cap < fwd) { r.down = cap; r.down_arc = self; } else { r.down = fwd; r.down_arc = fwd_arc; }
+    r.up = back; r.up_arc = back_arc;
+    r.rate = rc;
+    return r;
+}

@@ -2477,6 +2477,17 @@ struct mcf_handle {
     int64_t rng_arcs = 0;                                  // entries the two arrays hold
     int64_t *d_rng_idx = nullptr, *d_rng_gdown = nullptr, *d_rng_gup = nullptr;   // an index list and its gathered answer
     int64_t rng_list = 0;                                  // entries the three arrays hold
+    // mcf_supply_ranges / mcf_capacity_ranges: the ancestors and the two 8-byte tables above are shared (U = d_rng_p, D = d_rng_n)
+    unsigned long long* d_frng_info = nullptr;             // [FRNG_COUNTERS]
+    int32_t *d_frng_uid = nullptr, *d_frng_did = nullptr;  // [levels][n_nodes] the node whose tree arc attains the cell
+    int64_t frng_cells = 0;                                // levels * n_nodes the two tables hold
+    int64_t* d_frng_out = nullptr;                         // [5][m] down, up, down_arc, up_arc, rate in the caller's order
+    int64_t frng_arcs = 0;                                 // m the array is laid out for
+    int64_t *d_frng_idx = nullptr, *d_frng_gout = nullptr; // an index list [count] and its gathered answer [5][count]
+    int64_t frng_list = 0;
+    int32_t *d_frng_pair = nullptr, *d_frng_rise = nullptr;   // pairs: [2][count] from, to; [count] art_rising
+    int64_t* d_frng_pout = nullptr;                        // [3][count] limit, limit_arc, rate
+    int64_t frng_pairs = 0;
 };
 
 namespace {
@@ -2926,6 +2937,8 @@ void free_all(mcf_handle* h) {
     (void)hipFree(h->d_rhs_idx); (void)hipFree(h->d_rhs_val); (void)hipFree(h->d_rhs_bal); (void)hipFree(h->d_rhs_part); (void)hipFree(h->d_rhs_info);
     (void)hipFree(h->d_rng_part); (void)hipFree(h->d_rng_info); (void)hipFree(h->d_rng_anc); (void)hipFree(h->d_rng_p); (void)hipFree(h->d_rng_n);
     (void)hipFree(h->d_rng_down); (void)hipFree(h->d_rng_up); (void)hipFree(h->d_rng_idx); (void)hipFree(h->d_rng_gdown); (void)hipFree(h->d_rng_gup);
+    (void)hipFree(h->d_frng_info); (void)hipFree(h->d_frng_uid); (void)hipFree(h->d_frng_did); (void)hipFree(h->d_frng_out); (void)hipFree(h->d_frng_idx);
+    (void)hipFree(h->d_frng_gout); (void)hipFree(h->d_frng_pair); (void)hipFree(h->d_frng_rise); (void)hipFree(h->d_frng_pout);
     if (h->h_ctx) pinned_give(reinterpret_cast<char*>(h->h_ctx));   // (h_one lives in the same slot)
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
 }

@@ -1068,3 +1068,153 @@ __global__ __launch_bounds__(kRngThreads) void k_rng_gather(int64_t count, const
     rhs_count(info, RNG_INF_DOWN, inf_down);
     rhs_count(info, RNG_INF_UP, inf_up);
 }
+
+// ------------------------------------------------------------------ mcf_supply_ranges / mcf_capacity_ranges: flow ranging on the resident basis
+// Logic: mcf_core.h (mcf_frng_*).  Indexed by node like k_rng_*: both tree layouts run the same code.  The ancestors
+// (anc[k][v]) and the two 8-byte tables are the arrays of cost ranging, here U and D; two 4-byte tables beside them hold the
+// attaining node.  Gather only: no cell is written by more than one lane, there is no atomic but the census.  Bytes each pass
+// moves (N = n + 1 nodes, m arcs, K levels, 28 B per node and level):
+//   k_rng_depth   as for cost ranging: the greatest depth, one word back to the host;
+//   k_frng_base   one lane per node: node record (16 B), the tree arc's walk record gathered (16 B), level 0 written (28 B);
+//   k_frng_level  one launch per level 1 .. K - 1: the lane's own cells of the level below (28 B), the cells of its ancestor
+//                 there gathered (28 B), one level written (28 B);
+//   k_frng_pairs  one lane per pair: two node ids (8 B), two gathered node records for the depths, two potentials (8 B each);
+//                 per jump one gathered ancestor (4 B) and one gathered cell (12 B), a node record for a level-0 jump;
+//                 at most 3 K + 2 jumps; the attaining node's record and its arc's caller's index (16 + 4 B); 28 B written;
+//   k_frng_arcs   one lane per engine arc, workgroup b on head bucket b % 8 like k_rng_arcs: state (1 B), walk record (16 B),
+//                 orig (4 B), 40 B written at the caller's index; an arc at capacity besides tail, head, cost (4 B each), two
+//                 potentials, two node records, and per jump one ancestor and BOTH cells (24 B): its two pushes share one
+//                 enumeration.  Bound by its gathers like k_rng_arcs: no non-temporal variant;
+//   k_frng_gather one lane per requested index: 8 B index, 40 B gathered, 40 B written.
+// Census by wave reduction, one atomic per wave and counter (rhs_count).
+constexpr int kFrngThreads = kPassThreads;
+constexpr int kFrngMaxBlocks = kRngMaxBlocks;
+enum { FRNG_BASIC_REAL = 0, FRNG_BASIC_ART = 1, FRNG_AT_CAP = 2, FRNG_INF = 3, FRNG_ZERO = 4, FRNG_RISING = 5, FRNG_COUNTERS = 6 };
+
+struct FrngArgs {
+    int32_t K;                 // levels
+    int32_t count_sides;       // k_frng_arcs: 1 = the whole arrays are the answer, INF and 0 sides are counted as they are written
+    int32_t* anc;              // [K][n_nodes]
+    int64_t* val[2];           // [K][n_nodes] each: 0 = U, 1 = D
+    int32_t* id[2];            // [K][n_nodes] each: the attaining node
+    int64_t* out;              // k_frng_arcs: [5][m] down, up, down_arc, up_arc, rate in the caller's order
+    unsigned long long* info;  // [FRNG_COUNTERS]
+};
+
+// the attaining node as a caller's index: its tree arc through orig, m + v for an artificial one
+__device__ __forceinline__ int64_t frng_index(const McfView& v, int32_t node) {
+    if (node < 0) return -1;
+    const int64_t a = v.node[node].pred >> 1;
+    return a >= v.m ? a : (int64_t)v.orig[a];
+}
+
+__global__ __launch_bounds__(kFrngThreads) void k_frng_base(McfView v, FrngArgs a) {
+    const int32_t N = v.n_nodes, root = N - 1;
+    int32_t real = 0, art = 0;
+    for (int32_t u = blockIdx.x * kFrngThreads + threadIdx.x; u < N; u += gridDim.x * kFrngThreads) {
+        const McfNode nd = v.node[u];
+        int64_t U = MCF_RNG_INF, D = MCF_RNG_INF;
+        int32_t id = -1;
+        if (u != root && nd.pred >= 0 && (int64_t)(nd.pred >> 1) < v.m + root) {   // (a record that names no arc limits nothing)
+            const int64_t arc = nd.pred >> 1;
+            const McfArcW w = v.arcw[arc];
+            mcf_frng_residuals(nd.pred, v.m, w.cap, w.flow, &U, &D);
+            id = u;
+            if (arc >= v.m) ++art; else ++real;
+        }
+        a.anc[u] = mcf_rng_anc0(u, nd.parent, N);
+        a.val[0][u] = U; a.val[1][u] = D;
+        a.id[0][u] = id; a.id[1][u] = id;
+    }
+    rhs_count(a.info, FRNG_BASIC_REAL, real);
+    rhs_count(a.info, FRNG_BASIC_ART, art);
+}
+
+__global__ __launch_bounds__(kFrngThreads) void k_frng_level(int32_t n_nodes, int32_t k, FrngArgs a) {
+    const size_t row = (size_t)k * n_nodes, low = row - n_nodes;
+    for (int32_t u = blockIdx.x * kFrngThreads + threadIdx.x; u < n_nodes; u += gridDim.x * kFrngThreads) {
+        const int32_t up = a.anc[low + u];
+        a.anc[row + u] = a.anc[low + up];
+        const McfFrngMin U = mcf_frng_up({a.val[0][low + u], a.id[0][low + u]}, {a.val[0][low + up], a.id[0][low + up]});
+        const McfFrngMin D = mcf_frng_down({a.val[1][low + u], a.id[1][low + u]}, {a.val[1][low + up], a.id[1][low + up]});
+        a.val[0][row + u] = U.val; a.id[0][row + u] = U.id;
+        a.val[1][row + u] = D.val; a.id[1][row + u] = D.id;
+    }
+}
+
+__global__ __launch_bounds__(kFrngThreads) void k_frng_pairs(McfView v, FrngArgs a, int64_t count, const int32_t* __restrict__ from, const int32_t* __restrict__ to,
+                                                             int64_t* __restrict__ limit, int64_t* __restrict__ limit_arc, int64_t* __restrict__ rate,
+                                                             int32_t* __restrict__ rising) {
+    const int32_t N = v.n_nodes;
+    int32_t n_inf = 0, n_zero = 0, n_rising = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kFrngThreads + threadIdx.x; i < count; i += (int64_t)gridDim.x * kFrngThreads) {
+        const int32_t x = from[i], y = to[i];
+        McfFrngPush p;
+        mcf_frng_push(x, y, a.K, v.m,
+                      [&](int k, int32_t u) { return a.anc[(size_t)k * N + u]; },
+                      [&](int w, int k, int32_t u) { return McfFrngMin{a.val[w][(size_t)k * N + u], a.id[w][(size_t)k * N + u]}; },
+                      [&](int32_t u) { return v.node[u].depth; }, [&](int32_t u) { return v.node[u].pred; }, &p);
+        const McfFrngMin r = mcf_frng_end(p);
+        limit[i] = r.val;
+        limit_arc[i] = frng_index(v, r.id);
+        rate[i] = v.pi[y] - v.pi[x];
+        rising[i] = p.rising;
+        if (r.val == MCF_RNG_INF) ++n_inf;
+        if (r.val == 0) ++n_zero;
+        if (p.rising > 0) ++n_rising;
+    }
+    rhs_count(a.info, FRNG_INF, n_inf);
+    rhs_count(a.info, FRNG_ZERO, n_zero);
+    rhs_count(a.info, FRNG_RISING, n_rising);
+}
+
+__global__ __launch_bounds__(kFrngThreads) void k_frng_arcs(McfView v, FrngArgs a) {
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+    const int32_t N = v.n_nodes;
+    const int64_t m = v.m;
+    int32_t at_cap = 0, n_inf = 0, n_zero = 0, n_rising = 0;
+    for (int64_t e = lo + lb * kFrngThreads + threadIdx.x; e < hi; e += nlb * kFrngThreads) {
+        const int32_t st = v.state[e];
+        const McfArcW w = v.arcw[e];
+        const int64_t o = v.orig[e];
+        int64_t rc = 0;
+        McfFrngMin fwd = {MCF_RNG_INF, -1}, back = {MCF_RNG_INF, -1};
+        if (mcf_frng_needs_push(st, w.cap)) {
+            ++at_cap;
+            const int32_t t = v.tail[e], hd = v.head[e];
+            rc = (int64_t)v.cost[e] + v.pi[t] - v.pi[hd];
+            McfFrngPush pf, pb;
+            mcf_frng_push_both(t, hd, a.K, m,
+                               [&](int k, int32_t u) { return a.anc[(size_t)k * N + u]; },
+                               [&](int w, int k, int32_t u) { return McfFrngMin{a.val[w][(size_t)k * N + u], a.id[w][(size_t)k * N + u]}; },
+                               [&](int32_t u) { return v.node[u].depth; }, [&](int32_t u) { return v.node[u].pred; }, &pf, &pb);
+            fwd = mcf_frng_end(pf);
+            back = mcf_frng_end(pb);
+            n_rising += (pf.rising > 0) + (pb.rising > 0);
+        }
+        const McfFrngArc r = mcf_frng_arc(st, w.cap, w.flow, rc, o, fwd.val, frng_index(v, fwd.id), back.val, frng_index(v, back.id));
+        a.out[o] = r.down; a.out[m + o] = r.up; a.out[2 * m + o] = r.down_arc; a.out[3 * m + o] = r.up_arc; a.out[4 * m + o] = r.rate;
+        n_inf += (r.down == MCF_RNG_INF) + (r.up == MCF_RNG_INF);
+        n_zero += (r.down == 0) + (r.up == 0);
+    }
+    rhs_count(a.info, FRNG_AT_CAP, at_cap);
+    rhs_count(a.info, FRNG_RISING, n_rising);
+    if (a.count_sides) { rhs_count(a.info, FRNG_INF, n_inf); rhs_count(a.info, FRNG_ZERO, n_zero); }
+}
+
+// rows of `out` ([5][m]) at the indices asked -> `g` ([5][count])
+__global__ __launch_bounds__(kFrngThreads) void k_frng_gather(int64_t count, int64_t m, const int64_t* __restrict__ idx, const int64_t* __restrict__ out,
+                                                              int64_t* __restrict__ g, unsigned long long* __restrict__ info) {
+    int32_t n_inf = 0, n_zero = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kFrngThreads + threadIdx.x; i < count; i += (int64_t)gridDim.x * kFrngThreads) {
+        const int64_t o = idx[i];
+        const int64_t dn = out[o], up = out[m + o];
+        g[i] = dn; g[count + i] = up; g[2 * count + i] = out[2 * m + o]; g[3 * count + i] = out[3 * m + o]; g[4 * count + i] = out[4 * m + o];
+        n_inf += (dn == MCF_RNG_INF) + (up == MCF_RNG_INF);
+        n_zero += (dn == 0) + (up == 0);
+    }
+    rhs_count(info, FRNG_INF, n_inf);
+    rhs_count(info, FRNG_ZERO, n_zero);
+}

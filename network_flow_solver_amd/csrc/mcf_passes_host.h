@@ -988,6 +988,35 @@ int mcf_certify_cut(mcf_handle* h, const int8_t* in_S, int8_t* S_out, mcf_cut* o
     return MCF_OK;
 }
 
+// ---- what cost ranging and flow ranging share: the greatest depth, which decides the number of levels (one word comes back
+// before the tables are sized; *ms: the device time of the pass), and the ancestors with the two 8-byte tables
+static int rng_max_depth(mcf_handle* h, McfRngDepthAcc* D, float* ms) {
+    int rc;
+    if ((rc = lazy_group(h, "ranging partials", {{&h->d_rng_part, kCertMaxBlocks + 1}, {&h->d_rng_info, (size_t)RNG_COUNTERS}})) != MCF_OK) return rc;
+    for (hipEvent_t& ev : h->ct_ev) if (!ev) HIP_TRY(h, hipEventCreate(&ev));
+    const int32_t N = h->im.n_nodes;
+    const int nb = node_grid(N);
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
+    hipLaunchKernelGGL(k_rng_depth, dim3(nb), dim3(kRngThreads), 0, s, (const McfNode*)h->d_node, N, h->d_rng_part);
+    hipLaunchKernelGGL(k_final<McfRngDepthAcc>, dim3(1), dim3(kPassThreads), 0, s, h->d_rng_part, nb);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(D, h->d_rng_part + nb, sizeof *D, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, hipEventElapsedTime(ms, h->ct_ev[0], h->ct_ev[1]));
+    return MCF_OK;
+}
+// released and allocated again when the levels outgrew them
+static int rng_tables(mcf_handle* h, int64_t cells) {
+    if (cells <= h->rng_cells) return MCF_OK;
+    lazy_release({{&h->d_rng_anc, 0}, {&h->d_rng_p, 0}, {&h->d_rng_n, 0}});
+    h->rng_cells = 0;
+    const int rc = lazy_alloc(h, "ranging tables", {{&h->d_rng_anc, 1}, {&h->d_rng_p, 1}, {&h->d_rng_n, 1}}, (size_t)cells);
+    if (rc == MCF_OK) h->rng_cells = cells;
+    return rc;
+}
+
 // ---- cost ranging on the resident basis (include/mcf.h; kernels k_rng_* above, logic mcf_core.h: mcf_rng_*)
 int mcf_cost_ranges(mcf_handle* h, int64_t count, const int64_t* arc, int64_t* down, int64_t* up, mcf_ranges_report* out) {
     if (!h) return MCF_E_BAD_ARG;
@@ -1011,33 +1040,16 @@ int mcf_cost_ranges(mcf_handle* h, int64_t count, const int64_t* arc, int64_t* d
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = sync_ctx(h, h->stream);
     if (rc) return rc;
-    if ((rc = lazy_group(h, "ranging partials", {{&h->d_rng_part, kCertMaxBlocks + 1}, {&h->d_rng_info, (size_t)RNG_COUNTERS}})) != MCF_OK) return rc;
-    for (hipEvent_t& ev : h->ct_ev) if (!ev) HIP_TRY(h, hipEventCreate(&ev));
     const int32_t N = im.n_nodes;
     const int nb = node_grid(N);
     hipStream_t s = h->stream;
-
-    // ---- the greatest depth decides the number of levels: one word comes back before the tables are sized
     McfRngDepthAcc D;
-    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));
-    hipLaunchKernelGGL(k_rng_depth, dim3(nb), dim3(kRngThreads), 0, s, (const McfNode*)h->d_node, N, h->d_rng_part);
-    hipLaunchKernelGGL(k_final<McfRngDepthAcc>, dim3(1), dim3(kPassThreads), 0, s, h->d_rng_part, nb);
-    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(&D, h->d_rng_part + nb, sizeof D, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
     float ms1 = 0, ms2 = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms1, h->ct_ev[0], h->ct_ev[1]));
+    if ((rc = rng_max_depth(h, &D, &ms1)) != MCF_OK) return rc;
     const int K = mcf_rng_levels(D.depth);
 
-    // ---- scratch: the tables (released and allocated again when the levels outgrew them), the answer (when m outgrew it: mcf_add_arcs), the list
-    const int64_t cells = (int64_t)K * N;
-    if (cells > h->rng_cells) {
-        lazy_release({{&h->d_rng_anc, 0}, {&h->d_rng_p, 0}, {&h->d_rng_n, 0}});
-        h->rng_cells = 0;
-        if ((rc = lazy_alloc(h, "ranging tables", {{&h->d_rng_anc, 1}, {&h->d_rng_p, 1}, {&h->d_rng_n, 1}}, (size_t)cells)) != MCF_OK) return rc;
-        h->rng_cells = cells;
-    }
+    // ---- scratch: the tables, the answer (released and allocated again when m outgrew it: mcf_add_arcs), the list
+    if ((rc = rng_tables(h, (int64_t)K * N)) != MCF_OK) return rc;
     if (im.m > h->rng_arcs) {
         lazy_release({{&h->d_rng_down, 0}, {&h->d_rng_up, 0}});
         h->rng_arcs = 0;
@@ -1083,6 +1095,169 @@ int mcf_cost_ranges(mcf_handle* h, int64_t count, const int64_t* arc, int64_t* d
     rep.inf_down = (int64_t)info[RNG_INF_DOWN];
     rep.inf_up = (int64_t)info[RNG_INF_UP];
     rep.device_ms = ms1 + ms2;
+    if (out) *out = rep;
+    return MCF_OK;
+}
+
+// ---- flow ranging on the resident basis (include/mcf.h; kernels k_frng_* above, logic mcf_core.h: mcf_frng_*)
+// Everything the two calls share up to their query pass: the levels, the scratch of the tables, and -- enqueued behind the
+// event ct_ev[0] -- the counters, level 0 and the levels above it.
+static int frng_tables(mcf_handle* h, FrngArgs* a, McfRngDepthAcc* D, float* ms_depth) {
+    int rc;
+    if ((rc = rng_max_depth(h, D, ms_depth)) != MCF_OK) return rc;
+    const int32_t N = h->im.n_nodes;
+    const int K = mcf_rng_levels(D->depth);
+    const int64_t cells = (int64_t)K * N;
+    if ((rc = rng_tables(h, cells)) != MCF_OK) return rc;
+    if (cells > h->frng_cells) {
+        lazy_release({{&h->d_frng_uid, 0}, {&h->d_frng_did, 0}});
+        h->frng_cells = 0;
+        if ((rc = lazy_alloc(h, "flow ranging tables", {{&h->d_frng_uid, 1}, {&h->d_frng_did, 1}}, (size_t)cells)) != MCF_OK) return rc;
+        h->frng_cells = cells;
+    }
+    if ((rc = lazy_group(h, "flow ranging counters", {{&h->d_frng_info, (size_t)FRNG_COUNTERS}})) != MCF_OK) return rc;
+    std::memset(a, 0, sizeof *a);
+    a->K = K;
+    a->anc = h->d_rng_anc;
+    a->val[0] = h->d_rng_p; a->val[1] = h->d_rng_n;
+    a->id[0] = h->d_frng_uid; a->id[1] = h->d_frng_did;
+    a->info = h->d_frng_info;
+    return MCF_OK;
+}
+static int frng_build(mcf_handle* h, const FrngArgs& a) {
+    const int32_t N = h->im.n_nodes;
+    const int nb = node_grid(N);
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemsetAsync(h->d_frng_info, 0, FRNG_COUNTERS * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_frng_base, dim3(nb), dim3(kFrngThreads), 0, s, h->view, a);
+    for (int k = 1; k < a.K; ++k) hipLaunchKernelGGL(k_frng_level, dim3(nb), dim3(kFrngThreads), 0, s, N, k, a);
+    return MCF_OK;
+}
+static void frng_report(mcf_flow_ranges_report* rep, const unsigned long long* info, const McfRngDepthAcc& D, int K, double ms) {
+    rep->basic_real = (int64_t)info[FRNG_BASIC_REAL];
+    rep->basic_artificial = (int64_t)info[FRNG_BASIC_ART];
+    rep->at_capacity = (int64_t)info[FRNG_AT_CAP];
+    rep->max_depth = D.depth;
+    rep->levels = K;
+    rep->inf_count = (int64_t)info[FRNG_INF];
+    rep->zero_count = (int64_t)info[FRNG_ZERO];
+    rep->art_rising_count = (int64_t)info[FRNG_RISING];
+    rep->device_ms = ms;
+}
+static void frng_empty_report(mcf_flow_ranges_report* rep, const McfHostImage& im) {
+    std::memset(rep, 0, sizeof *rep);
+    rep->big_m = im.big_m;
+    rep->basic_artificial = im.n;
+    rep->levels = 1;
+    rep->max_depth = im.n > 0 ? 1 : 0;
+}
+
+int mcf_supply_ranges(mcf_handle* h, int64_t count, const int32_t* from, const int32_t* to, int64_t* limit, int64_t* limit_arc, int64_t* rate,
+                      int32_t* art_rising, mcf_flow_ranges_report* out) {
+    if (!h) return MCF_E_BAD_ARG;
+    const McfHostImage& im = h->im;
+    if (count < 0 || (count > 0 && (!from || !to))) { h->err = "mcf_supply_ranges: a negative count, or a positive one without both node lists"; return MCF_E_BAD_ARG; }
+    for (int64_t i = 0; i < count; ++i)
+        if (from[i] < 0 || from[i] >= im.n || to[i] < 0 || to[i] >= im.n) { h->err = "mcf_supply_ranges: node index outside [0, n)"; return MCF_E_BAD_ARG; }
+    mcf_flow_ranges_report rep;
+    frng_empty_report(&rep, im);
+    if (count == 0 || im.n <= 1) {   // no pair, or only pairs of the one node with itself: nothing limits, nothing moves
+        for (int64_t i = 0; i < count; ++i) {
+            if (limit) limit[i] = MCF_RANGE_INF;
+            if (limit_arc) limit_arc[i] = -1;
+            if (rate) rate[i] = 0;
+            if (art_rising) art_rising[i] = 0;
+        }
+        rep.inf_count = count;
+        if (out) *out = rep;
+        return MCF_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    FrngArgs a;
+    McfRngDepthAcc D;
+    float ms1 = 0, ms2 = 0;
+    if ((rc = frng_tables(h, &a, &D, &ms1)) != MCF_OK) return rc;
+    if ((rc = lazy_grow(h, "supply range pairs", &h->frng_pairs, count, {{&h->d_frng_pair, 2}, {&h->d_frng_rise, 1}, {&h->d_frng_pout, 3}})) != MCF_OK) return rc;
+    hipStream_t s = h->stream;
+    int32_t* d_from = h->d_frng_pair;
+    int32_t* d_to = h->d_frng_pair + count;
+    int64_t *d_limit = h->d_frng_pout, *d_arc = h->d_frng_pout + count, *d_rate = h->d_frng_pout + 2 * count;
+    HIP_TRY(h, hipMemcpyAsync(d_from, from, (size_t)count * 4, hipMemcpyHostToDevice, s));   // (the call ends with a synchronisation)
+    HIP_TRY(h, hipMemcpyAsync(d_to, to, (size_t)count * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));   // (after the uploads: device_ms is the passes alone)
+    if ((rc = frng_build(h, a)) != MCF_OK) return rc;
+    hipLaunchKernelGGL(k_frng_pairs, dim3(uc_blocks_for(count)), dim3(kFrngThreads), 0, s, h->view, a, count, (const int32_t*)d_from, (const int32_t*)d_to,
+                       d_limit, d_arc, d_rate, h->d_frng_rise);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long info[FRNG_COUNTERS] = {0, 0, 0, 0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(info, h->d_frng_info, sizeof info, hipMemcpyDeviceToHost, s));
+    if (limit) HIP_TRY(h, hipMemcpyAsync(limit, d_limit, (size_t)count * 8, hipMemcpyDeviceToHost, s));
+    if (limit_arc) HIP_TRY(h, hipMemcpyAsync(limit_arc, d_arc, (size_t)count * 8, hipMemcpyDeviceToHost, s));
+    if (rate) HIP_TRY(h, hipMemcpyAsync(rate, d_rate, (size_t)count * 8, hipMemcpyDeviceToHost, s));
+    if (art_rising) HIP_TRY(h, hipMemcpyAsync(art_rising, h->d_frng_rise, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, hipEventElapsedTime(&ms2, h->ct_ev[0], h->ct_ev[1]));
+    frng_report(&rep, info, D, a.K, ms1 + ms2);
+    if (out) *out = rep;
+    return MCF_OK;
+}
+
+int mcf_capacity_ranges(mcf_handle* h, int64_t count, const int64_t* arc, int64_t* down, int64_t* up, int64_t* down_arc, int64_t* up_arc, int64_t* rate,
+                        mcf_flow_ranges_report* out) {
+    if (!h) return MCF_E_BAD_ARG;
+    const McfHostImage& im = h->im;
+    const bool all = count < 0;
+    if (all ? arc != nullptr : (count > 0 && !arc)) { h->err = "mcf_capacity_ranges: count < 0 goes with a null index list, count > 0 with one"; return MCF_E_BAD_ARG; }
+    for (int64_t i = 0; !all && i < count; ++i)
+        if (arc[i] < 0 || arc[i] >= im.m) { h->err = "mcf_capacity_ranges: arc index outside [0, m)"; return MCF_E_BAD_ARG; }
+    const int64_t entries = all ? im.m : count;
+    mcf_flow_ranges_report rep;
+    frng_empty_report(&rep, im);
+    if (im.m == 0 || im.n <= 1 || entries == 0) {   // nothing to range: an empty answer
+        if (out) *out = rep;
+        return MCF_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = sync_ctx(h, h->stream);
+    if (rc) return rc;
+    FrngArgs a;
+    McfRngDepthAcc D;
+    float ms1 = 0, ms2 = 0;
+    if ((rc = frng_tables(h, &a, &D, &ms1)) != MCF_OK) return rc;
+    const int64_t m = im.m;
+    if (m != h->frng_arcs) {   // (laid out as five rows of m: mcf_add_arcs changes the layout)
+        lazy_release({{&h->d_frng_out, 0}});
+        h->frng_arcs = 0;
+        if ((rc = lazy_alloc(h, "capacity ranges", {{&h->d_frng_out, 5}}, (size_t)m)) != MCF_OK) return rc;
+        h->frng_arcs = m;
+    }
+    if (!all && (rc = lazy_grow(h, "capacity range indices", &h->frng_list, count, {{&h->d_frng_idx, 1}, {&h->d_frng_gout, 5}})) != MCF_OK) return rc;
+    a.count_sides = all ? 1 : 0;
+    a.out = h->d_frng_out;
+    hipStream_t s = h->stream;
+    int ab = mcf_price_blocks(m, 1, 0);
+    if (ab > kFrngMaxBlocks) ab = kFrngMaxBlocks;
+    if (!all) HIP_TRY(h, hipMemcpyAsync(h->d_frng_idx, arc, (size_t)count * 8, hipMemcpyHostToDevice, s));   // (the call ends with a synchronisation)
+    HIP_TRY(h, hipEventRecord(h->ct_ev[0], s));   // (after the upload: device_ms is the passes alone)
+    if ((rc = frng_build(h, a)) != MCF_OK) return rc;
+    hipLaunchKernelGGL(k_frng_arcs, dim3(ab), dim3(kFrngThreads), 0, s, h->view, a);
+    if (!all)
+        hipLaunchKernelGGL(k_frng_gather, dim3(uc_blocks_for(count)), dim3(kFrngThreads), 0, s, count, m, (const int64_t*)h->d_frng_idx, (const int64_t*)h->d_frng_out,
+                           h->d_frng_gout, h->d_frng_info);
+    HIP_TRY(h, hipEventRecord(h->ct_ev[1], s));
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long info[FRNG_COUNTERS] = {0, 0, 0, 0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(info, h->d_frng_info, sizeof info, hipMemcpyDeviceToHost, s));
+    const int64_t* src = all ? h->d_frng_out : h->d_frng_gout;
+    int64_t* const dst[5] = {down, up, down_arc, up_arc, rate};
+    for (int r = 0; r < 5; ++r)
+        if (dst[r]) HIP_TRY(h, hipMemcpyAsync(dst[r], src + (size_t)r * entries, (size_t)entries * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, hipEventElapsedTime(&ms2, h->ct_ev[0], h->ct_ev[1]));
+    frng_report(&rep, info, D, a.K, ms1 + ms2);
     if (out) *out = rep;
     return MCF_OK;
 }

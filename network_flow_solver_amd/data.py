@@ -280,6 +280,18 @@ class FlowResult:
 
 
 @dataclass(frozen=True)
+class SupplyRange:
+    """How far one supply shift ``supply[from] += d, supply[to] -= d`` can go on the basis a solver holds
+    (``NetworkSimplex.supply_ranges``)."""
+
+    limit: float | None             # the shift at which a tree flow reaches a bound; None: nothing limits it
+    rate: float                     # objective change per unit shifted; below the limit the basis stays and nothing pivots
+    limit_arc: tuple | None         # (tail, head) of the arc that reaches its bound first; ("artificial", node) for a node's
+                                    # artificial arc; None with no limit
+    creates_artificial_flow: bool   # any d > 0 leaves flow the network cannot carry: the shifted problem is infeasible
+
+
+@dataclass(frozen=True)
 class ProgressInfo:
     """Payload of the progress callback (data.py:325-343)."""
 

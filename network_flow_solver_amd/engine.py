@@ -33,9 +33,9 @@ ABI_SYMBOLS = (
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
     "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_add_arcs",
-    "mcf_cost_ranges", "mcf_small_narrow_ok",
+    "mcf_cost_ranges", "mcf_small_narrow_ok", "mcf_supply_ranges", "mcf_capacity_ranges",
 )
-RANGE_INF = (1 << 63) - 1   # MCF_RANGE_INF: no arc limits this side of a cost range
+RANGE_INF = (1 << 63) - 1   # MCF_RANGE_INF: no arc limits this side of a cost, supply or capacity range
 # mcf_certify: check groups and verdicts (include/mcf.h)
 CERT_BOUNDS, CERT_CONSERVATION, CERT_DUAL, CERT_OBJECTIVES, CERT_BASIS, CERT_PRICING = 1, 2, 4, 8, 16, 32
 CERT_VERDICTS = {0: "not_proven", 1: "optimal", 2: "infeasible"}
@@ -162,6 +162,15 @@ class McfRangesReport(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class McfFlowRangesReport(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "basic_real", "basic_artificial", "at_capacity", "max_depth", "levels", "inf_count", "zero_count", "art_rising_count",
+        "big_m")] + [("device_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 PROGRESS_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double)
 
 _lib = None
@@ -215,6 +224,8 @@ def load_library():
     if hasattr(lib, "mcf_small_narrow_ok"):   # (an A/B library built from an earlier commit lacks it: MCF_HIP_LIB)
         lib.mcf_small_narrow_ok.argtypes = [ctypes.c_int64, ctypes.c_int64, i64p]
         lib.mcf_small_narrow_ok.restype = ctypes.c_int
+    lib.mcf_supply_ranges.argtypes = [vp, ctypes.c_int64, i32p, i32p, i64p, i64p, i64p, i32p, ctypes.POINTER(McfFlowRangesReport)]
+    lib.mcf_capacity_ranges.argtypes = [vp, ctypes.c_int64, i64p, i64p, i64p, i64p, i64p, i64p, ctypes.POINTER(McfFlowRangesReport)]
     lib.mcf_dimacs_scan.argtypes = [ctypes.c_char_p, i64p, i64p, ctypes.c_char_p, ctypes.c_int32]
     lib.mcf_dimacs_load.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, i32p, i32p, i64p, i64p, i64p, i64p,
                                     ctypes.c_char_p, ctypes.c_int32]
@@ -225,7 +236,8 @@ def load_library():
     for name in ("mcf_create", "mcf_solve", "mcf_get_result", "mcf_price_once", "mcf_reset", "mcf_set_basis", "mcf_update_costs", "mcf_enqueue_price",
                  "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing", "mcf_time_copy",
                  "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load",
-                 "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_cost_ranges"):
+                 "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_cost_ranges",
+                 "mcf_supply_ranges", "mcf_capacity_ranges"):
         getattr(lib, name).restype = ctypes.c_int
     if lib.mcf_abi_version() != ABI_VERSION:
         raise EngineUnavailableError("libmcf_hip.so ABI version mismatch")
@@ -611,6 +623,50 @@ class McfEngine:
         self._check(self._lib.mcf_cost_ranges(self._h, count, None if idx is None or count == 0 else _p(idx, ctypes.c_int64),
                                               _p(down, ctypes.c_int64), _p(up, ctypes.c_int64), ctypes.byref(rep)))
         return down[:entries], up[:entries], rep.as_dict()
+
+    def supply_ranges(self, src, dst):
+        """``(limit, limit_arc, rate, art_rising, report)`` for the supply shifts ``supply[src[i]] += d, supply[dst[i]] -= d``
+        (``mcf_supply_ranges``), all pairs at once on the device: ``limit`` = how far ``d`` may go before a tree flow of the
+        resident basis leaves its bounds (``RANGE_INF``: no arc limits it), ``limit_arc`` = the first arc in push order that
+        attains it (``m + v``: the artificial arc of node ``v``; -1: none), ``rate`` = the exact objective change per unit
+        until then, ``art_rising`` = artificial arcs whose flow the shift raises (> 0: infeasible for any ``d > 0``).
+        ``update_rhs`` with ``d < limit`` keeps the basis and pivots nothing.  Read-only.  ``report``: the fields of
+        ``mcf_flow_ranges_report``."""
+        a = np.ascontiguousarray(src, dtype=np.int64).reshape(-1)
+        b = np.ascontiguousarray(dst, dtype=np.int64).reshape(-1)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("src and dst differ in length")
+        for idx in (a, b):   # (before the cast to the ABI's 32 bits, which would wrap an id outside them into a valid one)
+            if idx.size and (idx.min() < 0 or idx.max() >= self.n):
+                raise EngineError(-1, "mcf_supply_ranges: node index outside [0, n)")
+        a, b = a.astype(np.int32), b.astype(np.int32)
+        count = int(a.shape[0])
+        rep = McfFlowRangesReport()
+        limit, arc, rate = (np.zeros(max(count, 1), dtype=np.int64) for _ in range(3))
+        rising = np.zeros(max(count, 1), dtype=np.int32)
+        self._check(self._lib.mcf_supply_ranges(self._h, count, _p(a, ctypes.c_int32) if count else None, _p(b, ctypes.c_int32) if count else None,
+                                                _p(limit, ctypes.c_int64), _p(arc, ctypes.c_int64), _p(rate, ctypes.c_int64),
+                                                _p(rising, ctypes.c_int32), ctypes.byref(rep)))
+        return limit[:count], arc[:count], rate[:count], rising[:count], rep.as_dict()
+
+    def capacity_ranges(self, arcs=None):
+        """``(down, up, down_arc, up_arc, rate, report)``: by how much the capacity of each arc may fall / rise, one arc at a
+        time, before a tree flow of the resident basis leaves its bounds (``mcf_capacity_ranges``), all arcs at once on the
+        device.  ``arcs``: indices in this engine's arc order (duplicates allowed), default all.  ``rate``: objective change
+        per unit of capacity added (the reduced cost of an arc at capacity, else 0); ``down_arc`` / ``up_arc``: the arc that
+        attains the end (``m + v``: the artificial arc of node ``v``; -1: none).  ``RANGE_INF`` = nothing limits that side.
+        Read-only.  ``report``: the fields of ``mcf_flow_ranges_report``."""
+        rep = McfFlowRangesReport()
+        if arcs is None:
+            count, idx = -1, None
+            entries = self.m
+        else:
+            idx = np.ascontiguousarray(arcs, dtype=np.int64).reshape(-1)
+            count = entries = int(idx.shape[0])
+        outs = [np.zeros(max(entries, 1), dtype=np.int64) for _ in range(5)]
+        self._check(self._lib.mcf_capacity_ranges(self._h, count, None if idx is None or count == 0 else _p(idx, ctypes.c_int64),
+                                                  *(_p(o, ctypes.c_int64) for o in outs), ctypes.byref(rep)))
+        return (*(o[:entries] for o in outs), rep.as_dict())
 
     # -- measurement
     def time_pricing(self, reps: int = 20, rule: int | None = None) -> float:

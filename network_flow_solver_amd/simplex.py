@@ -30,7 +30,7 @@ import numpy as np
 
 from . import engine as _engine
 from .data import (ArrayBasis, Basis, FlowResult, LazyDuals, LazyFlows, NetworkProblem, ProgressCallback, ProgressInfo,
-                   SoAProblem, SolverOptions)
+                   SoAProblem, SolverOptions, SupplyRange)
 from .exceptions import InvalidProblemError, SolverConfigurationError, UnboundedProblemError
 from .specializations import analyze_network_structure, entering_rule_options
 
@@ -701,6 +701,105 @@ class NetworkSimplex:
         out = {}
         for k, c, d, u in zip(wanted, cost.tolist(), down.tolist(), up.tolist()):
             out[k] = (None if d == inf else (c - d) / scale, None if u == inf else (c + u) / scale)
+        return out
+
+    def _arc_name(self, index: int):
+        """A caller's arc index of the engine as the caller names it: a key, ``("artificial", node id)``, ``None`` for -1."""
+        f = self.flat
+        if index < 0:
+            return None
+        m = len(f.keys)
+        return f.keys[index] if index < m else ("artificial", f.node_ids[index - m])
+
+    def supply_ranges(self, pairs):
+        """Supply ranging on the basis resident on the device (``mcf_supply_ranges``): for every pair ``(a, b)``, how far the
+        shift ``supply[a] += d, supply[b] -= d`` can go -- this shift alone -- before a tree flow reaches a bound, and what
+        the objective does until then.  ``update_supplies`` with a shift below the limit keeps the basis, and the ``solve()``
+        after it makes no pivot; the objective moves by exactly ``rate * d``.  All pairs are answered at once on the device;
+        nothing is re-solved.  Meaningful after a ``solve()`` that ended "optimal".
+
+        * object-model problems: ``pairs`` = ``(from id, to id)`` tuples; returns a list of ``SupplyRange`` in the caller's
+          flow and cost units.
+        * ``SoAProblem``: ``pairs`` = ``(from indices, to indices)``; returns ``(limit, rate, limit_arc,
+          creates_artificial_flow)`` arrays: exact int64, ``engine.RANGE_INF`` for no limit, ``limit_arc`` an arc index,
+          ``m + v`` for the artificial arc of node ``v``, -1 for none."""
+        f = self.flat
+        n = len(f.node_ids)
+        if f.soa:
+            try:
+                src, dst = pairs
+            except (TypeError, ValueError):
+                raise InvalidProblemError("supply ranges of an SoAProblem take a pair (from indices, to indices) of arrays") from None
+            src, dst = np.asarray(src).reshape(-1), np.asarray(dst).reshape(-1)
+            if src.shape != dst.shape:
+                raise InvalidProblemError("supply ranges: from and to differ in length")
+            for idx in (src, dst):
+                if idx.size and not np.issubdtype(idx.dtype, np.integer):
+                    raise InvalidProblemError("supply ranges: node indices must be integers")
+                if idx.size and (idx.min() < 0 or idx.max() >= n):
+                    raise InvalidProblemError(f"supply ranges: node index outside [0, {n})")
+            limit, arc, rate, rising, _ = self.engine.supply_ranges(src, dst)
+            return limit, rate, arc, rising > 0
+        index = {nid: i for i, nid in enumerate(f.node_ids)}
+        pairs = [tuple(p) for p in pairs]
+        for p in pairs:
+            for nid in p:
+                if nid not in index:
+                    raise InvalidProblemError(f"supply range names node {nid!r} which is not in the problem")
+        src = np.fromiter((index[a] for a, _ in pairs), dtype=np.int32, count=len(pairs))
+        dst = np.fromiter((index[b] for _, b in pairs), dtype=np.int32, count=len(pairs))
+        limit, arc, rate, rising, _ = self.engine.supply_ranges(src, dst)
+        inf = _engine.RANGE_INF
+        return [SupplyRange(None if lim == inf else lim / f.flow_scale, r / f.cost_scale, self._arc_name(a), k > 0)
+                for lim, a, r, k in zip(limit.tolist(), arc.tolist(), rate.tolist(), rising.tolist())]
+
+    def capacity_ranges(self, keys=None):
+        """Capacity ranging on the basis resident on the device (``mcf_capacity_ranges``): for every arc, the interval its
+        capacity may move in -- this arc alone -- without a tree flow leaving its bounds, so that ``update_capacities`` inside
+        it keeps the basis and the ``solve()`` after it makes no pivot.  ``rate`` is the objective change per unit of capacity
+        added: the reduced cost of an arc that sits at its capacity, 0 for every other arc.  All arcs are answered at once on
+        the device.  Meaningful after a ``solve()`` that ended "optimal".
+
+        * object-model problems: ``keys`` = ``(tail, head)`` keys (default: all; of parallel arcs the LAST one, as in
+          ``update_capacities``); returns ``{(tail, head): (lowest_capacity, highest_capacity, rate, limiting_arc_down,
+          limiting_arc_up)}`` in the caller's units, lower bounds included; ``None`` for an unbounded end -- both ends of an
+          uncapacitated arc -- and for no limiting arc.
+        * ``SoAProblem``: ``keys`` = arc indices (default: all, duplicates allowed); returns ``(lowest, highest, rate,
+          limiting_arc_down, limiting_arc_up)`` arrays in the order asked: exact int64, ``engine.RANGE_INF`` for an unbounded
+          highest, -1 for the lowest of an uncapacitated arc and for no limiting arc."""
+        f = self.flat
+        m = len(f.keys)
+        if f.soa:
+            idx = None
+            if keys is not None:
+                idx = np.asarray(keys).reshape(-1)
+                if idx.size and not np.issubdtype(idx.dtype, np.integer):
+                    raise InvalidProblemError("capacity ranges: arc indices must be integers")
+                idx = idx.astype(np.int64)
+                if idx.size and (idx.min() < 0 or idx.max() >= m):
+                    raise InvalidProblemError(f"capacity ranges: arc index outside [0, {m})")
+        else:
+            last: dict[tuple[str, str], int] = {}
+            for i, key in enumerate(f.keys):
+                last[key] = i
+            wanted = list(last) if keys is None else [tuple(k) for k in keys]
+            missing = [k for k in wanted if k not in last]
+            if missing:
+                raise InvalidProblemError(f"capacity range asked for arc {missing[0]} which is not in the problem")
+            idx = np.fromiter((last[k] for k in wanted), dtype=np.int64, count=len(wanted))
+        down, up, down_arc, up_arc, rate, _ = self.engine.capacity_ranges(idx)
+        cap = f.cap if idx is None else f.cap[idx]
+        lower = f.lower if idx is None else f.lower[idx]
+        inf = _engine.RANGE_INF
+        if f.soa:
+            shift = lower.astype(np.int64)
+            lowest = np.where(down == inf, -1, cap - np.where(down == inf, 0, down) + shift)
+            highest = np.where(up == inf, inf, cap + np.where(up == inf, 0, up) + shift)
+            return lowest, highest, rate, down_arc, up_arc
+        out = {}
+        for k, c, lo, d, u, da, ua, r in zip(wanted, cap.tolist(), lower.tolist(), down.tolist(), up.tolist(), down_arc.tolist(), up_arc.tolist(), rate.tolist()):
+            out[k] = (None if d == inf else (c - d) / f.flow_scale + lo, None if u == inf else (c + u) / f.flow_scale + lo,
+                      r / f.cost_scale, self._arc_name(da), self._arc_name(ua))
         return out
 
     def _update_rhs(self, supplies, capacities) -> dict:
