@@ -24,6 +24,8 @@
  *   solving again after supplies / demands / capacities changed: the reference builds a new NetworkSimplex from the edited
  *       problem and passes solve(warm_start_basis=...), which recomputes the tree flows and falls back to the cold start
  *       when one of them leaves its bounds  simplex.py:99-265, 905-1010, 1491-1532 ...  mcf_update_rhs (the resident basis stays or is repaired)
+ *       the same edit re-optimised the way the algorithm wants -- the basis stays dual feasible, so DUAL pivots on the device
+ *       drive the violated tree flows back inside their bounds (the reference has no dual simplex) ...  mcf_update_rhs_dual
  *   adding arcs to a solved problem (examples/incremental_resolving_example.py:222-266, scenario 4): the reference builds a new
  *       NetworkSimplex from the extended problem and warm-starts it  simplex.py:99-265, 1491-1532 ...  mcf_add_arcs (the resident basis stays)
  *   validate_flow / compute_bottleneck_arcs  utils.py:169-312 (conservation, bounds, arcs
@@ -411,6 +413,74 @@ int mcf_update_rhs(mcf_handle* h,
                    int64_t n_sup, const int64_t* node, const int64_t* new_supply,
                    int64_t n_cap, const int64_t* arc,  const int64_t* new_cap,
                    mcf_rhs_report* out /* may be NULL */);
+
+/* mcf_update_rhs with a dual simplex phase on the device in front of path 1.  A supply / capacity edit leaves the resident basis
+ * DUAL feasible (reduced costs depend on neither) while some tree flows leave their bounds; instead of cutting every violated arc
+ * out on the host and driving big-M arcs back out with primal pivots, dual pivots repair the flows on the arrays that are resident.
+ *   before       argument checks, duplicate rule, errors and the device passes up to the census are mcf_update_rhs's own (one
+ *                code path).  The census stores the violating tree flows too (magnitude below 2^60), for the phase to work on.
+ *   the phase    runs where the census finds tree_violations > 0 and nothing below forbids it; otherwise ended = 3 and the call
+ *                IS mcf_update_rhs.
+ *   afterwards   tree flows and census are recomputed by the same passes, and the call continues exactly as mcf_update_rhs
+ *                does after its census -- path 0, 1 or 2 on the basis the phase left.  *out is that second census (upper_moved:
+ *                the first).  Every violation cleared and no wrong-way arc: path 0, an optimal handle is optimal again and the
+ *                next mcf_solve makes 0 pivots.  Otherwise the repair of path 1 picks up what is left: the phase is best effort,
+ *                the call always correct.  mcf_stats.pivots, degenerate, bound_flips and arcs_priced do not move in the phase.
+ *   the rule     exact integers throughout: rc = cost + pi[tail] - pi[head], slack = state * rc (>= 0 on every non-basic arc).
+ *     leaving    candidates: the tree arcs of the nodes 0 .. n-1 (artificial ones included).  violation = -flow when flow < 0,
+ *                flow - cap when the arc is capped and flow > cap.  The LARGEST violation leaves, ties to the lowest node; it
+ *                leaves at the bound it violated (state +1 at 0, -1 at capacity).
+ *     entering   q = the leaving arc's child node, S = the subtree of q (interval test on logical preorder positions, both tree
+ *                layouts).  When the arc carries too much from child to parent (an up arc over capacity, a down arc below 0) S
+ *                must EXPORT: candidates are the non-basic real arcs with cap != 0 at state +1 with tail in S and head outside,
+ *                or at state -1 with head in S and tail outside.  Otherwise S must import: the two classes mirrored.  The
+ *                LEAST slack enters, ties to the lowest caller's index.  No candidate: the edited instance needs artificial
+ *                flow across that cut; the phase stops (ended = 1).
+ *     pivot      the entering arc is pushed in its own direction by delta = the violation along the engine's route (second ->
+ *                join -> first -> arc): the leaving arc lands exactly on its bound; other cycle arcs -- the entering arc
+ *                included -- may leave theirs and are later leaving candidates.  T2 = S re-hangs on the entering arc; the
+ *                potentials of S shift by sigma = -rc when the arc's tail is in S, +rc otherwise, which zeroes the entering
+ *                arc's reduced cost and lowers every candidate's slack by the least one: dual feasibility is kept by construction.
+ *     the end    a closed arc (cap == 0) is no candidate, so nothing keeps its slack from turning negative; its flow is 0 at
+ *                either bound, and when the phase ends every such arc takes the state its reduced cost asks for (state =
+ *                -state, no flow moves).  With that every non-basic arc has slack >= 0 again.
+ *     magnitudes a pivot adds a violation to a flow; the phase stops (ended = 4) before a pivot when a tree flow or the violation
+ *                reaches 2^61 in magnitude, so no sum reaches 2^62.  Flows of 2^60 or more after the first census: reason 5.
+ *   options      max_pivots < 0: 163 * violations_before (twice the largest ratio of dual pivots per violation measured, 81.45).
+ *                enter_walk: 0 = auto (the subtree's adjacency is walked when it has <= 64 nodes, else the arcs are swept),
+ *                -1 = always the sweep, k > 0 = walk when |S| <= k.  Both searches choose the same arc.
+ *   log          four words per dual pivot: leaving arc (caller's index; m + v for the artificial arc of node v), entering arc
+ *                (caller's index), delta, slack.  The first log_cap pivots are kept; log may be NULL with log_cap 0.
+ *   valid        where mcf_update_rhs is valid; the phase itself runs on grid handles (both tree layouts, with or without
+ *                resident reduced costs or key codes, every rule and key_mode).  shard_count > 1: MCF_E_STATE. */
+typedef struct mcf_dual_options {
+    int64_t max_pivots;   /* < 0 = default budget */
+    int32_t enter_walk;   /* entering search: 0 = auto, -1 = always the arc sweep, k > 0 = walk the subtree's adjacency when it has <= k nodes */
+    int32_t reserved;
+} mcf_dual_options;
+
+typedef struct mcf_dual_report {
+    int64_t ended;              /* 0 = no violation left, 1 = a violated arc has no entering arc across its cut, 2 = budget exhausted,
+                                   3 = not attempted (reason), 4 = magnitude limit */
+    int64_t reason;             /* ended == 3: 1 = no violations, 2 = the handle runs as a persistent loop (pricing_mode 2 or 3),
+                                   3 = basis not dual feasible (a real non-basic arc has state * rc < 0 after the edit; an arc at
+                                   capacity whose capacity went to 0 or none can cause it), 4 = an artificial tree arc turned round
+                                   (art_flips > 0), 5 = a tree flow of magnitude 2^60 or more */
+    int64_t dual_pivots;
+    int64_t violations_before;  /* tree_violations of the first census */
+    int64_t violations_after;   /* ... of the census after the phase */
+    int64_t wrong_way_after;
+    int64_t sweeps, walks;      /* pivots whose entering arc came from the arc sweep / the adjacency walk */
+    int64_t log_written;        /* pivots in log */
+    double  device_ms;          /* HIP events round the phase */
+} mcf_dual_report;
+
+int mcf_update_rhs_dual(mcf_handle* h,
+                        int64_t n_sup, const int64_t* node, const int64_t* new_supply,
+                        int64_t n_cap, const int64_t* arc,  const int64_t* new_cap,
+                        const mcf_dual_options* opt /* NULL = defaults */,
+                        int64_t* log, int64_t log_cap,
+                        mcf_rhs_report* out /* may be NULL */, mcf_dual_report* dual_out /* may be NULL */);
 
 /* Add arcs to the resident handle: `count` new arcs tail[i] -> head[i] with cost[i] and cap[i] (mcf_create's conventions;
  * arc_priority[i] as in mcf_options.arc_priority for key_mode 2, NULL = 0).  New arc i gets the caller's index m + i, m the arc

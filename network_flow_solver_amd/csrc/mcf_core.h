@@ -1264,14 +1264,94 @@ MCF_HD void mcf_pivot_scan(const McfView& v, const McfPaths& sp, int32_t small_c
     MCF_PSTAMP(7);
 }
 
+// The basis swap's scalar decisions (simplex.py:1335-1425), shared by the primal decide below and the dual pivot's forced one:
+// q = stem[k] on side `result` leaves, T2 = the subtree of q.  leave_state 0: the state the ratio test implies -- the first
+// side is walked against the flow (an up arc ends empty), the second side with it (an up arc ends full).
+MCF_HD void mcf_pivot_swap(const McfView& v, const McfPaths& pp, const McfCycle& cy, int32_t result, int32_t k, int32_t leave_state) {
+    McfCtx* c = v.ctx;
+    const int32_t s = c->pv_s, first = c->pv_first, second = c->pv_second;
+    const int64_t rc = c->pv_rc;
+    const int32_t n1 = cy.n1, n2 = cy.n2;
+    // --- basis swap (simplex.py:1335-1425): scalar decisions only
+    const McfNode* srec = result == 1 ? pp.rec1 : pp.rec2;
+    const int32_t v_in = result == 1 ? second : first;
+    const McfNode rq = srec[k];
+    const bool tail_in_t2 = (result == 1) == (s > 0);
+    c->pv_k = k;
+    c->pv_vin = v_in;
+    c->pv_leave = rq.pred >> 1;
+    c->pv_leave_state = leave_state ? leave_state : (result == 1 ? ((rq.pred & 1) ? 1 : -1) : ((rq.pred & 1) ? -1 : 1));
+    c->pv_tail_in_t2 = tail_in_t2 ? 1 : 0;
+    c->sigma = tail_in_t2 ? -rc : rc;  // potential shift that zeroes the entering arc's reduced cost
+
+    const int32_t S = rq.size, a0 = (result == 1 ? pp.ppos1 : pp.ppos2)[k];
+    // v_in is the entering arc's end point on the other side: its record and position were read at the start
+    // (selects between loaded fields, not a record loaded through a selected address: a cycle held in registers -- the LDS
+    //  loop's -- must not be forced into private memory)
+    const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth, zu0 = cy.r0u.size, zw0 = cy.r0w.size;
+    const int32_t vin_depth = result == 1 ? dw0 : du0, vin_size = result == 1 ? zw0 : zu0;
+    const int32_t pvin = result == 1 ? cy.p0w : cy.p0u;
+    c->pv_vin_depth = vin_depth;
+    // depth change of the first piece of the re-rooted subtree (u_in and what hangs below it): with k == 0 that piece is all
+    // of T2 and the segment table is {t2_new, t2_old, S, this} -- the apply pass then needs no look-up in it (mcf_apply_source)
+    c->pv_dd0 = vin_depth + 1 - (result == 1 ? du0 : dw0);
+    // insertion point in OLD coordinates: directly behind v_in, or at the end of
+    // v_in's block -- whichever moves fewer array elements
+    const int32_t tA = pvin + 1, tB = pvin + vin_size;
+    const int32_t costA = tA <= a0 ? a0 - tA : tA - (a0 + S);
+    const int32_t costB = tB <= a0 ? a0 - tB : tB - (a0 + S);
+    const int32_t t = costA <= costB ? tA : tB;
+    const int32_t b = t <= a0 ? t : t - S;
+    c->t2_old = a0;
+    c->t2_new = b;
+    c->t2_size = S;
+    c->lo = t < a0 ? t : a0;
+    c->hi = t > a0 + S ? t : a0 + S;
+    c->nseg = 2 * k + 1;
+    c->nchg = (result == 1 ? n1 : n2) - k - 1;  // the old ancestors of q below the join: their subtrees shrink
+    c->apply = 1;
+    c->pending_flip = 1;
+    c->subtree_nodes += S;
+    c->stage = 2;
+    if (S == 1) {   // T2 = {u_in}: first (stem on the first side) or second (the adjacency range only rides along with resident reduced costs)
+        c->pv_t2n = 1;
+        c->pv_t2node = result == 1 ? first : second;
+        if (result != 1) { c->pv_adj[0] = c->pv_adj[2]; c->pv_adj[1] = c->pv_adj[3]; }
+    }
+    if (MCF_HAS_BPL(v)) {
+        // blocked list: T2 goes into fresh blocks (dense-packed), in front of them two blocks for what has to be cut off
+        // existing blocks; nothing else moves.  The pool is a bump allocator: when it runs out, this pivot's update writes
+        // the WHOLE list densely into the other arena instead (every position is then rewritten once).
+        c->t_ins = t;
+        c->nchg = 0;   // (shrunken subtrees are flagged in bext[], not listed)
+        c->t2_blk = (result == 1 ? pp.slot1 : pp.slot2)[k] >> v.blk_shift;
+        // inserted directly behind v_in: the cut, if any, is in v_in's block; at the end of v_in's subtree: wherever that is
+        c->ins_blk = t == tA ? ((result == 1 ? cy.s0w : cy.s0u) >> v.blk_shift) : -1;
+        const int32_t need = MCF_BLK_COPIES + ((S + (1 << v.blk_shift) - 1) >> v.blk_shift);
+        c->alloc_prev = c->alloc_next;
+        if (c->alloc_next + need > v.blk_cap) {
+            c->rebuild = 1;
+            c->rebuilds += 1;
+            c->alloc_lo = 0;
+            c->alloc_next = c->dense_blocks;
+            c->nodes_moved += v.n_nodes;
+        } else {
+            c->rebuild = 0;
+            c->alloc_lo = c->alloc_next;
+            c->alloc_next += need;
+            c->nodes_moved += S;   // (+ the cut-off runs, counted by the update pass)
+        }
+    } else {
+        c->nodes_moved += c->hi - c->lo;
+    }
+}
+
 // Step 3 (one lane): ratio-test decision + everything the finish / apply passes need to know.
 MCF_HD void mcf_pivot_decide(const McfView& v, const McfPaths& pp, const McfCycle& cy) {
     McfCtx* c = v.ctx;
-    const int32_t e = c->pv_e, s = c->pv_s, first = c->pv_first, second = c->pv_second;
-    const int64_t rc = c->pv_rc;
+    const int32_t e = c->pv_e, s = c->pv_s;
     const int64_t d1 = cy.d1, d2 = cy.d2;
     const int32_t k1 = cy.k1, k2 = cy.k2, n1 = cy.n1, n2 = cy.n2;
-    const McfNode ru = cy.ru;  // joined: ru == rw == the join's record
     const int64_t de = c->pv_cap;  // residual of the entering arc in its push direction (a non-basic arc sits at a bound)
     int32_t result;
     int64_t delta;
@@ -1338,81 +1418,112 @@ MCF_HD void mcf_pivot_decide(const McfView& v, const McfPaths& pp, const McfCycl
         return;
     }
 
-    // --- basis swap (simplex.py:1335-1425): scalar decisions only
-    const int32_t k = result == 1 ? k1 : k2;                 // stem[0] = u_in ... stem[k] = q
-    const McfNode* srec = result == 1 ? pp.rec1 : pp.rec2;
-    const int32_t v_in = result == 1 ? second : first;
-    const McfNode rq = srec[k];
-    const bool tail_in_t2 = (result == 1) == (s > 0);
-    c->pv_k = k;
-    c->pv_vin = v_in;
-    c->pv_leave = rq.pred >> 1;
-    // state the leaving arc takes: the first side is walked against the flow (an up arc ends empty),
-    // the second side with it (an up arc ends full)
-    c->pv_leave_state = result == 1 ? ((rq.pred & 1) ? 1 : -1) : ((rq.pred & 1) ? -1 : 1);
-    c->pv_tail_in_t2 = tail_in_t2 ? 1 : 0;
-    c->sigma = tail_in_t2 ? -rc : rc;  // potential shift that zeroes the entering arc's reduced cost
+    mcf_pivot_swap(v, pp, cy, result, result == 1 ? k1 : k2, 0);
+}
 
-    const int32_t S = rq.size, a0 = (result == 1 ? pp.ppos1 : pp.ppos2)[k];
-    // v_in is the entering arc's end point on the other side: its record and position were read at the start
-    // (selects between loaded fields, not a record loaded through a selected address: a cycle held in registers -- the LDS
-    //  loop's -- must not be forced into private memory)
-    const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth, zu0 = cy.r0u.size, zw0 = cy.r0w.size;
-    const int32_t vin_depth = result == 1 ? dw0 : du0, vin_size = result == 1 ? zw0 : zu0;
-    const int32_t pvin = result == 1 ? cy.p0w : cy.p0u;
-    c->pv_vin_depth = vin_depth;
-    // depth change of the first piece of the re-rooted subtree (u_in and what hangs below it): with k == 0 that piece is all
-    // of T2 and the segment table is {t2_new, t2_old, S, this} -- the apply pass then needs no look-up in it (mcf_apply_source)
-    c->pv_dd0 = vin_depth + 1 - (result == 1 ? du0 : dw0);
-    // insertion point in OLD coordinates: directly behind v_in, or at the end of
-    // v_in's block -- whichever moves fewer array elements
-    const int32_t tA = pvin + 1, tB = pvin + vin_size;
-    const int32_t costA = tA <= a0 ? a0 - tA : tA - (a0 + S);
-    const int32_t costB = tB <= a0 ? a0 - tB : tB - (a0 + S);
-    const int32_t t = costA <= costB ? tA : tB;
-    const int32_t b = t <= a0 ? t : t - S;
-    c->t2_old = a0;
-    c->t2_new = b;
-    c->t2_size = S;
-    c->lo = t < a0 ? t : a0;
-    c->hi = t > a0 + S ? t : a0 + S;
-    c->nseg = 2 * k + 1;
-    c->nchg = (result == 1 ? n1 : n2) - k - 1;  // the old ancestors of q below the join: their subtrees shrink
-    c->apply = 1;
-    c->pending_flip = 1;
-    c->subtree_nodes += S;
-    c->stage = 2;
-    if (S == 1) {   // T2 = {u_in}: first (stem on the first side) or second (the adjacency range only rides along with resident reduced costs)
-        c->pv_t2n = 1;
-        c->pv_t2node = result == 1 ? first : second;
-        if (result != 1) { c->pv_adj[0] = c->pv_adj[2]; c->pv_adj[1] = c->pv_adj[3]; }
+// ---------------------------------------------------------------------------
+// Dual pivots (mcf_update_rhs_dual; the rule is written out in include/mcf.h).  A supply / capacity edit leaves the basis
+// dual feasible -- slack = state * rc >= 0 on every non-basic arc -- while some tree flows leave their bounds.  One dual
+// pivot: the tree arc with the largest violation leaves at the bound it violated; of the non-basic arcs that cross the cut
+// of its subtree S in the direction that relieves it, the one with the least slack enters and is pushed by the violation.
+// The swap itself is the primal one (mcf_pivot_swap, mcf_pivot_finish, the update passes): only the two choices differ.
+// ---------------------------------------------------------------------------
+#define MCF_DUAL_FLOW_LIMIT ((int64_t)1 << 61)   // a pivot adds a violation to a flow: both below this, the sum stays below 2^62
+
+// how far a tree flow is outside [0, cap]; 0: inside
+MCF_HD int64_t mcf_dual_violation(int64_t cap, int64_t flow) {
+    if (flow < 0) return -flow;
+    return (cap < MCF_INF && flow > cap) ? flow - cap : 0;
+}
+// the state the leaving arc takes: +1 at 0, -1 at capacity
+MCF_HD int32_t mcf_dual_leave_state(int64_t flow) { return flow < 0 ? 1 : -1; }
+// does the subtree below the violated arc have to EXPORT flow?  It does when the arc carries too much from child to parent:
+// an up arc over capacity, or a down arc below 0.
+MCF_HD bool mcf_dual_exports(bool up, int64_t flow) { return up == (flow >= 0); }
+// is a non-basic arc a candidate?  tail_in / head_in: its end points lie in S
+MCF_HD bool mcf_dual_candidate(int32_t state, int64_t cap, bool tail_in, bool head_in, bool exports) {
+    if (state == 0 || cap == 0 || tail_in == head_in) return false;
+    // pushed in its own direction the arc carries flow from `first` to `second` (tail -> head at state +1)
+    const bool first_in = state > 0 ? tail_in : head_in;
+    return first_in == exports;
+}
+// A closed arc (cap == 0) is no candidate, so nothing keeps its slack from turning negative; its flow is 0 at either bound, and
+// when the phase ends it takes the state its reduced cost asks for.  Returns the state to store.
+MCF_HD int32_t mcf_dual_closed_state(int32_t state, int64_t cap, int64_t rc) {
+    return (state != 0 && cap == 0 && (int64_t)state * rc < 0) ? -state : state;
+}
+// membership in S by the interval test on logical preorder positions
+MCF_HD bool mcf_dual_in_subtree(int32_t pos, int32_t pos_q, int32_t size_q) { return pos >= pos_q && pos < pos_q + size_q; }
+
+// arg-max of the violations (ties: lowest node) and the largest |flow| on a tree arc (the magnitude check)
+struct McfDualLeave { int64_t viol; int64_t node; int64_t maxabs; };
+MCF_HD void mcf_acc_init(McfDualLeave* a) { a->viol = 0; a->node = -1; a->maxabs = 0; }
+MCF_HD void mcf_dual_leave_add(McfDualLeave* a, int64_t viol, int64_t node, int64_t flow) {
+    if (viol > 0 && (viol > a->viol || (viol == a->viol && (a->node < 0 || node < a->node)))) { a->viol = viol; a->node = node; }
+    const int64_t mag = flow < 0 ? -flow : flow;
+    if (mag > a->maxabs) a->maxabs = mag;
+}
+MCF_HD void mcf_acc_merge(McfDualLeave* a, const McfDualLeave& b) {
+    if (b.node >= 0) mcf_dual_leave_add(a, b.viol, b.node, 0);
+    if (b.maxabs > a->maxabs) a->maxabs = b.maxabs;
+}
+// the magnitude limit: no pivot once a tree flow or the violation has reached 2^61 (flow + delta then stays below 2^62)
+MCF_HD bool mcf_dual_too_large(const McfDualLeave& l) { return l.maxabs >= MCF_DUAL_FLOW_LIMIT || l.viol >= MCF_DUAL_FLOW_LIMIT; }
+// arg-min of the slacks (ties: lowest caller's index -- the high word of the packed id); arc < 0: none
+struct McfDualEnter { int64_t slack; int64_t arc; };
+MCF_HD void mcf_acc_init(McfDualEnter* a) { a->slack = 0; a->arc = -1; }
+MCF_HD void mcf_dual_enter_add(McfDualEnter* a, int64_t slack, int64_t packed_arc) {
+    if (a->arc < 0 || slack < a->slack || (slack == a->slack && packed_arc < a->arc)) { a->slack = slack; a->arc = packed_arc; }
+}
+MCF_HD void mcf_acc_merge(McfDualEnter* a, const McfDualEnter& b) { if (b.arc >= 0) mcf_dual_enter_add(a, b.slack, b.arc); }
+
+// The dual pivot's begin: the pending flip of the double buffers exactly as mcf_pivot_begin_t performs it, then the entering
+// arc's data and *cy as mcf_cycle_init would leave it.  No key test, no rule bookkeeping.
+MCF_HD void mcf_pivot_begin_dual(const McfView& v, int64_t packed_arc, McfCycle* cy) {
+    McfCtx* c = v.ctx;
+    c->apply = 0;
+    c->stage = 0;
+    c->nchg = 0;
+    if (c->wreset) { c->wreset = 0; c->wlist_n = 0; }
+    if (c->pending_flip) {
+        c->cur ^= 1;
+        c->prev_lo = c->lo;
+        c->prev_hi = c->hi;
+        c->pending_flip = 0;
+        if (c->rebuild) { c->arena ^= 1; c->rebuild = 0; }
     }
-    if (MCF_HAS_BPL(v)) {
-        // blocked list: T2 goes into fresh blocks (dense-packed), in front of them two blocks for what has to be cut off
-        // existing blocks; nothing else moves.  The pool is a bump allocator: when it runs out, this pivot's update writes
-        // the WHOLE list densely into the other arena instead (every position is then rewritten once).
-        c->t_ins = t;
-        c->nchg = 0;   // (shrunken subtrees are flagged in bext[], not listed)
-        c->t2_blk = (result == 1 ? pp.slot1 : pp.slot2)[k] >> v.blk_shift;
-        // inserted directly behind v_in: the cut, if any, is in v_in's block; at the end of v_in's subtree: wherever that is
-        c->ins_blk = t == tA ? ((result == 1 ? cy.s0w : cy.s0u) >> v.blk_shift) : -1;
-        const int32_t need = MCF_BLK_COPIES + ((S + (1 << v.blk_shift) - 1) >> v.blk_shift);
-        c->alloc_prev = c->alloc_next;
-        if (c->alloc_next + need > v.blk_cap) {
-            c->rebuild = 1;
-            c->rebuilds += 1;
-            c->alloc_lo = 0;
-            c->alloc_next = c->dense_blocks;
-            c->nodes_moved += v.n_nodes;
-        } else {
-            c->rebuild = 0;
-            c->alloc_lo = c->alloc_next;
-            c->alloc_next += need;
-            c->nodes_moved += S;   // (+ the cut-off runs, counted by the update pass)
-        }
-    } else {
-        c->nodes_moved += c->hi - c->lo;
+    if (packed_arc < 0) return;   // (the flip alone: nothing enters)
+    const int32_t e = (int32_t)(packed_arc & 0xffffffff);
+    const McfArcW ae = v.arcw[e];
+    const bool resident = v.rcache && !v.rc_partial;
+    const int32_t te = v.tail[e], he = v.head[e];
+    const int32_t s = v.state[e];
+    const int32_t first = s > 0 ? te : he, second = s > 0 ? he : te;
+    const int64_t rc = resident ? v.rcache[e] : (int64_t)v.cost[e] + v.pi[te] - v.pi[he];
+    c->pv_e = e; c->pv_s = s; c->pv_first = first; c->pv_second = second; c->pv_rc = rc;
+    c->pv_cap = ae.cap;
+    c->pv_flow = ae.flow;
+    c->pv_t2n = 0;
+    if (v.rcache && v.adj_off) {
+        c->pv_adj[0] = v.adj_off[first]; c->pv_adj[1] = v.adj_off[first + 1];
+        c->pv_adj[2] = v.adj_off[second]; c->pv_adj[3] = v.adj_off[second + 1];
     }
+    mcf_cycle_init(v, cy);
+}
+
+// The dual pivot's decide: the leaving arc is GIVEN -- the tree arc of node q (depth q_depth), which lies on the cycle because
+// the entering arc crosses the cut of q's subtree.  result = the side that holds q (1 iff `first` is in S), k = q's index on
+// that side's recorded path (index = depth difference, as the scan files its hits), delta and the leaving state as chosen.
+// No ratio test, no unbounded test, no Devex / tuner bookkeeping; c->pivots, degenerate and bound_flips are untouched.
+MCF_HD void mcf_pivot_decide_forced(const McfView& v, const McfPaths& pp, const McfCycle& cy, int32_t q, int32_t q_depth,
+                                    bool first_in_s, int64_t delta, int32_t leave_state) {
+    McfCtx* c = v.ctx;
+    const int32_t result = first_in_s ? 1 : 2;
+    const int32_t k = (first_in_s ? cy.r0u.depth : cy.r0w.depth) - q_depth;
+    const int32_t nside = first_in_s ? cy.n1 : cy.n2;
+    if (k < 0 || k >= nside || (first_in_s ? pp.path1 : pp.path2)[k] != q) { c->status = MCF_INTERNAL_ERROR; return; }
+    c->pv_n1 = cy.n1; c->pv_n2 = cy.n2; c->pv_delta = delta; c->pv_result = result;
+    mcf_pivot_swap(v, pp, cy, result, k, leave_state);
 }
 
 // ---------------------------------------------------------------------------

@@ -2467,6 +2467,13 @@ struct mcf_handle {
     mcf_u128* d_rhs_bal = nullptr;                         // [n_nodes] balance per preorder position, then its prefix sums
     mcf_u128* d_rhs_part = nullptr;                        // per chunk of positions
     unsigned long long* d_rhs_info = nullptr;              // [RHS_COUNTERS]
+    // mcf_update_rhs_dual: partials of the two choices, the phase's status record, the pivot log
+    McfDualLeave* d_dual_leave = nullptr;                  // [kCertMaxBlocks + 1]
+    McfDualEnter* d_dual_enter = nullptr;                  // [kMaxPriceBlocks]
+    DualState* d_dual_state = nullptr;
+    unsigned long long* d_dual_count = nullptr;            // arcs with a negative slack
+    int64_t* d_dual_log = nullptr;                         // four words per pivot
+    int64_t dual_log_cap = 0;                              // pivots the log holds
     // mcf_cost_ranges: everything allocated on first use (events are the certificate's)
     McfRngDepthAcc* d_rng_part = nullptr;                  // [kCertMaxBlocks + 1] per-workgroup partials, then the total
     unsigned long long* d_rng_info = nullptr;              // [RNG_COUNTERS]
@@ -2935,6 +2942,7 @@ void free_all(mcf_handle* h) {
     (void)hipFree(h->d_uc_arc); (void)hipFree(h->d_uc_cost); (void)hipFree(h->d_uc_jump[0]); (void)hipFree(h->d_uc_jump[1]); (void)hipFree(h->d_uc_info);
     (void)hipFree(h->d_ray_part); (void)hipFree(h->d_ray_idx); (void)hipFree(h->d_cut_mark); (void)hipFree(h->d_cut_level); (void)hipFree(h->d_cut_byte); (void)hipFree(h->d_cut_part);
     (void)hipFree(h->d_rhs_idx); (void)hipFree(h->d_rhs_val); (void)hipFree(h->d_rhs_bal); (void)hipFree(h->d_rhs_part); (void)hipFree(h->d_rhs_info);
+    (void)hipFree(h->d_dual_leave); (void)hipFree(h->d_dual_enter); (void)hipFree(h->d_dual_state); (void)hipFree(h->d_dual_count); (void)hipFree(h->d_dual_log);
     (void)hipFree(h->d_rng_part); (void)hipFree(h->d_rng_info); (void)hipFree(h->d_rng_anc); (void)hipFree(h->d_rng_p); (void)hipFree(h->d_rng_n);
     (void)hipFree(h->d_rng_down); (void)hipFree(h->d_rng_up); (void)hipFree(h->d_rng_idx); (void)hipFree(h->d_rng_gdown); (void)hipFree(h->d_rng_gup);
     (void)hipFree(h->d_frng_info); (void)hipFree(h->d_frng_uid); (void)hipFree(h->d_frng_did); (void)hipFree(h->d_frng_out); (void)hipFree(h->d_frng_idx);

@@ -627,7 +627,7 @@ __global__ __launch_bounds__(kCertThreads) void k_cut_nodes(McfView v, const int
 constexpr int kRhsThreads = kPassThreads;
 constexpr int kRhsPer = 8;                             // positions per lane in the scan
 constexpr int kRhsChunk = kRhsThreads * kRhsPer;       // positions per workgroup
-enum { RHS_VIOL = 0, RHS_WRONG = 1, RHS_FLIPS = 2, RHS_MOVED = 3, RHS_COUNTERS = 4 };
+enum { RHS_VIOL = 0, RHS_WRONG = 1, RHS_FLIPS = 2, RHS_MOVED = 3, RHS_HUGE = 4, RHS_COUNTERS = 5 };
 
 __device__ __forceinline__ void rhs_count(unsigned long long* info, int which, int32_t mine) {
     mine = wave_sum(mine);
@@ -715,11 +715,13 @@ __global__ __launch_bounds__(kRhsThreads) void k_rhs_scan_apply(mcf_u128* __rest
     for (int k = 0; k < kRhsPer; ++k) if (base + k < count) bal[base + k] = x[k] + before;
 }
 
+// `keep`: a real tree arc's flow is stored even where it violates a bound, as long as its magnitude stays below 2^60 (the dual
+// phase of mcf_update_rhs_dual pivots on these flows; RHS_HUGE counts the ones that do not fit)
 __global__ __launch_bounds__(kRhsThreads) void k_rhs_flows(McfView v, int32_t cur, const mcf_u128* __restrict__ pre, int64_t bigm, McfJump* __restrict__ jump,
-                                                           unsigned long long* __restrict__ info) {
+                                                           unsigned long long* __restrict__ info, int32_t keep) {
     const int32_t N = v.n_nodes, n = N - 1;
     const int64_t m = v.m;
-    int32_t viol = 0, wrong = 0, flips = 0;
+    int32_t viol = 0, wrong = 0, flips = 0, huge = 0;
     for (int32_t u = blockIdx.x * kRhsThreads + threadIdx.x; u < n; u += gridDim.x * kRhsThreads) {
         const McfNode nd = v.node[u];
         int32_t slot = 0;
@@ -731,12 +733,16 @@ __global__ __launch_bounds__(kRhsThreads) void k_rhs_flows(McfView v, int32_t cu
         if (a < m) {
             const __int128 f = up ? x : -x;
             const int64_t cap = v.arcw[a].cap;
-            if (f < 0 || f > cap || f >= MCF_INF) { ++viol; continue; }
+            if (f < 0 || f > cap || f >= MCF_INF) {
+                ++viol;
+                if (keep) { if (f > -(__int128)MCF_INF && f < (__int128)MCF_INF) v.arcw[a].flow = (int64_t)f; else ++huge; }
+                continue;
+            }
             v.arcw[a].flow = (int64_t)f;
             if ((up && cap < MCF_INF && f == cap) || (!up && f == 0)) ++wrong;
         } else {
             const __int128 ax = x < 0 ? -x : x;
-            if (ax >= MCF_INF) { ++viol; continue; }
+            if (ax >= MCF_INF) { ++viol; ++huge; continue; }
             v.arcw[a].flow = (int64_t)ax;
             const bool nup = x >= 0;
             if (nup != up) {   // the arc turns round: pi[u] = pi[root] -+ big-M, and with it every potential below
@@ -749,6 +755,7 @@ __global__ __launch_bounds__(kRhsThreads) void k_rhs_flows(McfView v, int32_t cu
     rhs_count(info, RHS_VIOL, viol);
     rhs_count(info, RHS_WRONG, wrong);
     rhs_count(info, RHS_FLIPS, flips);
+    if (keep) rhs_count(info, RHS_HUGE, huge);
 }
 
 // ------------------------------------------------------------------ mcf_add_arcs: merge new arcs into a resident handle
@@ -1217,4 +1224,277 @@ __global__ __launch_bounds__(kFrngThreads) void k_frng_gather(int64_t count, int
     }
     rhs_count(info, FRNG_INF, n_inf);
     rhs_count(info, FRNG_ZERO, n_zero);
+}
+
+// ------------------------------------------------------------------ mcf_update_rhs_dual: dual pivots on the resident arrays
+// The rule is in include/mcf.h, the choices and the forced decide in mcf_core.h.  One dual pivot is five launches:
+//   k_dual_leave   one lane per node: node record (16 B) and the tree arc's walk record (16 B); arg-max of the violations
+//                  per workgroup (block_reduce), k_final<McfDualLeave> merges the partials.
+//   k_dual_enter   every lane reads the winner (q, its record, position and flow: five scalar loads), then one of
+//       sweep:     the streaming pass of k_cut_arcs -- tail, head (4 B each), state (1 B) of every arc, and for the
+//                  non-basic ones two gathered positions (4 B dense; 4 + 8 B blocked); an arc across the cut adds its
+//                  capacity (8 B), caller's index (4 B) and reduced cost (8 B resident, else cost + two potentials);
+//       walk:      |S| <= enter_walk: the nodes at the positions of S (dense: order[]; blocked list: the slots of the blocks
+//                  that meet the range) walk their adjacency lists: 8 B per entry, state, and for the non-basic arcs the
+//                  other end's position and the same three words.  Every arc across the cut is met once, from inside.
+//                  Both reduce to one McfDualEnter per workgroup; arg-min and tie rule do not depend on the order.
+//   k_pivot_dual   one workgroup: merges the candidates, begins (the pending flip), finds the cycle with k_pivot's climb /
+//                  scan, decides with the leaving arc given (mcf_pivot_decide_forced) and finishes (mcf_pivot_finish).
+//   launch_apply   unchanged.
+// After the last pivot k_dual_close sweeps the arcs once: a closed arc whose slack turned negative changes its state.
+// Status and counters live in one DualState record; the host reads it once per batch of queued pivots.
+enum { DUAL_RUNNING = 0, DUAL_CLEARED = 1, DUAL_NO_ENTERING = 2, DUAL_BUDGET = 3, DUAL_MAGNITUDE = 4, DUAL_INTERNAL = 5 };
+struct DualState {
+    int64_t status;       // DUAL_*
+    int64_t pivots;       // dual pivots made
+    int64_t max_pivots;   // the budget
+    int64_t sweeps, walks;
+};
+struct DualArgs {
+    const McfCtx* ctx;
+    const McfDualLeave* leave;   // the merged arg-max
+    const struct DualState* st;  // the phase's status record: once it has stopped, the launches still queued do nothing
+    const int64_t* adj_off;      // full adjacency (the handle's, or the certificate's own)
+    const int64_t* adj;
+    int32_t walk_max;            // walk when |S| <= this (0: always sweep)
+};
+
+// the view of the tree a pass between two pivots sees: a flip the last update left pending counted (tree_sel on the host)
+struct DualSel { int32_t cur, arena, nblk; };
+__device__ __forceinline__ DualSel dual_sel(const McfCtx* c) {
+    const int32_t pf = c->pending_flip ? 1 : 0;
+    return DualSel{c->cur ^ pf, c->arena ^ ((pf && c->rebuild) ? 1 : 0), c->alloc_next};
+}
+
+__global__ __launch_bounds__(kPassThreads) void k_dual_leave(McfView v, const DualState* __restrict__ st, McfDualLeave* __restrict__ part) {
+    __shared__ McfDualLeave s_wave[kPassWaves];
+    const int32_t n = st->status == DUAL_RUNNING ? v.n_nodes - 1 : 0;   // (uniform; a stopped phase: empty partials)
+    const int64_t narc = v.m + n;
+    McfDualLeave acc;
+    mcf_acc_init(&acc);
+    for (int32_t u = blockIdx.x * kPassThreads + threadIdx.x; u < n; u += gridDim.x * kPassThreads) {
+        const int32_t pred = v.node[u].pred;
+        if (pred < 0 || (int64_t)(pred >> 1) >= narc) continue;
+        const McfArcW w = v.arcw[pred >> 1];
+        mcf_dual_leave_add(&acc, mcf_dual_violation(w.cap, w.flow), u, w.flow);
+    }
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// slack of a non-basic arc across the cut, into the lane's accumulator
+template <bool NT>
+__device__ __forceinline__ void dual_enter_arc(const McfView& v, McfDualEnter* acc, int64_t e, int32_t t, int32_t hd, int32_t st, bool tail_in, bool head_in,
+                                               bool exports) {
+    const int64_t cap = cert_ld<NT>(reinterpret_cast<const int64_t*>(v.arcw + e));
+    if (!mcf_dual_candidate(st, cap, tail_in, head_in, exports)) return;
+    const int64_t rc = (v.rcache && !v.rc_partial) ? cert_ld<NT>(v.rcache + e) : (int64_t)v.cost[e] + v.pi[t] - v.pi[hd];
+    mcf_dual_enter_add(acc, (int64_t)st * rc, mcf_pack_arc(cert_ld<NT>(v.orig + e), e));
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kPassThreads) void k_dual_enter(McfView v, DualArgs a, McfDualEnter* __restrict__ part) {
+    __shared__ McfDualEnter s_wave[kPassWaves];
+    McfDualEnter acc;
+    mcf_acc_init(&acc);
+    const int32_t n = v.n_nodes - 1;
+    const int64_t q = a.st->status == DUAL_RUNNING ? a.leave->node : (int64_t)-1;   // (a stopped phase: empty partials)
+    if (q >= 0 && q < n) {   // (uniform)
+        const DualSel sel = dual_sel(a.ctx);
+        const McfNode rq = v.node[q];
+        int32_t slot = 0;
+        const int32_t pq = tree_pos(v, sel.cur, (int32_t)q, &slot), zq = rq.size;
+        const int64_t qa = rq.pred >> 1;
+        if (pq >= 1 && zq >= 1 && (int64_t)pq + zq <= v.n_nodes && rq.pred >= 0 && qa < v.m + n) {
+            const bool exports = mcf_dual_exports((rq.pred & 1) != 0, v.arcw[qa].flow);
+            if (zq > a.walk_max) {
+                // ---- sweep: workgroup b on head bucket b % 8
+                const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+                const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+                const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+                for (int64_t e = lo + lb * kPassThreads + threadIdx.x; e < hi; e += nlb * kPassThreads) {
+                    const int32_t st = cert_ld<NT>(v.state + e);
+                    if (st == 0) continue;
+                    const int32_t t = cert_ld<NT>(v.tail + e), hd = cert_ld<NT>(v.head + e);
+                    const bool tin = mcf_dual_in_subtree(tree_pos(v, sel.cur, t, &slot), pq, zq);
+                    const bool hin = mcf_dual_in_subtree(tree_pos(v, sel.cur, hd, &slot), pq, zq);
+                    if (tin != hin) dual_enter_arc<NT>(v, &acc, e, t, hd, st, tin, hin, exports);
+                }
+            } else {
+                // ---- walk: one lane per node of S
+                const int64_t gtid = (int64_t)blockIdx.x * kPassThreads + threadIdx.x, gsize = (int64_t)gridDim.x * kPassThreads;
+                auto node_walk = [&](int32_t u) {
+                    for (int64_t k = a.adj_off[u]; k < a.adj_off[u + 1]; ++k) {
+                        const int64_t w = a.adj[k];
+                        const int64_t e = (w & 0xffffffff) >> 1;
+                        const int32_t other = (int32_t)(w >> 32);
+                        const int32_t st = v.state[e];
+                        if (st == 0 || other < 0 || other >= n) continue;
+                        if (mcf_dual_in_subtree(tree_pos(v, sel.cur, other, &slot), pq, zq)) continue;
+                        const bool is_tail = (w & 1) != 0;
+                        dual_enter_arc<false>(v, &acc, e, is_tail ? u : other, is_tail ? other : u, st, is_tail, !is_tail, exports);
+                    }
+                };
+                if (MCF_HAS_BPL(v)) {
+                    const int32_t bs = v.blk_shift;
+                    const McfBlkMeta* bm = sel.cur ? v.bmeta[1] : v.bmeta[0];
+                    const int32_t* xa = sel.arena ? v.bext[1] : v.bext[0];
+                    const int32_t* tok = sel.arena ? v.order[1] : v.order[0];
+                    const int32_t* psz = sel.arena ? v.psz[1] : v.psz[0];
+                    const int32_t nblk = sel.nblk < v.blk_cap ? sel.nblk : v.blk_cap;
+                    for (int32_t b = blockIdx.x; b < nblk; b += gridDim.x) {   // (uniform per workgroup)
+                        const McfBlkMeta mb = bm[b];
+                        if (mb.base == MCF_BLK_FREE) continue;
+                        const int32_t xe = xa[b];
+                        int32_t o0 = mcf_ext_beg(xe), o1 = mcf_ext_end(xe);
+                        if (pq - mb.base > o0) o0 = pq - mb.base;
+                        if (pq + zq - mb.base < o1) o1 = pq + zq - mb.base;
+                        for (int32_t o = o0 + (int32_t)threadIdx.x; o < o1; o += kPassThreads) {
+                            const int32_t sl = (b << bs) + o;
+                            if (psz[sl] == 0) continue;   // an empty slot
+                            const int32_t u = tok[sl];
+                            int32_t s2 = 0;
+                            if (u < 0 || u >= n || tree_pos(v, sel.cur, u, &s2) != mb.base + o) continue;
+                            node_walk(u);
+                        }
+                    }
+                } else {
+                    const int32_t* ord = sel.cur ? v.order[1] : v.order[0];
+                    for (int64_t i = gtid; i < zq; i += gsize) {
+                        const int32_t u = ord[pq + i];
+                        if (u >= 0 && u < n) node_walk(u);
+                    }
+                }
+            }
+        }
+    }
+    block_reduce(acc, s_wave);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+template <bool BPL>
+__global__ __launch_bounds__(kPivotThreads) void k_pivot_dual(McfView g, DualArgs a, const McfDualEnter* __restrict__ part, int npart, DualState* __restrict__ st,
+                                                              int64_t* __restrict__ log, int64_t log_cap) {
+    __shared__ PivotShared S;
+    __shared__ int32_t s_q, s_qdepth, s_first_in, s_lstate;
+    __shared__ int64_t s_delta;
+    if (threadIdx.x < kCtxWords) reinterpret_cast<int32_t*>(&S.ctx)[threadIdx.x] = reinterpret_cast<const int32_t*>(g.ctx)[threadIdx.x];
+    // the candidates: least slack, ties to the lowest caller's index -- as an arg-max of (2^62 - slack) with k_pivot's reduction
+    int64_t key = 0, arc = -1;
+    for (int i = threadIdx.x; i < npart; i += kPivotThreads) {
+        const McfDualEnter c = part[i];
+        const int64_t kk = c.arc >= 0 ? ((int64_t)1 << 62) - c.slack : 0;
+        if (c.arc >= 0 && mcf_cand_better(kk, c.arc, key, arc)) { key = kk; arc = c.arc; }
+    }
+    block_argmax<kPivotThreads>(key, arc);   // (its barrier also covers the control block)
+    McfView v = g;
+    v.ctx = &S.ctx;
+    v.dirty = nullptr;   // every mark is raised again when the call ends (uc_finish)
+    if (!BPL) { v.bmeta[0] = nullptr; v.bmeta[1] = nullptr; }
+    const McfPaths gp = mcf_view_paths(v);
+    const McfPaths sp = McfPaths{S.path[0], S.path[1], S.rec[0], S.rec[1], S.ppos[0], S.ppos[1], S.flow[0], S.flow[1], S.pslot[0], S.pslot[1]};
+    const int32_t n = v.n_nodes - 1;
+    if (threadIdx.x == 0) {
+        McfCtx* c = v.ctx;
+        int go = 0;
+        int64_t stop = st->status;
+        const McfDualLeave L = *a.leave;
+        const int64_t q = L.node;
+        if (stop == DUAL_RUNNING) {
+            if (q < 0 || q >= n) stop = DUAL_CLEARED;
+            else if (mcf_dual_too_large(L)) stop = DUAL_MAGNITUDE;
+            else if (st->pivots >= st->max_pivots) stop = DUAL_BUDGET;
+            else if (arc < 0 || key <= 0) stop = DUAL_NO_ENTERING;
+        }
+        mcf_pivot_begin_dual(v, stop == DUAL_RUNNING ? arc : (int64_t)-1, &S.cy);   // (the pending flip in every case)
+        if (stop == DUAL_RUNNING) {
+            const McfNode rq = v.node[q];
+            const int64_t qflow = v.arcw[rq.pred >> 1].flow, qcap = v.arcw[rq.pred >> 1].cap;
+            int32_t slot = 0;
+            const int32_t pq = mcf_node_pos(v, c, (int32_t)q, &slot);
+            const bool fin = mcf_dual_in_subtree(mcf_node_pos(v, c, c->pv_first, &slot), pq, rq.size);
+            const bool sin = mcf_dual_in_subtree(mcf_node_pos(v, c, c->pv_second, &slot), pq, rq.size);
+            const int64_t viol = mcf_dual_violation(qcap, qflow);
+            if (fin == sin || viol != L.viol || c->pv_s == 0) stop = DUAL_INTERNAL;   // (the passes disagree: never pivot on that)
+            else {
+                s_q = (int32_t)q; s_qdepth = rq.depth; s_first_in = fin ? 1 : 0; s_lstate = mcf_dual_leave_state(qflow); s_delta = viol;
+                const int32_t deep = S.cy.ru.depth > S.cy.rw.depth ? S.cy.ru.depth : S.cy.rw.depth;
+                const bool gate = v.psz[0] && deep <= c->climb_depth && deep < kSmallPath;
+                bool ok;
+                if (gate) { ok = mcf_pivot_climb(v, sp, &S.cy, INT32_MAX); S.cy.small = 1; }
+                else ok = mcf_pivot_climb(v, gp, &S.cy, mcf_climb_budget(v, S.cy));
+                if (ok) go = S.cy.u == S.cy.w ? 1 : 2;
+                else stop = DUAL_INTERNAL;
+                if (go == 2) mcf_scan_init(&S.acc);
+                // the log entry: leaving arc, entering arc (caller's indices), delta, slack
+                if (ok && st->pivots < log_cap) {
+                    const int64_t la = rq.pred >> 1, at = st->pivots * 4;
+                    log[at] = la < v.m ? (int64_t)v.orig[la] : la;
+                    log[at + 1] = arc >> 32;
+                    log[at + 2] = viol;
+                    log[at + 3] = ((int64_t)1 << 62) - key;
+                }
+            }
+        }
+        if (stop != DUAL_RUNNING) st->status = stop;
+        S.go = go;
+    }
+    __syncthreads();
+    const int go = S.go;
+    if (go == 2) mcf_pivot_scan(v, sp, kSmallPath, &S.cy, &S.acc, S.hits, kHitsLds, threadIdx.x, kPivotThreads);  // barriers inside
+    if (go && threadIdx.x == 0) {
+        if (S.ctx.status == MCF_RUNNING && S.cy.u == S.cy.w) {
+            const bool sm = S.cy.small != 0;
+            const McfPaths pp = McfPaths{sm ? sp.path1 : gp.path1, sm ? sp.path2 : gp.path2, sm ? sp.rec1 : gp.rec1, sm ? sp.rec2 : gp.rec2,
+                                         sm ? sp.ppos1 : gp.ppos1, sm ? sp.ppos2 : gp.ppos2, sm ? sp.flow1 : gp.flow1, sm ? sp.flow2 : gp.flow2,
+                                         sm ? sp.slot1 : gp.slot1, sm ? sp.slot2 : gp.slot2};
+            mcf_pivot_decide_forced(v, pp, S.cy, s_q, s_qdepth, s_first_in != 0, s_delta, s_lstate);
+        }
+        if (S.ctx.stage == 2) {
+            const bool walked = S.ctx.t2_size <= a.walk_max;
+            st->pivots += 1;
+            if (walked) st->walks += 1; else st->sweeps += 1;
+        } else {
+            st->status = DUAL_INTERNAL;   // (status word of the control block says why, where it does)
+        }
+    }
+    __syncthreads();
+    if (go && S.cy.small) mcf_pivot_finish(v, sp, threadIdx.x, kPivotThreads);
+    else mcf_pivot_finish(v, gp, threadIdx.x, kPivotThreads);
+    if (threadIdx.x < kCtxWords) reinterpret_cast<int32_t*>(g.ctx)[threadIdx.x] = reinterpret_cast<const int32_t*>(&S.ctx)[threadIdx.x];
+}
+
+// the end of the phase: closed arcs whose slack turned negative change their state (mcf_dual_closed_state); 1 B + 8 B per
+// non-basic arc in, and the reduced cost of the closed ones
+template <bool NT>
+__global__ __launch_bounds__(kPassThreads) void k_dual_close(McfView v) {
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+    for (int64_t e = lo + lb * kPassThreads + threadIdx.x; e < hi; e += nlb * kPassThreads) {
+        const int32_t st = cert_ld<NT>(v.state + e);
+        if (st == 0 || cert_ld<NT>(reinterpret_cast<const int64_t*>(v.arcw + e)) != 0) continue;
+        const int64_t rc = (v.rcache && !v.rc_partial) ? v.rcache[e] : (int64_t)v.cost[e] + v.pi[v.tail[e]] - v.pi[v.head[e]];
+        const int32_t ns = mcf_dual_closed_state(st, 0, rc);
+        if (ns == st) continue;
+        v.state[e] = (int8_t)ns;
+        if (v.vkey) v.vkey[e] = mcf_vkey(-(int64_t)ns * rc, v.vk_bigm, v.vk_half);
+    }
+}
+
+// real non-basic arcs with a negative slack: more than none and the basis is not dual feasible
+template <bool NT>
+__global__ __launch_bounds__(kPassThreads) void k_dual_census(McfView v, unsigned long long* __restrict__ count) {
+    const int x = blockIdx.x & (MCF_NUM_BUCKETS - 1);
+    const int64_t lb = blockIdx.x >> 3, nlb = gridDim.x >> 3;
+    const int64_t lo = v.bucket_off[x], hi = v.bucket_off[x + 1];
+    int32_t bad = 0;
+    for (int64_t e = lo + lb * kPassThreads + threadIdx.x; e < hi; e += nlb * kPassThreads) {
+        const int32_t st = cert_ld<NT>(v.state + e);
+        if (st == 0) continue;
+        const int64_t rc = (v.rcache && !v.rc_partial) ? cert_ld<NT>(v.rcache + e)
+                                                        : (int64_t)cert_ld<NT>(v.cost + e) + v.pi[cert_ld<NT>(v.tail + e)] - v.pi[cert_ld<NT>(v.head + e)];
+        if ((int64_t)st * rc < 0) ++bad;
+    }
+    rhs_count(count, 0, bad);
 }

@@ -174,6 +174,142 @@ int uc_finish(mcf_handle* h, bool rebuild) {
     return MCF_OK;
 }
 
+// ---- mcf_update_rhs_dual: the dual phase (kernels k_dual_* / k_pivot_dual).  The first census has run with `keep`, the
+// control block on the host is current.  Pivots are queued in batches of kDualBatch; one DualState record comes back per batch.
+constexpr int kDualBatch = 32;
+// enter_walk = 0: walk the adjacency of subtrees up to this many nodes.  A guess, bounded by what was measured at 262 144 /
+// 2 097 152 (profiles/update_rhs_dual_262k_2m.txt): walking up to 4 096 nodes costs 144.7 us per dual pivot against 139.8 us with
+// the sweep alone, walking every subtree 145 us per search against the sweep's 34 us; with the walk up to 64 nodes 5 995 of 223 893
+// pivots walk and the time per pivot is the same (140.3 us); neither search was timed on its own at that size.
+constexpr int kDualWalkAuto = 64;
+// max_pivots < 0: this many pivots per violation of the first census -- twice the largest ratio measured (81.45 dual pivots per
+// violation, supplies edit of the same profile)
+constexpr int64_t kDualBudgetMul = 163;
+constexpr int64_t kDualBudgetMax = (int64_t)1 << 60;   // no budget is larger
+
+int dual_phase(mcf_handle* h, const FullAdj& fa, const mcf_dual_options* dopt, int64_t* log, int64_t log_cap, int64_t violations,
+               mcf_dual_report* drep) {
+    const McfHostImage& im = h->im;
+    hipStream_t s = h->stream;
+    int rc;
+    const int ab = mcf_price_blocks(im.m, 1, 0), nb = node_grid(im.n_nodes);
+    if ((rc = lazy_group(h, "dual pivot partials", {{&h->d_dual_leave, (size_t)kCertMaxBlocks + 1}, {&h->d_dual_enter, (size_t)kMaxPriceBlocks},
+                                                    {&h->d_dual_state, 1}, {&h->d_dual_count, 1}})) != MCF_OK) return rc;
+    // dual feasibility: one census over the arcs
+    const bool nt = im.m >= kIncrementalMinArcs;
+    HIP_TRY(h, hipMemsetAsync(h->d_dual_count, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(nt ? k_dual_census<true> : k_dual_census<false>, dim3(ab), dim3(kPassThreads), 0, s, h->view, h->d_dual_count);
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long bad = 0;
+    HIP_TRY(h, hipMemcpyAsync(&bad, h->d_dual_count, sizeof bad, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    if (bad > 0) { drep->reason = 3; return MCF_OK; }
+
+    int64_t budget = dopt && dopt->max_pivots >= 0 ? dopt->max_pivots : kDualBudgetMul * violations;
+    if (budget > kDualBudgetMax) budget = kDualBudgetMax;   // (the loop below counts past it in steps of kDualBatch)
+    const int32_t ew = dopt ? dopt->enter_walk : 0;
+    const int64_t keep_log = log_cap < budget ? log_cap : budget;
+    if ((rc = lazy_grow(h, "dual pivot log", &h->dual_log_cap, keep_log, {{&h->d_dual_log, 4}})) != MCF_OK) return rc;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIP_TRY(h, hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(ev[0]); h->err = "hipEventCreate"; return MCF_E_HIP; }
+    const McfCtx was = *h->h_ctx;
+    // every way out after this point: the events go, and the host's control block says what it said before
+    auto fail = [&](int code) {
+        (void)hipStreamSynchronize(s); (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); (void)hipGetLastError();
+        h->h_ctx->status = was.status;
+        h->ctx_current = false;
+        return code;
+    };
+
+    // the control block says "running" for the pivot machinery (as every path of the call leaves it in the end)
+    h->h_ctx->status = MCF_RUNNING;
+    DualState st;
+    std::memset(&st, 0, sizeof st);
+    st.max_pivots = budget;
+    if (hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(h->d_dual_state, &st, sizeof st, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipEventRecord(ev[0], s) != hipSuccess) { h->err = "mcf_update_rhs_dual: upload"; return fail(MCF_E_HIP); }
+    h->ctx_current = false;
+    DualArgs a;
+    a.ctx = h->d_ctx;
+    a.leave = h->d_dual_leave + nb;
+    a.st = h->d_dual_state;
+    a.adj_off = fa.off; a.adj = fa.adj;
+    a.walk_max = ew < 0 ? 0 : (ew == 0 ? kDualWalkAuto : ew);
+    // MCF_DUAL_TIMING=1 (diagnostic, like MCF_STAMPS): HIP events round the launches of every pivot, one line on stderr at the
+    // end -- where a dual pivot's time goes.  The pivots are then synchronised one by one.
+    const char* tenv = std::getenv("MCF_DUAL_TIMING");
+    const bool timing = tenv && tenv[0] == '1';
+    hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double tms[4] = {0, 0, 0, 0};
+    int64_t timed = 0;
+    if (timing) for (hipEvent_t& x : tev) if (hipEventCreate(&x) != hipSuccess) { (void)hipGetLastError(); x = nullptr; }
+    const bool tim = timing && tev[4] != nullptr;
+    // every pivot the budget allows plus the one launch that finds nothing left: bounded in code, whatever the device reports
+    for (int64_t queued = 0; queued <= budget; queued += kDualBatch) {
+        for (int i = 0; i < kDualBatch; ++i) {
+            if (tim) (void)hipEventRecord(tev[0], s);
+            hipLaunchKernelGGL(k_dual_leave, dim3(nb), dim3(kPassThreads), 0, s, h->view, (const DualState*)h->d_dual_state, h->d_dual_leave);
+            hipLaunchKernelGGL(k_final<McfDualLeave>, dim3(1), dim3(kPassThreads), 0, s, h->d_dual_leave, nb);
+            if (tim) (void)hipEventRecord(tev[1], s);
+            hipLaunchKernelGGL(nt ? k_dual_enter<true> : k_dual_enter<false>, dim3(ab), dim3(kPassThreads), 0, s, h->view, a, h->d_dual_enter);
+            if (tim) (void)hipEventRecord(tev[2], s);
+            if (h->bpl) hipLaunchKernelGGL(k_pivot_dual<true>, dim3(1), dim3(kPivotThreads), 0, s, h->view, a, (const McfDualEnter*)h->d_dual_enter, ab, h->d_dual_state, h->d_dual_log, keep_log);
+            else hipLaunchKernelGGL(k_pivot_dual<false>, dim3(1), dim3(kPivotThreads), 0, s, h->view, a, (const McfDualEnter*)h->d_dual_enter, ab, h->d_dual_state, h->d_dual_log, keep_log);
+            if (tim) (void)hipEventRecord(tev[3], s);
+            launch_apply(h, s);
+            if (tim) {
+                (void)hipEventRecord(tev[4], s);
+                if (hipEventSynchronize(tev[4]) == hipSuccess) {
+                    for (int k = 0; k < 4; ++k) { float ms1 = 0; if (hipEventElapsedTime(&ms1, tev[k], tev[k + 1]) == hipSuccess) tms[k] += ms1; }
+                    ++timed;
+                }
+                (void)hipGetLastError();
+            }
+        }
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&st, h->d_dual_state, sizeof st, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) { for (hipEvent_t x : tev) if (x) (void)hipEventDestroy(x); h->err = "mcf_update_rhs_dual: pivot batch"; return fail(MCF_E_HIP); }
+        if (st.status != DUAL_RUNNING) break;
+    }
+    for (hipEvent_t x : tev) if (x) (void)hipEventDestroy(x);
+    if (tim && timed > 0)
+        std::fprintf(stderr, "mcf_update_rhs_dual timing: %lld pivot slots (%lld pivots: %lld sweeps, %lld walks), us per slot: leave %.2f, enter %.2f, "
+                     "pivot %.2f, update %.2f\n", (long long)timed, (long long)st.pivots, (long long)st.sweeps, (long long)st.walks,
+                     tms[0] * 1e3 / timed, tms[1] * 1e3 / timed, tms[2] * 1e3 / timed, tms[3] * 1e3 / timed);
+    {   // closed arcs take the state their reduced cost asks for (key codes only where they are kept exact)
+        McfView vw = h->view;
+        if (!h->rcached) vw.vkey = nullptr;
+        hipLaunchKernelGGL(nt ? k_dual_close<true> : k_dual_close<false>, dim3(ab), dim3(kPassThreads), 0, s, vw);
+    }
+    if (hipEventRecord(ev[1], s) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess) { h->err = "mcf_update_rhs_dual: events"; return fail(MCF_E_HIP); }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
+    drep->device_ms = ms;
+    drep->dual_pivots = st.pivots;
+    drep->sweeps = st.sweeps;
+    drep->walks = st.walks;
+    drep->log_written = st.pivots < keep_log ? st.pivots : keep_log;
+    if (drep->log_written > 0 && hipMemcpy(log, h->d_dual_log, (size_t)drep->log_written * 4 * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) {
+        h->err = "mcf_update_rhs_dual: log download"; return fail(MCF_E_HIP);
+    }
+    if ((rc = read_ctx(h, s)) != MCF_OK) return fail(rc);
+    (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
+    if (st.status == DUAL_INTERNAL || h->h_ctx->status == MCF_INTERNAL_ERROR) { h->err = "mcf_update_rhs_dual: the dual pivot passes disagree (internal error)"; return MCF_E_STATE; }
+    // the solver's counters do not move in the phase: its work is in the report
+    McfCtx& c = *h->h_ctx;
+    c.status = was.status;
+    c.pivots = was.pivots; c.degenerate = was.degenerate; c.bound_flips = was.bound_flips; c.arcs_priced = was.arcs_priced;
+    c.nodes_moved = was.nodes_moved; c.subtree_nodes = was.subtree_nodes; c.cycle_arcs = was.cycle_arcs;
+    c.scans = was.scans; c.scan_rounds = was.scan_rounds; c.rebuilds = was.rebuilds;
+    HIP_TRY(h, hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->ctx_current = true;
+    drep->ended = st.status == DUAL_CLEARED ? 0 : st.status == DUAL_NO_ENTERING ? 1 : st.status == DUAL_MAGNITUDE ? 4 : 2;
+    drep->reason = 0;
+    return MCF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -256,9 +392,12 @@ int mcf_update_costs(mcf_handle* h, int64_t count, const int64_t* arc, const int
 // Re-optimise after supplies / capacities changed (kernels k_rhs_* above).  Non-basic flows follow their capacities, tree
 // flows are recomputed as subtree sums of the node balances, and a census decides: the basis stays (path 0), is repaired
 // on the host at mcf_set_basis cost (path 1, mcf_repair_basis), or the handle goes to the cold start (path 2).
-int mcf_update_rhs(mcf_handle* h, int64_t n_sup, const int64_t* node, const int64_t* new_supply, int64_t n_cap,
-                   const int64_t* arc, const int64_t* new_cap, mcf_rhs_report* out) {
+// (mcf_update_rhs_dual is this very call with a dual simplex phase between two runs of the census: `dual`)
+static int rhs_update(mcf_handle* h, int64_t n_sup, const int64_t* node, const int64_t* new_supply, int64_t n_cap,
+                      const int64_t* arc, const int64_t* new_cap, mcf_rhs_report* out, bool dual, const mcf_dual_options* dopt,
+                      int64_t* log, int64_t log_cap, mcf_dual_report* dual_out) {
     if (!h) return MCF_E_BAD_ARG;
+    if (dual && (log_cap < 0 || (log_cap > 0 && !log))) { h->err = "mcf_update_rhs_dual: bad log_cap / null log"; return MCF_E_BAD_ARG; }
     if (h->shards != 1) {
         h->err = "mcf_update_rhs: handle was created with shard_count > 1; sharded handles cannot change their supplies / capacities";
         return MCF_E_STATE;
@@ -323,26 +462,32 @@ int mcf_update_rhs(mcf_handle* h, int64_t n_sup, const int64_t* node, const int6
         HIP_TRY(h, hipMemcpyAsync(h->d_rhs_idx, idx.data(), (size_t)(ns + nc) * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(h->d_rhs_val, val.data(), (size_t)(ns + nc) * 8, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(h, hipMemsetAsync(h->d_rhs_info, 0, RHS_COUNTERS * sizeof(unsigned long long), s));
-    HIP_TRY(h, hipMemsetAsync(h->d_uc_info, 0, 2 * sizeof(int32_t), s));
-    HIP_TRY(h, hipMemsetAsync(h->d_rhs_bal, 0, (size_t)N * sizeof(mcf_u128), s));
-    if (ns + nc > 0)
-        hipLaunchKernelGGL(k_rhs_scatter, dim3(uc_blocks_for(ns > nc ? ns : nc)), dim3(kRhsThreads), 0, s, vw, ns, (const int32_t*)h->d_rhs_idx,
-                           (const int64_t*)h->d_rhs_val, h->d_ct_supply, nc, (const int32_t*)(h->d_rhs_idx + ns), (const int64_t*)(h->d_rhs_val + ns), h->d_rhs_info);
-    hipLaunchKernelGGL(k_rhs_balance, dim3(uc_blocks_for(N)), dim3(kRhsThreads), 0, s, vw, cur, (const int64_t*)h->d_ct_supply,
-                       fa.off, fa.adj, h->d_rhs_bal);
-    hipLaunchKernelGGL(k_rhs_scan_totals, dim3((unsigned)chunks), dim3(kRhsThreads), 0, s, (const mcf_u128*)h->d_rhs_bal, N, h->d_rhs_part);
-    hipLaunchKernelGGL((k_scan_chunks<mcf_u128, mcf_u128>), dim3(1), dim3(1024), 0, s, (const mcf_u128*)h->d_rhs_part, chunks, h->d_rhs_part, (mcf_u128*)nullptr);
-    hipLaunchKernelGGL(k_rhs_scan_apply, dim3((unsigned)chunks), dim3(kRhsThreads), 0, s, h->d_rhs_bal, N, (const mcf_u128*)h->d_rhs_part);
-    // jump records for the potentials below an artificial arc that turns round (seeded with 0; the flow pass marks the turns)
-    hipLaunchKernelGGL(k_uc_seed, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfNode*)h->d_node, N, im.m, (int64_t)0, h->d_uc_jump[0], h->d_uc_info);
-    hipLaunchKernelGGL(k_rhs_flows, dim3(uc_blocks_for(N)), dim3(kRhsThreads), 0, s, vw, cur, (const mcf_u128*)h->d_rhs_bal, im.big_m, h->d_uc_jump[0], h->d_rhs_info);
-    HIP_TRY(h, hipGetLastError());
-    unsigned long long info[RHS_COUNTERS] = {0, 0, 0, 0};
+    unsigned long long info[RHS_COUNTERS] = {0, 0, 0, 0, 0};
     int32_t depth[2] = {0, 0};
-    HIP_TRY(h, hipMemcpyAsync(info, h->d_rhs_info, sizeof info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(depth, h->d_uc_info, sizeof depth, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));   // (also: the pageable sources above are free again)
+    // the passes up to the census (`scatter`: with the edit itself; `cur`: the copy of the preorder arrays that is current;
+    // `keep`: violating tree flows are stored too), and its figures on the host
+    auto census = [&](bool scatter, int32_t cur, int32_t keep) -> int {
+        HIP_TRY(h, hipMemsetAsync(h->d_rhs_info, 0, RHS_COUNTERS * sizeof(unsigned long long), s));
+        HIP_TRY(h, hipMemsetAsync(h->d_uc_info, 0, 2 * sizeof(int32_t), s));
+        HIP_TRY(h, hipMemsetAsync(h->d_rhs_bal, 0, (size_t)N * sizeof(mcf_u128), s));
+        if (scatter && ns + nc > 0)
+            hipLaunchKernelGGL(k_rhs_scatter, dim3(uc_blocks_for(ns > nc ? ns : nc)), dim3(kRhsThreads), 0, s, vw, ns, (const int32_t*)h->d_rhs_idx,
+                               (const int64_t*)h->d_rhs_val, h->d_ct_supply, nc, (const int32_t*)(h->d_rhs_idx + ns), (const int64_t*)(h->d_rhs_val + ns), h->d_rhs_info);
+        hipLaunchKernelGGL(k_rhs_balance, dim3(uc_blocks_for(N)), dim3(kRhsThreads), 0, s, vw, cur, (const int64_t*)h->d_ct_supply,
+                           fa.off, fa.adj, h->d_rhs_bal);
+        hipLaunchKernelGGL(k_rhs_scan_totals, dim3((unsigned)chunks), dim3(kRhsThreads), 0, s, (const mcf_u128*)h->d_rhs_bal, N, h->d_rhs_part);
+        hipLaunchKernelGGL((k_scan_chunks<mcf_u128, mcf_u128>), dim3(1), dim3(1024), 0, s, (const mcf_u128*)h->d_rhs_part, chunks, h->d_rhs_part, (mcf_u128*)nullptr);
+        hipLaunchKernelGGL(k_rhs_scan_apply, dim3((unsigned)chunks), dim3(kRhsThreads), 0, s, h->d_rhs_bal, N, (const mcf_u128*)h->d_rhs_part);
+        // jump records for the potentials below an artificial arc that turns round (seeded with 0; the flow pass marks the turns)
+        hipLaunchKernelGGL(k_uc_seed, dim3(uc_blocks_for(N)), dim3(kUcThreads), 0, s, (const McfNode*)h->d_node, N, im.m, (int64_t)0, h->d_uc_jump[0], h->d_uc_info);
+        hipLaunchKernelGGL(k_rhs_flows, dim3(uc_blocks_for(N)), dim3(kRhsThreads), 0, s, vw, cur, (const mcf_u128*)h->d_rhs_bal, im.big_m, h->d_uc_jump[0], h->d_rhs_info, keep);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(info, h->d_rhs_info, sizeof info, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(depth, h->d_uc_info, sizeof depth, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));   // (also: the pageable sources above are free again)
+        return MCF_OK;
+    };
+    if ((rc = census(true, cur, dual ? 1 : 0)) != MCF_OK) return rc;
 
     // host image: the objective, a later mcf_reset / mcf_set_basis and the repair below use the new data
     for (int64_t i = 0; i < ns; ++i) im.supply[(size_t)idx[(size_t)i]] = val[(size_t)i];
@@ -354,6 +499,31 @@ int mcf_update_rhs(mcf_handle* h, int64_t n_sup, const int64_t* node, const int6
     rep.wrong_way = (int64_t)info[RHS_WRONG];
     rep.art_flips = (int64_t)info[RHS_FLIPS];
     rep.upper_moved = (int64_t)info[RHS_MOVED];
+    if (dual) {
+        mcf_dual_report drep;
+        std::memset(&drep, 0, sizeof drep);
+        drep.violations_before = drep.violations_after = rep.tree_violations;
+        drep.wrong_way_after = rep.wrong_way;
+        drep.ended = 3;
+        if (rep.tree_violations == 0) drep.reason = 1;
+        else if (h->small || h->mid) drep.reason = 2;
+        else if (rep.art_flips > 0) drep.reason = 4;
+        else if (info[RHS_HUGE] > 0) drep.reason = 5;
+        else if ((rc = dual_phase(h, fa, dopt, log, log_cap, rep.tree_violations, &drep)) != MCF_OK) return rc;
+        if (drep.ended != 3) {
+            // the phase ran: tree flows and census once more, on the basis it left
+            const int64_t moved = rep.upper_moved;
+            if ((rc = census(false, tree_sel(*h->h_ctx).cur, 0)) != MCF_OK) return rc;
+            std::memset(&rep, 0, sizeof rep);
+            rep.tree_violations = (int64_t)info[RHS_VIOL];
+            rep.wrong_way = (int64_t)info[RHS_WRONG];
+            rep.art_flips = (int64_t)info[RHS_FLIPS];
+            rep.upper_moved = moved;
+            drep.violations_after = rep.tree_violations;
+            drep.wrong_way_after = rep.wrong_way;
+        }
+        if (dual_out) *dual_out = drep;
+    }
     if (rep.tree_violations == 0 && rep.wrong_way == 0) {
         // ---- path 0: the basis stays
         if (rep.art_flips > 0) uc_jump_rounds(h, depth[0]);
@@ -405,6 +575,17 @@ int mcf_update_rhs(mcf_handle* h, int64_t n_sup, const int64_t* node, const int6
     rep.device_ms = ms;
     if (out) *out = rep;
     return MCF_OK;
+}
+
+int mcf_update_rhs(mcf_handle* h, int64_t n_sup, const int64_t* node, const int64_t* new_supply, int64_t n_cap,
+                   const int64_t* arc, const int64_t* new_cap, mcf_rhs_report* out) {
+    return rhs_update(h, n_sup, node, new_supply, n_cap, arc, new_cap, out, false, nullptr, nullptr, 0, nullptr);
+}
+
+int mcf_update_rhs_dual(mcf_handle* h, int64_t n_sup, const int64_t* node, const int64_t* new_supply, int64_t n_cap,
+                        const int64_t* arc, const int64_t* new_cap, const mcf_dual_options* opt, int64_t* log, int64_t log_cap,
+                        mcf_rhs_report* out, mcf_dual_report* dual_out) {
+    return rhs_update(h, n_sup, node, new_supply, n_cap, arc, new_cap, out, true, opt, log, log_cap, dual_out);
 }
 
 // Add arcs to the resident handle (kernels k_aa_* above).  The new arcs are sorted on the host and uploaded with their keys

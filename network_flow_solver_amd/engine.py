@@ -33,7 +33,7 @@ ABI_SYMBOLS = (
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
     "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_add_arcs",
-    "mcf_cost_ranges", "mcf_small_narrow_ok", "mcf_supply_ranges", "mcf_capacity_ranges",
+    "mcf_cost_ranges", "mcf_small_narrow_ok", "mcf_supply_ranges", "mcf_capacity_ranges", "mcf_update_rhs_dual",
 )
 RANGE_INF = (1 << 63) - 1   # MCF_RANGE_INF: no arc limits this side of a cost, supply or capacity range
 # mcf_certify: check groups and verdicts (include/mcf.h)
@@ -113,6 +113,19 @@ class McfCertificate(ctypes.Structure):
 class McfRhsReport(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int64) for name in (
         "path", "tree_violations", "wrong_way", "arcs_cut", "repair_rounds", "art_flips", "upper_moved")] + [("device_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class McfDualOptions(ctypes.Structure):
+    _fields_ = [("max_pivots", ctypes.c_int64), ("enter_walk", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class McfDualReport(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "ended", "reason", "dual_pivots", "violations_before", "violations_after", "wrong_way_after", "sweeps", "walks",
+        "log_written")] + [("device_ms", ctypes.c_double)]
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -203,6 +216,10 @@ def load_library():
     lib.mcf_update_costs.argtypes = [vp, ctypes.c_int64, i64p, i64p]
     lib.mcf_update_rhs.argtypes = [vp, ctypes.c_int64, i64p, i64p, ctypes.c_int64, i64p, i64p, ctypes.POINTER(McfRhsReport)]
     lib.mcf_add_arcs.argtypes = [vp, ctypes.c_int64, i32p, i32p, i64p, i64p, i8p, ctypes.POINTER(McfArcsReport)]
+    if hasattr(lib, "mcf_update_rhs_dual"):   # (an A/B library built from an earlier commit lacks it: MCF_HIP_LIB)
+        lib.mcf_update_rhs_dual.argtypes = [vp, ctypes.c_int64, i64p, i64p, ctypes.c_int64, i64p, i64p, ctypes.POINTER(McfDualOptions),
+                                            i64p, ctypes.c_int64, ctypes.POINTER(McfRhsReport), ctypes.POINTER(McfDualReport)]
+        lib.mcf_update_rhs_dual.restype = ctypes.c_int
     lib.mcf_enqueue_price.argtypes = [vp, vp, vp]
     lib.mcf_enqueue_pivot.argtypes = [vp, vp, vp, ctypes.c_int32]
     lib.mcf_shard_info.argtypes = [vp, i32p, i32p]
@@ -444,27 +461,55 @@ class McfEngine:
                 self._cost_private = True
             self.cost[a] = c               # (numpy assigns in order: the last entry wins here too)
 
-    def update_rhs(self, nodes=(), supplies=(), arcs=(), caps=()) -> dict:
-        """New integer supplies for the nodes ``nodes`` and new capacities (negative: uncapacitated) for the arcs ``arcs``
-        (this engine's orders; of duplicates the last entry wins), in one call.  The device-resident basis stays where its
-        tree flows, recomputed on the device, respect the new data; otherwise it is repaired (``mcf_update_rhs``).  Returns
-        the fields of ``mcf_rhs_report``: ``path`` 0 = basis kept, 1 = repaired, 2 = cold start."""
+    @staticmethod
+    def _rhs_args(nodes, supplies, arcs, caps):
         nd = np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)
         sv = np.ascontiguousarray(supplies, dtype=np.int64).reshape(-1)
         ar = np.ascontiguousarray(arcs, dtype=np.int64).reshape(-1)
         cv = np.ascontiguousarray(caps, dtype=np.int64).reshape(-1)
         if nd.shape[0] != sv.shape[0] or ar.shape[0] != cv.shape[0]:
             raise ValueError("indices and values differ in length")
-        rep = McfRhsReport()
-        self._check(self._lib.mcf_update_rhs(self._h, int(nd.shape[0]), _p(nd, ctypes.c_int64), _p(sv, ctypes.c_int64),
-                                             int(ar.shape[0]), _p(ar, ctypes.c_int64), _p(cv, ctypes.c_int64), ctypes.byref(rep)))
+        return nd, sv, ar, cv
+
+    def _rhs_applied(self, nd, sv, ar, cv):
+        """This object's copies of the supplies / capacities follow an edit the library accepted."""
         if nd.shape[0] or ar.shape[0]:
             if not self._rhs_private:      # the arrays may be the caller's own: copied once, on the first change
                 self.supply, self.cap = self.supply.copy(), self.cap.copy()
                 self._rhs_private = True
             self.supply[nd] = sv           # (numpy assigns in order: the last entry wins here too)
             self.cap[ar] = cv
+
+    def update_rhs(self, nodes=(), supplies=(), arcs=(), caps=()) -> dict:
+        """New integer supplies for the nodes ``nodes`` and new capacities (negative: uncapacitated) for the arcs ``arcs``
+        (this engine's orders; of duplicates the last entry wins), in one call.  The device-resident basis stays where its
+        tree flows, recomputed on the device, respect the new data; otherwise it is repaired (``mcf_update_rhs``).  Returns
+        the fields of ``mcf_rhs_report``: ``path`` 0 = basis kept, 1 = repaired, 2 = cold start."""
+        nd, sv, ar, cv = self._rhs_args(nodes, supplies, arcs, caps)
+        rep = McfRhsReport()
+        self._check(self._lib.mcf_update_rhs(self._h, int(nd.shape[0]), _p(nd, ctypes.c_int64), _p(sv, ctypes.c_int64),
+                                             int(ar.shape[0]), _p(ar, ctypes.c_int64), _p(cv, ctypes.c_int64), ctypes.byref(rep)))
+        self._rhs_applied(nd, sv, ar, cv)
         return rep.as_dict()
+
+    def update_rhs_dual(self, nodes=(), supplies=(), arcs=(), caps=(), max_pivots: int = -1, enter_walk: int = 0, log_cap: int = 0):
+        """``update_rhs`` with dual simplex pivots on the device before the repair (``mcf_update_rhs_dual``): where the edit
+        leaves tree flows outside their bounds, dual pivots drive them back in on the resident arrays.  Returns
+        ``(rhs_report, dual_report, log)``: the fields of ``mcf_rhs_report`` after the phase, those of ``mcf_dual_report``, and
+        an int64 array of shape (pivots kept, 4): leaving arc, entering arc, delta, slack per dual pivot."""
+        if not hasattr(self._lib, "mcf_update_rhs_dual"):
+            raise EngineUnavailableError(f"{LIB_PATH} does not export mcf_update_rhs_dual (a library built from an earlier commit)")
+        nd, sv, ar, cv = self._rhs_args(nodes, supplies, arcs, caps)
+        if log_cap < 0:
+            raise ValueError("log_cap must not be negative")
+        rep, drep = McfRhsReport(), McfDualReport()
+        opt = McfDualOptions(int(max_pivots), int(enter_walk), 0)
+        log = np.zeros((int(log_cap), 4), dtype=np.int64)
+        self._check(self._lib.mcf_update_rhs_dual(self._h, int(nd.shape[0]), _p(nd, ctypes.c_int64), _p(sv, ctypes.c_int64),
+                                                  int(ar.shape[0]), _p(ar, ctypes.c_int64), _p(cv, ctypes.c_int64), ctypes.byref(opt),
+                                                  _p(log, ctypes.c_int64) if log_cap else None, int(log_cap), ctypes.byref(rep), ctypes.byref(drep)))
+        self._rhs_applied(nd, sv, ar, cv)
+        return rep.as_dict(), drep.as_dict(), log[:int(drep.log_written)].copy()
 
     def add_arcs(self, tail, head, cost, cap, priority=None) -> dict:
         """Add the arcs ``tail[i] -> head[i]`` with integer ``cost[i]`` and ``cap[i]`` (negative: uncapacitated) to the resident

@@ -802,10 +802,14 @@ class NetworkSimplex:
                       r / f.cost_scale, self._arc_name(da), self._arc_name(ua))
         return out
 
-    def _update_rhs(self, supplies, capacities) -> dict:
+    def _update_rhs(self, supplies, capacities, dual: bool = False) -> dict:
         f = self.flat
         s_idx, s_int, s_val, c_idx, c_int, c_val = map_rhs_changes(f, supplies, capacities, self.tolerance)
-        report = self.engine.update_rhs(s_idx, s_int, c_idx, c_int)
+        if dual:
+            report, dual_report, _ = self.engine.update_rhs_dual(s_idx, s_int, c_idx, c_int)
+            report["dual"] = dual_report
+        else:
+            report = self.engine.update_rhs(s_idx, s_int, c_idx, c_int)
         new_supply, new_cap = f.supply.copy(), f.cap.copy()
         new_supply[s_idx] = s_int
         new_cap[c_idx] = c_int
@@ -833,19 +837,21 @@ class NetworkSimplex:
         self.flat = replace(f, supply=new_supply, cap=new_cap)
         return report
 
-    def update_supplies(self, changes) -> dict:
+    def update_supplies(self, changes, dual: bool = False) -> dict:
         """Change supplies / demands and keep the solved state (``mcf_update_rhs``): the tree flows of the resident basis
         are recomputed on the device; where they respect the bounds the basis stays (a solved instance is optimal again in
         zero pivots), otherwise it is repaired and the next ``solve()`` pivots on from it.  ``changes``: ``{node id:
         supply}`` for an object-model problem, ``(indices, supplies)`` for an ``SoAProblem`` (``map_rhs_changes``; on an
         invalid change nothing is changed).  The caller's problem object is left alone: ``self.problem`` becomes an updated
-        copy.  Returns the engine's report (``path`` 0 = basis kept, 1 = repaired, 2 = cold start)."""
-        return self._update_rhs(changes, None)
+        copy.  Returns the engine's report (``path`` 0 = basis kept, 1 = repaired, 2 = cold start).  ``dual=True``: dual simplex
+        pivots on the device drive violated tree flows back inside their bounds before any repair (``mcf_update_rhs_dual``);
+        the report then carries the fields of ``mcf_dual_report`` under ``"dual"``."""
+        return self._update_rhs(changes, None, dual)
 
-    def update_capacities(self, changes) -> dict:
+    def update_capacities(self, changes, dual: bool = False) -> dict:
         """Change arc capacities and keep the solved state, as ``update_supplies`` does.  ``changes``: ``{(tail, head):
         capacity or None}`` for an object-model problem, ``(indices, capacities)`` (negative: none) for an ``SoAProblem``."""
-        return self._update_rhs(None, changes)
+        return self._update_rhs(None, changes, dual)
 
     def _arc_order(self) -> list[int]:
         """flat arc j is arc order[j] of the problem: flatten_problem's stable sort by key, then the arcs ``add_arcs`` appended."""
