@@ -1775,7 +1775,13 @@ MCF_HD void mcf_pivot_walk(const McfView& v, int64_t best_key, int64_t best_arc,
     MCF_PSTAMP(16);
 }
 
-MCF_HD void mcf_pivot_finish(const McfView& v, const McfPaths& pp, int32_t lane, int32_t nlanes) {
+// BESIDE_APPLY (dense layout only: no position-space sizes, no coarse index, no blocked list): a finish pass that the apply
+// pass of the same pivot need not wait for -- the LDS loop runs the two between the same two barriers, in different waves.
+// It writes no segment table (the apply pass computes its sources from the recorded stem: mcf_apply_source_paths) and
+// stores the parent, pred and size words of node[stem[i]] only: the depth word, which the plain pass rewrites with the
+// value it had, belongs to the apply pass.  Everything else -- flows, states, sizes, Devex weights -- is the plain pass's.
+template <bool BESIDE_APPLY = false>
+MCF_HD void mcf_pivot_finish_t(const McfView& v, const McfPaths& pp, int32_t lane, int32_t nlanes) {
     const McfCtx* c = v.ctx;
     const int32_t stage = c->stage;
     if (stage == 0) return;
@@ -1877,7 +1883,7 @@ MCF_HD void mcf_pivot_finish(const McfView& v, const McfPaths& pp, int32_t lane,
             nr.parent = v_in;
             nr.pred = (e << 1) | c->pv_tail_in_t2;
             nr.size = S;
-            v.seg[0] = McfSeg{b, p, r.size, dd};
+            if (!BESIDE_APPLY) v.seg[0] = McfSeg{b, p, r.size, dd};
         } else {
             const McfNode rp = srec[i - 1];
             const int32_t pp = spos[i - 1];
@@ -1887,14 +1893,25 @@ MCF_HD void mcf_pivot_finish(const McfView& v, const McfPaths& pp, int32_t lane,
             const int32_t left = pp - p;                            // s_i itself + blocks before block(s_{i-1})
             const int32_t right = (p + r.size) - (pp + rp.size);   // blocks after it (may be empty)
             const int32_t dst = b + rp.size;
-            v.seg[2 * i - 1] = McfSeg{dst, p, left, dd};
-            v.seg[2 * i] = McfSeg{dst + left, pp + rp.size, right, dd};
+            if (!BESIDE_APPLY) {
+                v.seg[2 * i - 1] = McfSeg{dst, p, left, dd};
+                v.seg[2 * i] = McfSeg{dst + left, pp + rp.size, right, dd};
+            }
         }
-        v.node[stem[i]] = nr;
+        if (BESIDE_APPLY) {
+            McfNode* const q = &v.node[stem[i]];
+            q->parent = nr.parent; q->pred = nr.pred; q->size = nr.size;
+        } else {
+            v.node[stem[i]] = nr;
+        }
         if (bpl) zarena[sslot[i]] = nr.size;   // moved to its new slot by the update pass
         else if (v.psz[0]) { v.psz[0][p] = nr.size; v.psz[1][p] = nr.size; }  // moved to its new position by the apply pass
     }
     if (bpl) mcf_bpl_prepare(v, *c, lane, nlanes);
+}
+
+MCF_HD void mcf_pivot_finish(const McfView& v, const McfPaths& pp, int32_t lane, int32_t nlanes) {
+    mcf_pivot_finish_t<false>(v, pp, lane, nlanes);
 }
 
 // Convenience for single-threaded callers (CPU emulation): the whole pivot.
@@ -1929,6 +1946,40 @@ MCF_HD int32_t mcf_apply_source(const McfCtx& c, const McfSeg* seg, int32_t j, b
     return b <= a0 ? j - S : j + S;
 }
 
+// The same (source position, in_t2, ddepth) from the stem as the search recorded it -- srec[i] / spos[i], i = 0 .. pv_k, on the
+// leaving arc's side -- and the control block, not from the segment table: a caller that uses this one need not wait for the
+// finish pass (mcf_pivot_finish_t<true> writes no table).  With z_i = srec[i].size and p_i = spos[i]: the pieces 0 .. i of the
+// re-rooted subtree are exactly the old block of s_i, so piece i occupies the new positions [b + z_{i-1}, b + z_i), z_{-1} = 0,
+// and the piece of j is the smallest i with j < b + z_i -- a binary search over k + 1 sizes.  Inside piece i >= 1, s_i and what
+// preceded block(s_{i-1}) inside block(s_i) come first (left = p_{i-1} - p_i positions, from p_i on), then what followed it
+// (from p_{i-1} + z_{i-1} on; may be empty).  Every node of piece i moves from depth(s_i) to depth(v_in) + 1 + i.
+MCF_HD int32_t mcf_apply_source_paths(const McfCtx& c, const McfNode* srec, const int32_t* spos, int32_t j, bool* in_t2, int32_t* ddepth) {
+    const int32_t b = c.t2_new, S = c.t2_size, a0 = c.t2_old;
+    if (j >= b && j < b + S) {
+        *in_t2 = true;
+        if (c.nseg == 1) {   // (one piece, described by the control block alone)
+            *ddepth = c.pv_dd0;
+            return a0 + (j - b);
+        }
+        const int32_t r = j - b;
+        int32_t lo = 0, hi = c.pv_k;  // first piece with z_i > r (z_k = S > r)
+        while (lo < hi) {
+            const int32_t mid = (lo + hi) >> 1;
+            if (srec[mid].size > r) hi = mid; else lo = mid + 1;
+        }
+        const McfNode ri = srec[lo];
+        const int32_t p = spos[lo];
+        *ddepth = c.pv_vin_depth + 1 + lo - ri.depth;
+        if (lo == 0) return p + r;
+        const int32_t zp = srec[lo - 1].size, pprev = spos[lo - 1];
+        const int32_t off = r - zp, left = pprev - p;
+        return off < left ? p + off : pprev + zp + (off - left);
+    }
+    *in_t2 = false;
+    *ddepth = 0;
+    return b <= a0 ? j - S : j + S;
+}
+
 // One element of the apply pass (the HIP kernel runs this for a grid-strided j).
 // Returns the subtree size now stored at position j (0 when the view keeps none): the apply pass re-indexes reach[] from it.
 MCF_HD int32_t mcf_apply_one(const McfView& v, const McfCtx& c, int32_t j) {
@@ -1960,6 +2011,32 @@ MCF_HD int32_t mcf_apply_one(const McfView& v, const McfCtx& c, int32_t j) {
         int32_t z = 0;
         if (zsrc) { z = zsrc[j]; zdst[j] = z; }
         return z;
+    }
+}
+
+// mcf_apply_one on the dense layout without position-space sizes, its source from the recorded stem (mcf_apply_source_paths):
+// srec / spos are the leaving arc's side of the paths (pv_result == 1: rec1 / ppos1, else rec2 / ppos2).  Reads order[cur] and
+// the path arrays, reads and writes pi[] and node[].depth, writes order[cur ^ 1] and pos[cur ^ 1] -- no word that
+// mcf_pivot_finish_t<true> writes.
+MCF_HD void mcf_apply_one_paths(const McfView& v, const McfCtx& c, const McfNode* srec, const int32_t* spos, int32_t j) {
+    const int32_t* src = c.cur ? v.order[1] : v.order[0];
+    int32_t* dst = c.cur ? v.order[0] : v.order[1];
+    int32_t* pnext = c.cur ? v.posbuf[0] : v.posbuf[1];
+    if (j >= c.lo && j < c.hi) {
+        bool in_t2;
+        int32_t dd;
+        const int32_t i = mcf_apply_source_paths(c, srec, spos, j, &in_t2, &dd);
+        const int32_t nd = src[i];
+        dst[j] = nd;
+        pnext[nd] = j;
+        if (in_t2) {
+            v.pi[nd] += c.sigma;
+            if (dd) v.node[nd].depth += dd;
+        }
+    } else {
+        const int32_t nd = src[j];
+        dst[j] = nd;  // catch up on what the previous apply changed in the other copy
+        pnext[nd] = j;
     }
 }
 

@@ -1606,6 +1606,15 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t 
 #else
 #define STAMP(slot) do {} while (0)
 #endif
+// (diagnostic build: the finishing wave's own clock -- the cycles of its finish pass, summed into slot 7 -- since lane 0's
+//  stamps merge finish and apply into one figure once the two run side by side)
+#ifdef MCF_STAMPS
+#define MCF_LAST_WAVE_BEGIN() const unsigned long long lw0_ = __builtin_amdgcn_s_memtime()
+#define MCF_LAST_WAVE_STAMP() do { last_wave_ += __builtin_amdgcn_s_memtime() - lw0_; } while (0)
+#else
+#define MCF_LAST_WAVE_BEGIN() do {} while (0)
+#define MCF_LAST_WAVE_STAMP() do {} while (0)
+#endif
 
 // ------------------------------------------------------------------ node-parallel cycle search (LDS loop)
 // A tree that fits one workgroup's lanes needs no walk at all: lane x asks whether NODE x is an ancestor of the entering arc's
@@ -1628,6 +1637,18 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t 
 struct SmallCycleAcc {
     int32_t c1[16], c2[16];   // one-sided ancestors per wave, first / second side
 };
+// The join is not looked for: nothing behind the search reads it (mcf_pivot_decide: d1 / d2 / k1 / k2 / n1 / n2; mcf_pivot_swap:
+// n1 / n2 and the end points' r0 / p0 / s0), so the common ancestors file nothing -- the loads of the look-up folded away on their
+// own, the by-depth LDS stores could not -- and the by-depth part of the scratch goes unused.  The root, node n_nodes - 1, is a
+// common ancestor at every pivot: the passes run over the real nodes only, one pass instead of two at 256 real nodes and 256
+// lanes.  At 256 lanes only: at 1 024 lanes, where 257 tree nodes are one pass either way, the kernels without the join measured
+// 80 - 470 cycles per pivot SLOWER than with it (profiles/small_loop_back_stamps.txt), so they keep it.
+// A/B build: -DMCF_SMALL_JOIN files the common ancestors, looks the join up and passes over the root at every width, as before.
+#if defined(MCF_SMALL_JOIN)
+template <int THREADS> struct SmallSearchJoin { static constexpr bool value = true; };
+#else
+template <int THREADS> struct SmallSearchJoin { static constexpr bool value = THREADS != 256; };
+#endif
 
 // Ratio test of one side over res[0 .. n), by all 64 lanes of a wave.  !LAST: strictly smaller wins, the lowest index among
 // equal residuals (d = MCF_INF, k = -1 when nothing is below MCF_INF); LAST: smaller or equal wins, the highest index.
@@ -1654,6 +1675,7 @@ __device__ __forceinline__ void small_ratio_side(const int64_t* res, int32_t n, 
 template <int THREADS>
 __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycleAcc& A, int64_t* scratch, McfCycle& cy) {
     constexpr bool kScalar = SmallScalarControl<THREADS>::value;
+    constexpr bool kSearchJoin = SmallSearchJoin<THREADS>::value;
     const McfCtx* c = v.ctx;   // (the caller's registers)
     const int32_t* pcur = c->cur ? v.posbuf[1] : v.posbuf[0];
     const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth;
@@ -1666,14 +1688,15 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
     int64_t* const res2 = res1 + N;
     int32_t* const by_depth = reinterpret_cast<int32_t*>(res2 + N);
     int32_t n1w = 0, n2w = 0;   // this wave's one-sided ancestors, over its passes
-    for (int32_t x0 = 0; x0 < N; x0 += THREADS) {   // (uniform: every wave makes every pass)
+    const int32_t nx = kSearchJoin ? N : N - 1;   // (the root files nothing: see kSearchJoin)
+    for (int32_t x0 = 0; x0 < nx; x0 += THREADS) {   // (uniform: every wave makes every pass)
         const int32_t x = x0 + (int32_t)threadIdx.x;
         bool h1 = false, h2 = false;
-        if (x < N) {
+        if (x < nx) {
             const McfNode rec = v.node[x];
             const int32_t px = pcur[x];
             const bool au = (uint32_t)(pu - px) < (uint32_t)rec.size, aw = (uint32_t)(pw - px) < (uint32_t)rec.size;
-            if (au && aw) by_depth[rec.depth] = x;
+            if (au && aw) { if (kSearchJoin) by_depth[rec.depth] = x; }
             else if (au) {
                 const McfArcW a = v.arcw[rec.pred >> 1];
                 const int32_t idx = du0 - rec.depth;
@@ -1716,13 +1739,15 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         small_ratio_side<true>(res2, n2, &d2, &k2);
     }
 #endif
-    const int32_t jn = uni32<kScalar>(by_depth[du0 - n1]);   // the join: the common ancestor right above the first side's path
-    const McfNode rj = uni_node<kScalar>(v.node[jn]);        // (the finish pass leaves the join's record alone)
-    const int32_t pj = uni32<kScalar>(pcur[jn]);
     cy.d1 = uni64<kScalar>(d1); cy.k1 = uni32<kScalar>(k1); cy.d2 = uni64<kScalar>(d2); cy.k2 = uni32<kScalar>(k2);
     cy.n1 = n1; cy.n2 = n2;
-    cy.u = jn; cy.w = jn; cy.ru = rj; cy.rw = rj;
-    cy.pu = pj; cy.pw = pj; cy.su = pj; cy.sw = pj;
+    if (kSearchJoin) {
+        const int32_t jn = uni32<kScalar>(by_depth[du0 - n1]);   // the join: the common ancestor right above the first side's path
+        const McfNode rj = uni_node<kScalar>(v.node[jn]);        // (the finish pass leaves the join's record alone)
+        const int32_t pj = uni32<kScalar>(pcur[jn]);
+        cy.u = jn; cy.w = jn; cy.ru = rj; cy.rw = rj;
+        cy.pu = pj; cy.pw = pj; cy.su = pj; cy.sw = pj;
+    }
     // (p0u / p0w / s0u / s0w / r0u / r0w stay what mcf_pivot_begin_t<true> read)
 }
 
@@ -1806,6 +1831,32 @@ constexpr bool kBeginWx = false;
 #else
 constexpr bool kBeginWx = true;
 #endif
+// ---- the back of a pivot.  A/B builds: -DMCF_SMALL_NO_BESIDE runs the finish pass on all lanes and the apply pass behind a
+// barrier, from the segment table; -DMCF_SMALL_FRONT_WEIGHT leaves the Devex pointers of the front kernel's view to the run time.
+#if defined(MCF_SMALL_NO_BESIDE)
+constexpr bool kFinishBeside = false;
+#else
+constexpr bool kFinishBeside = true;
+#endif
+#if defined(MCF_SMALL_FRONT_WEIGHT)
+constexpr bool kFrontNoDevex = false;
+#else
+constexpr bool kFrontNoDevex = true;
+#endif
+// The pivot descriptor in the LDS image: at 256 lanes the general kernel carries it in registers across the loop and lane 0 stores
+// it once behind the loop (small_desc_store_all: -280 to -340 cycles per pivot under Devex and the candidate list, 0 B scratch);
+// the front kernel keeps lane 0's per-pivot stores (small_desc_store: -85 there, inside the repeat spread), and so do the
+// 1 024-lane kernels, where carrying it spilled.  A/B builds: -DMCF_SMALL_DESC_PER_PIVOT stores per pivot in every
+// kernel, -DMCF_SMALL_DESC_ONCE once in the 256-lane front kernel too.
+template <int THREADS, bool FRONT> struct SmallDescOnce {
+#if defined(MCF_SMALL_DESC_PER_PIVOT)
+    static constexpr bool value = false;
+#elif defined(MCF_SMALL_DESC_ONCE)
+    static constexpr bool value = THREADS == 256;
+#else
+    static constexpr bool value = THREADS == 256 && !FRONT;
+#endif
+};
 // What a lane remembers of its best arc besides the key: end points and slot in one word -- tail | head << 11 | slot << 22,
 // slot q = the lane's q-th arc, engine index r_lo + q * kPer -- the invariant part precomputed per register arc; bit 31 is
 // the state's sign (set: -1, the arc sits at capacity).  11 bits per node and 9 per slot cover every instance of the LDS plan
@@ -1889,6 +1940,14 @@ __device__ __forceinline__ void small_desc_store(McfCtx* c, const McfCtx& x, int
         if (x.pv_result != 1) { c->pv_adj[0] = adj2; c->pv_adj[1] = adj3; }
     }
 }
+// The whole descriptor at once, after the loop (kDescOnce): cx starts as a copy of the image, and begin / decide / swap change
+// exactly the fields small_desc_store copies under exactly its conditions, so the image ends up the same.
+__device__ __forceinline__ void small_desc_store_all(McfCtx* c, const McfCtx& x) {
+    MCF_SMALL_DESC_BEGIN_32(MCF_FST) MCF_SMALL_DESC_BEGIN_64(MCF_FST)
+    MCF_SMALL_DESC_DECIDE_32(MCF_FST) MCF_SMALL_DESC_DECIDE_64(MCF_FST)
+    MCF_SMALL_DESC_SWAP_32(MCF_FST) MCF_SMALL_DESC_SWAP_64(MCF_FST)
+    c->pv_t2node = x.pv_t2node; c->pv_adj[0] = x.pv_adj[0]; c->pv_adj[1] = x.pv_adj[1];
+}
 #undef MCF_FST
 template <bool SCALAR> __device__ __forceinline__ void uni_cycle(McfCycle& y) {
     y.d1 = uni64<SCALAR>(y.d1); y.d2 = uni64<SCALAR>(y.d2); y.k1 = uni32<SCALAR>(y.k1); y.k2 = uni32<SCALAR>(y.k2); y.n1 = uni32<SCALAR>(y.n1); y.n2 = uni32<SCALAR>(y.n2);
@@ -1911,6 +1970,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
 #ifdef MCF_STAMPS
     unsigned long long stamps_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long last_ = __builtin_amdgcn_s_memtime();
+    unsigned long long last_wave_ = 0;
     if (threadIdx.x == 0) { for (int i = 0; i < 24; ++i) mcf_stamp_acc[i] = 0; mcf_stamp_last = last_; }
 #endif
     const uint32_t m_pad4 = (uint32_t)((g.m + 1023) / 1024 * 1024) * 4u;
@@ -1944,6 +2004,9 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     v.reach = nullptr;
     v.bmeta[0] = nullptr; v.bmeta[1] = nullptr; v.candx = nullptr; v.dirty = nullptr; v.dirty_hdr = nullptr;   // (folds the blocked list etc. away)
     v.rcache = nullptr; v.adj_off = nullptr;   // (a handle on this path keeps no resident reduced costs, mcf_create: folds their branches away)
+    // the front kernel is Dantzig's: no weights, no Devex state (small_front_for refuses a view that carries weights) -- the
+    // Devex branches of mcf_pivot_decide and of the finish pass fold away
+    if constexpr (FRONT && kFrontNoDevex) { v.weight = nullptr; v.dx = nullptr; }
 
     // (All fourteen arrays' loads in flight together -- one fused loop, 4- or 16-byte loads -- was measured SLOWER than these
     //  plain loops: 131 / 125 us against 117 us per 20-pivot launch.)
@@ -1952,7 +2015,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     copy_words<THREADS>(smem + L.cost, g.cost, m_pad4);
     copy_words<THREADS>(smem + L.orig, g.orig, m_pad4);
     copy_words<THREADS>(smem + L.state, g.state, m_padb);
-    if (g.weight) copy_words<THREADS>(smem + L.weight, g.weight, m_pad4);
+    if (v.weight) copy_words<THREADS>(smem + L.weight, g.weight, m_pad4);
     copy_words<THREADS>(smem + L.arcw, g.arcw, arcw_b);
     copy_words<THREADS>(smem + L.pi, g.pi, N * 8u);
     copy_words<THREADS>(smem + L.node, g.node, N * 16u);
@@ -2021,6 +2084,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     // record to begin.  64-bit keys price, reduce and begin as before.
     const bool reg_plain = kRegSweep && sweep == kSweepPlain;
     constexpr bool nar = FRONT;
+    constexpr bool kDescOnce = SmallDescOnce<THREADS, FRONT>::value;
     constexpr bool hand = FRONT && kHandover;
     const int32_t* const pi32 = reinterpret_cast<const int32_t*>(v.pi);   // low words of the potentials
     // ---- control in registers.  Every wave carries the control block itself -- a private McfCtx whose fields live in scalar
@@ -2030,8 +2094,16 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     // "lane 0 wrote, everybody reads" are gone.  The LDS image is written once after the loop.
     // THE RULE that replaces those barriers: between two barriers no wave reads an LDS location that a faster wave can write
     // before the next barrier.  Its instances here:
-    //   * the parallel search's residual / by-depth scratch has LDS of its own, not the segment table's (the finish pass
-    //     of a faster wave fills that table while a slower one still runs its ratio tests);
+    //   * the parallel search's residual / by-depth scratch has LDS of its own, not the segment table's (the general finish pass
+    //     fills that table; the one that runs here leaves it alone);
+    //   * finish and apply run between the SAME two barriers, the finish pass in the last wave (mcf_pivot_finish_t<true>), the
+    //     apply pass in every wave (mcf_apply_one_paths), and touch disjoint LDS words.  Finish reads the recorded paths (path /
+    //     rec / ppos, ordered by the search barrier) and the descriptor in registers; it writes arcw[].flow, state[], the Devex
+    //     weights, node[].size along both sides and node[stem[i]].{parent, pred, size} -- never a depth word, never the segment
+    //     table.  Apply reads order[cur] and the same recorded paths (its sources come from them: mcf_apply_source_paths); it
+    //     reads and writes pi[] and node[].depth and writes order[cur ^ 1] and pos[cur ^ 1].  A wave that still runs its ratio
+    //     tests or decides reads the residual scratch, the per-wave counts and the recorded paths: nothing either pass writes.
+    //     The end-of-iteration barrier orders both passes' stores before the next sweep, begin and search;
     //   * the end points' records and positions (r0u / r0w / p0u / p0w) are begin's reads, taken before the search barrier:
     //     the finish pass rewrites node[u_in];
     //   * begin reads arcw[e].flow and state[e], finish writes them: all of begin's reads precede the search barrier;
@@ -2242,19 +2314,41 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             }
         }
         small_ctx_uniform<kScalar>(cx);
-        if (threadIdx.x == 0) small_desc_store(c, cx, adj2, adj3);
+        if constexpr (!kDescOnce) { if (threadIdx.x == 0) small_desc_store(c, cx, adj2, adj3); }
         MCF_PSTAMP(16);
         STAMP(3);
         // (no barrier: the finish pass reads the recorded paths, which the search barrier ordered, and the descriptor in registers)
-        mcf_pivot_finish(v, mcf_view_paths(v), threadIdx.x, THREADS);
-        __syncthreads();   // the finish pass's segment table and node records -> the apply pass
-        STAMP(4);
-        // ---- apply: block permutation of the preorder array + potential shift, the descriptor straight from registers
-        if (cx.apply) {
-            const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
-            for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one(v, cx, j);
-            for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
-                if (j < lo || j >= hi) mcf_apply_one(v, cx, j);
+        if constexpr (kFinishBeside) {
+            // finish and apply between the same two barriers: the LAST wave alone finishes (uniform per wave; the pass needs
+            // n1 + n2 and k + 1 lanes, about ten on netgen_8_08a) while the others apply; it then takes the apply positions from
+            // lo + THREADS - 64 on, which most pivots do not have.  See THE RULE above for why the two never meet.
+            if ((int32_t)threadIdx.x >= THREADS - 64) {
+                MCF_LAST_WAVE_BEGIN();
+                mcf_pivot_finish_t<true>(v, mcf_view_paths(v), (int32_t)threadIdx.x - (THREADS - 64), 64);
+                MCF_LAST_WAVE_STAMP();
+            }
+            STAMP(4);
+            // ---- apply: block permutation of the preorder array + potential shift, the descriptor straight from registers, the
+            // sources from the recorded stem (mcf_apply_source_paths)
+            if (cx.apply) {
+                const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
+                const McfNode* const srec = cx.pv_result == 1 ? v.rec1 : v.rec2;
+                const int32_t* const spos = cx.pv_result == 1 ? v.ppos1 : v.ppos2;
+                for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one_paths(v, cx, srec, spos, j);
+                for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
+                    if (j < lo || j >= hi) mcf_apply_one_paths(v, cx, srec, spos, j);
+            }
+        } else {
+            mcf_pivot_finish(v, mcf_view_paths(v), threadIdx.x, THREADS);
+            __syncthreads();   // the finish pass's segment table and node records -> the apply pass
+            STAMP(4);
+            // ---- apply: block permutation of the preorder array + potential shift, the descriptor straight from registers
+            if (cx.apply) {
+                const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
+                for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one(v, cx, j);
+                for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
+                    if (j < lo || j >= hi) mcf_apply_one(v, cx, j);
+            }
         }
         __syncthreads();   // the apply pass's order / position / potential / depth stores and the finish pass's flows and states
                            // -> the next iteration's sweep, begin and search
@@ -2262,7 +2356,10 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         STAMP(5);
     }
     // the control state goes back into the LDS image, once
-    if (threadIdx.x == 0) small_ctx_store(c, cx);
+    if (threadIdx.x == 0) {
+        small_ctx_store(c, cx);
+        if constexpr (kDescOnce) small_desc_store_all(c, cx);
+    }
     v.ctx = c;
     __syncthreads();   // the LDS control block -> the budget check and the copy-out
 
@@ -2280,7 +2377,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         __syncthreads();
     }
     copy_words<THREADS>(g.state, smem + L.state, m_padb);
-    if (g.weight) copy_words<THREADS>(g.weight, smem + L.weight, m_pad4);
+    if (v.weight) copy_words<THREADS>(g.weight, smem + L.weight, m_pad4);
     copy_words<THREADS>(g.arcw, smem + L.arcw, arcw_b);
     copy_words<THREADS>(g.pi, smem + L.pi, N * 8u);
     copy_words<THREADS>(g.node, smem + L.node, N * 16u);
@@ -2296,9 +2393,10 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     STAMP(6);
     if (threadIdx.x == 0) {  // diagnostic build only: cycle sums into the (global) path scratch, read by mcf_debug_stamps
         unsigned long long* out = reinterpret_cast<unsigned long long*>(g.rec1);
-        for (int i = 0; i < 8; ++i) out[i] = stamps_[i];
+        for (int i = 0; i < 7; ++i) out[i] = stamps_[i];
         for (int i = 0; i < 24; ++i) g_pivot_stamps[i] += mcf_stamp_acc[i];
     }
+    if (threadIdx.x == THREADS - 64) reinterpret_cast<unsigned long long*>(g.rec1)[7] = last_wave_;   // (0 when nothing ran beside)
 #endif
 }
 
@@ -3010,9 +3108,11 @@ int32_t small_narrow_for(const McfHostImage& im, bool allowed) {
     return allowed && small_info_fits(im.n_nodes, im.m_pad) && mcf_small_narrow_fits(im.big_m, max_abs) ? 1 : 0;
 }
 
-// Which kernel: the front kernel (k_solve_small<.., true>) for Dantzig with the plain key on a range that fits
-bool small_front_for(int32_t narrow, int32_t rule, int32_t key_mode) {
-    return kNarrowSweep && kRegSweep && narrow != 0 && rule == MCF_RULE_DANTZIG && key_mode == MCF_KEY_PLAIN;
+// Which kernel: the front kernel (k_solve_small<.., true>) for Dantzig with the plain key on a range that fits.  The front kernel
+// sets the view's Devex pointers to null at compile time: a view that carries weights never takes it (mcf_create gives weights
+// to MCF_RULE_DEVEX_BLOCK only, so this refuses nothing today -- it states what the kernel relies on).
+bool small_front_for(int32_t narrow, int32_t rule, int32_t key_mode, const McfView& view) {
+    return kNarrowSweep && kRegSweep && narrow != 0 && rule == MCF_RULE_DANTZIG && key_mode == MCF_KEY_PLAIN && !view.weight && !view.dx;
 }
 
 // The dynamic-LDS limit of the fused kernels covers `total` bytes on this device.  (The limit is a property of the kernel,
@@ -3464,7 +3564,7 @@ int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user,
                 const int32_t narrow = small_narrow_for(h->im, h->small_narrow_ok);   // (per launch: big-M may have grown)
                 h->stats.small_narrow = narrow;
                 auto kernel = k_solve_small<256, false>;
-                const bool front = small_front_for(narrow, h->opt.rule, h->view.key_mode);
+                const bool front = small_front_for(narrow, h->opt.rule, h->view.key_mode, h->view);
                 if (h->small_threads == 1024) kernel = front ? k_solve_small<1024, true> : k_solve_small<1024, false>;
                 else if (front) kernel = k_solve_small<256, true>;
                 hipLaunchKernelGGL(kernel, dim3(1), dim3(h->small_threads == 1024 ? 1024 : 256), h->small_layout.total, h->stream, h->view,
@@ -3616,7 +3716,7 @@ int mcf_solve_batch(mcf_handle* const* handles, int32_t count, const int64_t* ma
     // candidate-list jobs last (their own launch)
     std::stable_partition(mid_jobs.begin(), mid_jobs.end(), [](const MidJob& J) { return J.rule != MCF_RULE_CANDIDATE_LIST; });
     // ... and the LDS jobs of the front kernel behind the others (small_front_for: a launch each)
-    auto job_front = [](const SmallJob& J) { return small_front_for(J.narrow, J.rule, J.g.key_mode); };
+    auto job_front = [](const SmallJob& J) { return small_front_for(J.narrow, J.rule, J.g.key_mode, J.g); };
     std::stable_partition(small_jobs.begin(), small_jobs.end(), [&](const SmallJob& J) { return !job_front(J); });
     size_t n_front = 0;
     for (const SmallJob& J : small_jobs) n_front += job_front(J) ? 1 : 0;

@@ -15,7 +15,7 @@ for rule in (0, 1, 2):
     eng._lib.mcf_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]
     eng._lib.mcf_debug_stamps(eng._h, out)
     v = np.array(list(out), dtype=np.float64)
-    names = ["copy_in", "price", "argmax", "walk", "finish", "apply", "copy_out", "-"]
+    names = ["copy_in", "price", "argmax", "walk", "finish", "apply", "copy_out", "fin_last"]   # fin_last: the finishing (last) wave's own clock over its finish pass
     piv = max(st["pivots"], 1)
     print("rule", rule, "pivots", piv, "solve_s", st["solve_seconds"], "ticks/pivot in loop", v[1:6].sum() / piv)
     for n, x in zip(names, v):
