@@ -104,7 +104,60 @@ __device__ __forceinline__ int64_t mcf_wave_max64(int64_t x) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)x >> 32), 63);
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
+// The same six controls on an unsigned 32-bit value: a lane the control leaves out reads the reduction's identity, so a step is
+// ONE v_min_u32 / v_max_u32 with the DPP modifier on its operand -- no moves, no 64-bit compare, no selects.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t mcf_dpp_min_u32_step(uint32_t x) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)x, CTRL, ROW_MASK, 0xf, false);
+    return o < x ? o : x;
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t mcf_dpp_max_u32_step(uint32_t x) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROW_MASK, 0xf, false);
+    return o > x ? o : x;
+}
+__device__ __forceinline__ uint32_t mcf_wave_min_u32(uint32_t x) {
+    x = mcf_dpp_min_u32_step<0xB1, 0xf>(x);
+    x = mcf_dpp_min_u32_step<0x4E, 0xf>(x);
+    x = mcf_dpp_min_u32_step<0x141, 0xf>(x);
+    x = mcf_dpp_min_u32_step<0x140, 0xf>(x);
+    x = mcf_dpp_min_u32_step<0x142, 0xa>(x);
+    x = mcf_dpp_min_u32_step<0x143, 0xc>(x);
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+__device__ __forceinline__ uint32_t mcf_wave_max_u32(uint32_t x) {
+    x = mcf_dpp_max_u32_step<0xB1, 0xf>(x);
+    x = mcf_dpp_max_u32_step<0x4E, 0xf>(x);
+    x = mcf_dpp_max_u32_step<0x141, 0xf>(x);
+    x = mcf_dpp_max_u32_step<0x140, 0xf>(x);
+    x = mcf_dpp_max_u32_step<0x142, 0xa>(x);
+    x = mcf_dpp_max_u32_step<0x143, 0xc>(x);
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
 #endif
+
+// ---- selection arithmetic round the 32-bit wave reductions of the fused LDS loop (mcf_engine.hip: small_ratio_side and the
+// front kernel's arg-max).  The device code calls these round its DPP steps; csrc/mcf_small_reduce_host.cpp calls the same
+// functions round plain loops over an array of 64 "lanes", for the CPU tests.
+// Ratio test: a residual is a flow or a spare capacity, or MCF_INF.  A side is NARROW when every residual of it is MCF_INF or in
+// [0, 2^32 - 2]: then it maps to a 32-bit key in order, MCF_INF above every finite residual, and the minimum of the keys names the
+// minimum of the residuals.  Anything else (a negative residual, a finite one from 2^32 - 1 on, a value above MCF_INF) is not.
+MCF_HD bool mcf_ratio_narrow_ok(int64_t r) { return r == MCF_INF || (uint64_t)r <= 0xfffffffeull; }
+MCF_HD uint32_t mcf_ratio_key32(int64_t r) { return r == MCF_INF ? 0xffffffffu : (uint32_t)r; }   // (of a narrow residual)
+MCF_HD int64_t mcf_ratio_unkey32(uint32_t k) { return k == 0xffffffffu ? MCF_INF : (int64_t)k; }
+// One stride of 64 path indices from `base` on: `mn` its minimum, `mask` the lanes (inside the side) that hold it; never empty.
+// !LAST: strictly smaller wins, the lowest index among equals; LAST: smaller or equal wins, the highest index.
+template <bool LAST>
+MCF_HD void mcf_ratio_take(int64_t mn, uint64_t mask, int32_t base, int64_t& d, int32_t& k) {
+    if (LAST ? mn <= d : mn < d) {
+        d = mn;
+        k = base + (LAST ? 63 - __builtin_clzll((unsigned long long)mask) : __builtin_ctzll((unsigned long long)mask));
+    }
+}
+// Arg-max of the packed pricing keys (violation << 32) | ~id in two 32-bit stages: the violations first; among the lanes that
+// hold the largest, ~id (an id is >= 0, so ~id has its top bit set and 0 stands for "not among them").
+MCF_HD uint32_t mcf_argmax_viol(uint64_t packed) { return (uint32_t)(packed >> 32); }
+MCF_HD uint32_t mcf_argmax_second(uint64_t packed, uint32_t vmx) { return mcf_argmax_viol(packed) == vmx ? (uint32_t)packed : 0u; }
 
 // Diagnostic build (-DMCF_STAMPS): cycle stamps of the one-workgroup pivot kernel, accumulated per phase.
 #if defined(MCF_STAMPS) && defined(__HIPCC__)

@@ -1652,30 +1652,64 @@ template <int THREADS> struct SmallSearchJoin { static constexpr bool value = TH
 
 // Ratio test of one side over res[0 .. n), by all 64 lanes of a wave.  !LAST: strictly smaller wins, the lowest index among
 // equal residuals (d = MCF_INF, k = -1 when nothing is below MCF_INF); LAST: smaller or equal wins, the highest index.
+// A side whose residuals are all MCF_INF or below 2^32 - 1 (mcf_ratio_narrow_ok; one ballot over all its strides makes that a
+// uniform test) is reduced on 32-bit keys: one v_min_u32 with a DPP operand per step where the 64-bit reduction takes two moves,
+// a 64-bit compare and two selects.  Lanes past the end hold the key of MCF_INF and stay out of the winner's ballot.  Any other
+// side takes the 64-bit reduction; d and k are the same either way.  A/B build: -DMCF_SMALL_RATIO64 never takes the 32-bit path.
+#if defined(MCF_SMALL_RATIO64)
+constexpr bool kRatioNarrow = false;
+#else
+constexpr bool kRatioNarrow = true;
+#endif
 template <bool LAST>
 __device__ __forceinline__ void small_ratio_side(const int64_t* res, int32_t n, int64_t* d_out, int32_t* k_out) {
     const int32_t lane = (int32_t)(threadIdx.x & 63);
     int64_t d = MCF_INF;
     int32_t k = -1;
+    if (kRatioNarrow) {
+        const int64_t r0 = lane < n ? res[lane] : MCF_INF;
+        bool wide = !mcf_ratio_narrow_ok(r0);
+        for (int32_t i = 64 + lane; i < n; i += 64) wide |= !mcf_ratio_narrow_ok(res[i]);
+        if (__ballot(wide) == 0) {
+            for (int32_t base = 0; base < n; base += 64) {   // (uniform, as below)
+                const int32_t i = base + lane;
+                const uint32_t key = mcf_ratio_key32(base == 0 ? r0 : (i < n ? res[i] : MCF_INF));
+                const uint32_t mn = mcf_wave_min_u32(key);
+                const uint64_t mask = __ballot(i < n && key == mn);
+                mcf_ratio_take<LAST>(mcf_ratio_unkey32(mn), mask, base, d, k);
+            }
+            *d_out = d; *k_out = k;
+            return;
+        }
+    }
     for (int32_t base = 0; base < n; base += 64) {   // (uniform; one trip unless the path is longer than a wave)
         const int32_t i = base + lane;
         // lanes past the end can never hold the minimum: a residual is at most MCF_INF
         const int64_t r = i < n ? res[i] : INT64_MAX;
         const int64_t mn = -mcf_wave_max64(-r);
         const uint64_t mask = __ballot(r == mn);
-        if (LAST ? mn <= d : mn < d) {
-            d = mn;
-            k = base + (LAST ? 63 - __builtin_clzll((unsigned long long)mask) : __builtin_ctzll((unsigned long long)mask));
-        }
+        mcf_ratio_take<LAST>(mn, mask, base, d, k);
     }
     *d_out = d; *k_out = k;
 }
+
+// One branch for both sides: a one-sided ancestor picks its side's path, record, position and residual arrays and the end point's
+// depth with selects on `au`, computes ONE residual -- the arc loses flow when (up arc) == (first side) -- and stores once: the same
+// words with the same values as one branch per side, but a wave that holds ancestors of both end points no longer runs two
+// bodies one after the other.  At 256 lanes only: the 1 024-lane front kernel measured 135 cycles per pivot SLOWER with it
+// (profiles/small_loop_reduce_stamps.txt).  A/B build: -DMCF_SMALL_TWO_BRANCHES keeps one branch per side at every width.
+#if defined(MCF_SMALL_TWO_BRANCHES)
+template <int THREADS> struct SmallSearchOneBranch { static constexpr bool value = false; };
+#else
+template <int THREADS> struct SmallSearchOneBranch { static constexpr bool value = THREADS == 256; };
+#endif
 
 // `cy` as mcf_pivot_begin_t<true> left it (in registers, uniform); on return the finished cycle, uniform in every wave.
 template <int THREADS>
 __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycleAcc& A, int64_t* scratch, McfCycle& cy) {
     constexpr bool kScalar = SmallScalarControl<THREADS>::value;
     constexpr bool kSearchJoin = SmallSearchJoin<THREADS>::value;
+    constexpr bool kSearchOneBranch = SmallSearchOneBranch<THREADS>::value;
     const McfCtx* c = v.ctx;   // (the caller's registers)
     const int32_t* pcur = c->cur ? v.posbuf[1] : v.posbuf[0];
     const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth;
@@ -1697,7 +1731,17 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
             const int32_t px = pcur[x];
             const bool au = (uint32_t)(pu - px) < (uint32_t)rec.size, aw = (uint32_t)(pw - px) < (uint32_t)rec.size;
             if (au && aw) { if (kSearchJoin) by_depth[rec.depth] = x; }
-            else if (au) {
+            else if (kSearchOneBranch) {
+                if (au || aw) {
+                    const McfArcW a = v.arcw[rec.pred >> 1];
+                    const int32_t idx = (au ? du0 : dw0) - rec.depth;
+                    (au ? v.path1 : v.path2)[idx] = x; (au ? v.rec1 : v.rec2)[idx] = rec; (au ? v.ppos1 : v.ppos2)[idx] = px;
+                    // the first side is walked against the flow, the second with it: an up arc loses flow there and gains here
+                    const bool loses = ((rec.pred & 1) != 0) == au;
+                    (au ? res1 : res2)[idx] = loses ? a.flow : (a.cap >= MCF_INF ? MCF_INF : a.cap - a.flow);
+                    h1 = au; h2 = aw;
+                }
+            } else if (au) {
                 const McfArcW a = v.arcw[rec.pred >> 1];
                 const int32_t idx = du0 - rec.depth;
                 v.path1[idx] = x; v.rec1[idx] = rec; v.ppos1[idx] = px;
@@ -1830,6 +1874,13 @@ constexpr bool kHandover = true;
 constexpr bool kBeginWx = false;
 #else
 constexpr bool kBeginWx = true;
+#endif
+// The front kernel's arg-max.  A/B build: -DMCF_SMALL_ARGMAX64 reduces the packed key in one 64-bit max per wave, not in 32-bit
+// stages.
+#if defined(MCF_SMALL_ARGMAX64)
+constexpr bool kArgmaxStaged = false;
+#else
+constexpr bool kArgmaxStaged = true;
 #endif
 // ---- the back of a pivot.  A/B builds: -DMCF_SMALL_NO_BESIDE runs the finish pass on all lanes and the apply pass behind a
 // barrier, from the segment table; -DMCF_SMALL_FRONT_WEIGHT leaves the Devex pointers of the front kernel's view to the run time.
@@ -2232,9 +2283,24 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             constexpr int kWaves = THREADS / 64;
             __shared__ SmallWaveSlot s_slot[kWaves];
             const int32_t lane = (int32_t)(threadIdx.x & 63), wave = (int32_t)(threadIdx.x >> 6);
-            const uint64_t mx = (uint64_t)mcf_wave_max64((int64_t)nbest);
-            const bool any = (mx >> 32) != 0;
-            if (any ? nbest == mx : lane == 0) s_slot[wave] = SmallWaveSlot{any ? mx : 0, (int32_t)(arc & 0xffffffff), info};
+            bool any, win;
+            if constexpr (kArgmaxStaged) {
+                // in 32-bit stages: the largest violation; if one lane holds it, that lane wins, else the largest ~id among the
+                // lanes that do.  The winner's own packed key IS the 64-bit maximum.
+                const uint32_t vmx = mcf_wave_max_u32(mcf_argmax_viol(nbest));
+                any = vmx != 0;
+                win = mcf_argmax_viol(nbest) == vmx;
+                const uint64_t tied = __ballot(win);
+                if (any && (tied & (tied - 1))) {   // (uniform: several lanes share the violation)
+                    const uint32_t imx = mcf_wave_max_u32(mcf_argmax_second(nbest, vmx));
+                    win = win && (uint32_t)nbest == imx;
+                }
+            } else {
+                const uint64_t mx = (uint64_t)mcf_wave_max64((int64_t)nbest);
+                any = (mx >> 32) != 0;
+                win = nbest == mx;
+            }
+            if (any ? win : lane == 0) s_slot[wave] = SmallWaveSlot{any ? nbest : 0, (int32_t)(arc & 0xffffffff), info};
             __syncthreads();   // per-wave slots -> every wave's pick
             SmallWaveSlot b;
             if constexpr (kWaves <= 4) {   // one round trip, kWaves reads
