@@ -159,6 +159,19 @@ MCF_HD void mcf_ratio_take(int64_t mn, uint64_t mask, int32_t base, int64_t& d, 
 MCF_HD uint32_t mcf_argmax_viol(uint64_t packed) { return (uint32_t)(packed >> 32); }
 MCF_HD uint32_t mcf_argmax_second(uint64_t packed, uint32_t vmx) { return mcf_argmax_viol(packed) == vmx ? (uint32_t)packed : 0u; }
 
+// ---- even deal of the Dantzig register sweep (mcf_engine.hip: solve_small_body).  Dantzig's arg-max is over all arcs and
+// (violation, ~id) is a total order, so which lane prices an arc does not matter: lane t of `threads` takes the engine arcs
+// base + t + slot * threads, and a sweep runs mcf_even_slots(arcs, threads) slots -- every lane the same number, the last one
+// partly filled -- where a deal per head bucket runs as many as the fullest bucket needs.  The device code and
+// csrc/mcf_small_cycle_regs_host.cpp (CPU tests) both call these.
+MCF_HD int32_t mcf_even_arc(int32_t base, int32_t lane, int32_t slot, int32_t threads) { return base + lane + slot * threads; }
+MCF_HD int32_t mcf_even_slots(int32_t arcs, int32_t threads) { return (arcs + threads - 1) / threads; }
+// The unrolled register slots a sweep executes: the loop is compiled for `few` and for `reg` slots (few <= reg); the arcs from
+// slot `reg` on are priced from LDS.
+MCF_HD int32_t mcf_even_reg_slots(int32_t arcs, int32_t threads, int32_t few, int32_t reg) {
+    return mcf_even_slots(arcs, threads) <= few ? few : reg;
+}
+
 // Diagnostic build (-DMCF_STAMPS): cycle stamps of the one-workgroup pivot kernel, accumulated per phase.
 #if defined(MCF_STAMPS) && defined(__HIPCC__)
 __shared__ unsigned long long mcf_stamp_acc[24];

@@ -1585,6 +1585,33 @@ constexpr bool kRegSweep = true;
 // scratch memory.
 template <int THREADS> struct SmallScalarControl { static constexpr bool value = THREADS > 256; };
 template <int THREADS> struct SmallRegArcs { static constexpr int value = THREADS <= 256 ? 10 : (THREADS <= 512 ? 5 : 3); };
+// Dantzig with the plain sweep deals the arcs evenly, not per head bucket (mcf_core.h: mcf_even_arc): lane t prices the engine
+// arcs bucket_off[0] + t + slot * THREADS.  netgen_8_08a's buckets hold 229 .. 299 arcs -- 8 .. 10 slots of 32 lanes, so every
+// wave ran all ten unrolled slots -- where 2 048 arcs over 256 lanes are 8.  The front kernels' loop is compiled for two slot
+// counts, kReg and SmallRegArcsFew (2 048 arcs' worth), and the launch's constant arc count picks one (mcf_even_reg_slots: a
+// uniform branch).  In the front kernels only, where the deal is a compile-time constant: in the general kernels -- Dantzig with
+// 64-bit keys beside Devex and the candidate list, which keeps the deal per bucket since its list is each bucket's best -- the
+// stride becomes a run-time value, and Devex and the candidate list, which never deal evenly, measured 1.5 - 3 % slower over
+// whole solves with it; they keep the deal per bucket and the one sweep of kReg slots.
+// A/B builds: -DMCF_SMALL_BUCKET_DEAL deals per bucket in every kernel, as before; -DMCF_SMALL_EVEN_GENERAL deals evenly under
+// Dantzig in the general kernels too; -DMCF_SMALL_EVEN_ALL_SLOTS deals evenly but always runs kReg slots.
+template <int THREADS, bool FRONT> struct SmallEvenDeal {
+#if defined(MCF_SMALL_BUCKET_DEAL)
+    static constexpr bool value = false;
+#elif defined(MCF_SMALL_EVEN_GENERAL)
+    static constexpr bool value = true;
+#else
+    static constexpr bool value = FRONT;
+#endif
+};
+#if defined(MCF_SMALL_EVEN_ALL_SLOTS)
+template <int THREADS, bool FRONT> struct SmallRegArcsFew { static constexpr int value = SmallRegArcs<THREADS>::value; };
+#else
+template <int THREADS, bool FRONT> struct SmallRegArcsFew {
+    static constexpr int value = !FRONT ? SmallRegArcs<THREADS>::value : (THREADS <= 256 ? 8 : (THREADS <= 512 ? 4 : 2));
+};
+#endif
+template <int N> struct SmallSlots { static constexpr int value = N; };
 
 template <int THREADS>
 __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t bytes) {
@@ -1909,8 +1936,8 @@ template <int THREADS, bool FRONT> struct SmallDescOnce {
 #endif
 };
 // What a lane remembers of its best arc besides the key: end points and slot in one word -- tail | head << 11 | slot << 22,
-// slot q = the lane's q-th arc, engine index r_lo + q * kPer -- the invariant part precomputed per register arc; bit 31 is
-// the state's sign (set: -1, the arc sits at capacity).  11 bits per node and 9 per slot cover every instance of the LDS plan
+// slot q = the lane's q-th arc, engine index r_lo + q * r_step (the lanes' stride: THREADS under the even deal) -- the invariant
+// part precomputed per register arc; bit 31 is the state's sign (set: -1, the arc sits at capacity).  11 bits per node and 9 per slot cover every instance of the LDS plan
 // (small_plan: fewer than 1 371 tree nodes and 7 314 padded arcs, so at most 229 arcs per lane); small_info_fits is the
 // host's check of exactly that.
 __device__ __forceinline__ uint32_t small_info(int32_t tail, int32_t head, int32_t q) { return (uint32_t)tail | ((uint32_t)head << 11) | ((uint32_t)q << 22); }
@@ -2117,15 +2144,23 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     const int sweep = FRONT ? (int)kSweepPlain
                             : (devex ? kSweepDevex : (rule != MCF_RULE_DEVEX_BLOCK && v.key_mode == MCF_KEY_PLAIN ? kSweepPlain : kSweepGeneric));
     // Plain sweep: the arcs a lane prices are the same at every pivot (whole buckets), and tail / head / cost / orig never
-    // change during a launch: the first kReg of them live in registers from here on.  (Slots past the bucket's end price
+    // change during a launch: the first kReg of them live in registers from here on.  (Slots past the lane's last arc price
     // arc 0 with its state masked to 0.)
     int32_t r_tail[kReg], r_head[kReg], r_cost[kReg], r_orig[kReg];
     uint32_t r_info[kReg];   // (small_info: what the arg-max hands over to begin)
     int32_t r_n = 0;   // slots in use
-    const int32_t r_lo = s_gran[px][0] + pl, r_hi = s_gran[px][MCF_GRANULES];
+    // The front kernels: the even deal over all arcs (SmallEvenDeal, a compile-time constant); the general ones: per head bucket.
+    // r_step apart either way, and slot q of a lane is engine arc r_lo + q * r_step.
+    constexpr int kRegFew = SmallRegArcsFew<THREADS, FRONT>::value;
+    static_assert(kRegFew <= kReg, "the shorter unrolled sweep is a prefix of the longer");
+    const bool even = SmallEvenDeal<THREADS, FRONT>::value && kRegSweep && sweep == kSweepPlain && rule == MCF_RULE_DANTZIG;
+    const int32_t r_step = even ? THREADS : kPer;
+    const int32_t r_lo = even ? mcf_even_arc(s_gran[0][0], (int32_t)threadIdx.x, 0, THREADS) : s_gran[px][0] + pl;
+    const int32_t r_hi = even ? s_gran[MCF_NUM_BUCKETS - 1][MCF_GRANULES] : s_gran[px][MCF_GRANULES];
+    const bool r_few = even && uni32<kScalar>(mcf_even_reg_slots(s_gran[MCF_NUM_BUCKETS - 1][MCF_GRANULES] - s_gran[0][0], THREADS, kRegFew, kReg)) == kRegFew;
 #pragma unroll
     for (int k = 0; k < kReg; ++k) {
-        const int32_t i = r_lo + k * kPer;
+        const int32_t i = r_lo + k * r_step;
         const bool on = kRegSweep && sweep == kSweepPlain && i < r_hi;
         r_tail[k] = on ? v.tail[i] : 0; r_head[k] = on ? v.head[i] : 0; r_cost[k] = on ? v.cost[i] : 0; r_orig[k] = on ? v.orig[i] : 0;
         r_info[k] = small_info(r_tail[k], r_head[k], k);
@@ -2196,44 +2231,55 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             if (nar) {
                 // 32-bit keys: the low words of the potentials, one compare and two selects per arc.  The plain maximum of
                 // (violation << 32) | ~orig is mcf_cand_better's winner -- larger violation, then lower id -- and never ties.
-                int32_t st[kReg], pt[kReg], ph[kReg];
+                // The first NS register slots; under the even deal NS = kRegFew when those hold every arc (r_few, uniform).
+                auto slots = [&](auto ns) {
+                    constexpr int NS = decltype(ns)::value;
+                    int32_t st[NS], pt[NS], ph[NS];
 #pragma unroll
-                for (int k = 0; k < kReg; ++k) {
-                    st[k] = v.state[k < r_n ? r_lo + k * kPer : 0];
-                    pt[k] = pi32[2 * r_tail[k]];
-                    ph[k] = pi32[2 * r_head[k]];
-                }
+                    for (int k = 0; k < NS; ++k) {
+                        st[k] = v.state[k < r_n ? r_lo + k * r_step : 0];
+                        pt[k] = pi32[2 * r_tail[k]];
+                        ph[k] = pi32[2 * r_head[k]];
+                    }
 #pragma unroll
-                for (int k = 0; k < kReg; ++k) {
-                    const int32_t rc = (int32_t)((uint32_t)r_cost[k] + (uint32_t)pt[k] - (uint32_t)ph[k]);
-                    const int32_t s = k < r_n ? st[k] : 0;
-                    const int32_t viol = s > 0 ? -rc : rc;
-                    const uint64_t p = ((uint64_t)(uint32_t)((s != 0 && viol > 0) ? viol : 0) << 32) | (uint32_t)~r_orig[k];
-                    if (p > nbest) { nbest = p; info = r_info[k] | ((uint32_t)s & 0x80000000u); }
-                }
-                int32_t q = kReg;
-                for (int32_t i = r_lo + kReg * kPer; i < r_hi; i += kPer, ++q) small_price_lds_narrow(v, i, q, nbest, info);
+                    for (int k = 0; k < NS; ++k) {
+                        const int32_t rc = (int32_t)((uint32_t)r_cost[k] + (uint32_t)pt[k] - (uint32_t)ph[k]);
+                        const int32_t s = k < r_n ? st[k] : 0;
+                        const int32_t viol = s > 0 ? -rc : rc;
+                        const uint64_t p = ((uint64_t)(uint32_t)((s != 0 && viol > 0) ? viol : 0) << 32) | (uint32_t)~r_orig[k];
+                        if (p > nbest) { nbest = p; info = r_info[k] | ((uint32_t)s & 0x80000000u); }
+                    }
+                };
+                if (r_few) slots(SmallSlots<kRegFew>{});
+                else slots(SmallSlots<kReg>{});
+                int32_t q = kReg;   // (no trip when r_few)
+                for (int32_t i = r_lo + kReg * r_step; i < r_hi; i += r_step, ++q) small_price_lds_narrow(v, i, q, nbest, info);
                 // the present form, for the candidate list's entries and for the record
-                if (nbest >> 32) { key = (int64_t)(nbest >> 32); arc = mcf_pack_arc((int32_t)~(uint32_t)nbest, r_lo + (int32_t)((info >> 22) & 0x1ff) * kPer); }
+                if (nbest >> 32) { key = (int64_t)(nbest >> 32); arc = mcf_pack_arc((int32_t)~(uint32_t)nbest, r_lo + (int32_t)((info >> 22) & 0x1ff) * r_step); }
             } else if (reg_plain) {
                 // one LDS round trip for the whole lane: states and potentials of all its register arcs, then selects
-                int32_t st[kReg];
-                int64_t pt[kReg], ph[kReg];
+                auto slots = [&](auto ns) {
+                    constexpr int NS = decltype(ns)::value;
+                    int32_t st[NS];
+                    int64_t pt[NS], ph[NS];
 #pragma unroll
-                for (int k = 0; k < kReg; ++k) {
-                    st[k] = v.state[k < r_n ? r_lo + k * kPer : 0];
-                    pt[k] = v.pi[r_tail[k]];
-                    ph[k] = v.pi[r_head[k]];
-                }
+                    for (int k = 0; k < NS; ++k) {
+                        st[k] = v.state[k < r_n ? r_lo + k * r_step : 0];
+                        pt[k] = v.pi[r_tail[k]];
+                        ph[k] = v.pi[r_head[k]];
+                    }
 #pragma unroll
-                for (int k = 0; k < kReg; ++k) {
-                    const int64_t rc = (int64_t)r_cost[k] + pt[k] - ph[k];
-                    const int32_t s = k < r_n ? st[k] : 0;
-                    const int64_t viol = s > 0 ? -rc : rc;
-                    const int64_t pid = mcf_pack_arc(r_orig[k], r_lo + k * kPer);
-                    if (s != 0 && viol > 0 && mcf_cand_better(viol, pid, key, arc)) { key = viol; arc = pid; }
-                }
-                for (int32_t i = r_lo + kReg * kPer; i < r_hi; i += kPer) small_price_lds<kSweepPlain>(v, rule, devex, i, key, arc);
+                    for (int k = 0; k < NS; ++k) {
+                        const int64_t rc = (int64_t)r_cost[k] + pt[k] - ph[k];
+                        const int32_t s = k < r_n ? st[k] : 0;
+                        const int64_t viol = s > 0 ? -rc : rc;
+                        const int64_t pid = mcf_pack_arc(r_orig[k], r_lo + k * r_step);
+                        if (s != 0 && viol > 0 && mcf_cand_better(viol, pid, key, arc)) { key = viol; arc = pid; }
+                    }
+                };
+                if (r_few) slots(SmallSlots<kRegFew>{});
+                else slots(SmallSlots<kReg>{});
+                for (int32_t i = r_lo + kReg * r_step; i < r_hi; i += r_step) small_price_lds<kSweepPlain>(v, rule, devex, i, key, arc);
             } else {
                 const int32_t lo = s_gran[px][bg0], hi = s_gran[px][bg1];
                 if (sweep == kSweepDevex) for (int32_t i = lo + pl; i < hi; i += kPer) small_price_lds<kSweepDevex>(v, rule, devex, i, key, arc);
