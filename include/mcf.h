@@ -535,6 +535,50 @@ int mcf_add_arcs(mcf_handle* h, int64_t count, const int32_t* tail, const int32_
                  const int64_t* cap, const int8_t* arc_priority /* key_mode 2; may be NULL = 0 */,
                  mcf_arcs_report* out /* may be NULL */);
 
+/* ---- fork a resident handle on the device.  Every edit above consumes the state it starts from; the reference's what-if
+ * loops (examples/sensitivity_analysis_example.py, scenarios 1-3 and 5 of examples/incremental_resolving_example.py) go back
+ * to the same optimum again and again, which on a handle meant a new mcf_create, a full upload and mcf_set_basis' host walk
+ * per what-if.  mcf_fork makes `count` new handles, each a complete copy of src's resident state: every introspection call
+ * (mcf_get_result with all integer fields of mcf_stats, mcf_get_tree, mcf_get_reduced_costs, mcf_get_pricing_keys,
+ * mcf_get_weights, mcf_certify, mcf_cost_ranges) answers for a fork what it answers for src, bit for bit (measured times
+ * aside), and any later sequence of calls makes the same pivots in the same order on a fork as on src -- in every state of
+ * the handle between two solves: fresh, at an iteration limit (mid-solve), optimal, infeasible, unbounded; on every engine
+ * path, tree layout, rule and key_mode; after mcf_update_* and mcf_add_arcs; with dropped reduced costs.
+ *
+ *   what is copied    the control block (status, counters, Devex block cursor, swap count, tuner counts, minor-iteration
+ *                     state, blocked-list arena and allocation cursor), weights and touched-weight list, candidate list and
+ *                     candidate cache, dirty marks, per-workgroup swept counts, both arenas of the blocked list with block
+ *                     records and extents, the coarse index, reduced costs and key codes (or their absence: rc_dropped_at),
+ *                     the run-shape state, arc priorities, and the host image with every host-side field a later call reads.
+ *                     All device arrays of all `count` handles are written by ONE kernel launch over a segment table.
+ *   what is not       scratch every pivot writes before it reads; captured graphs (rebuilt on first use); scratch of the
+ *                     post-solve passes (allocated on first use).  mcf_options.arc_priority of a fork is NULL.  Decisions
+ *                     mcf_create took from environment variables are inherited from src, not read again.
+ *   independence      no device memory, pinned slot, stream of its own, graph or event is shared: destroying src leaves the
+ *                     forks whole and the other way round.  Streams follow mcf_create's rule (pooled for small handles).
+ *   src               is only read, exactly as by mcf_certify (its stream is synchronised first): a later mcf_solve of src
+ *                     makes the same pivots.  A handle driven through mcf_enqueue_* must be quiescent (the caller's part).
+ *
+ * Errors, all before any device work: MCF_E_BAD_ARG (null src / out, count < 0), MCF_E_STATE (shard_count > 1);
+ * count == 0 is MCF_OK and does nothing.  MCF_E_ALLOC / MCF_E_HIP part-way: every handle made by the call is destroyed,
+ * out[0..count) is all NULL, src is untouched; the message through mcf_last_error(NULL), as for mcf_create.
+ *
+ * mcf_restore runs the same copy into handles that already exist, without allocating: each dst[i] must have src's shape --
+ * n, m, padded m, device, rule, key_mode, engine path, tree layout geometry, pricing grid, and which of reduced costs, key
+ * codes, dirty marks, candidate cache and priorities it was created with (mcf_add_arcs keeps the record current) --
+ * otherwise MCF_E_STATE names the field (mcf_last_error(src)) before anything changes.  dst[i] == src, a duplicate or a
+ * NULL entry: MCF_E_BAD_ARG.  Afterwards dst[i] is what a fresh fork of src would be, host image and options included;
+ * its captured graphs are dropped. */
+typedef struct mcf_fork_report {
+    int64_t count;           /* handles written */
+    int64_t segments;        /* device arrays copied per handle */
+    int64_t bytes_per_fork;  /* device bytes copied per handle */
+    double  device_ms;       /* HIP events round the copy launch(es) */
+} mcf_fork_report;
+
+int mcf_fork(mcf_handle* src, int32_t count, mcf_handle** out, mcf_fork_report* report /* may be NULL */);
+int mcf_restore(mcf_handle* const* dst, int32_t count, mcf_handle* src, mcf_fork_report* report /* may be NULL */);
+
 /* ---- certificate on the device (the reference's validate_flow / compute_bottleneck_arcs, utils.py:169-312, plus the dual
  * half the reference never checks).  Conservation, bounds, complementary slackness, the exact objectives and the
  * consistency of the resident basis are evaluated where the data is: one streaming pass over the arcs, one pass over the

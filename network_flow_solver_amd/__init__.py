@@ -33,7 +33,7 @@ from .exceptions import (
     UnboundedProblemError,
 )
 from .simplex import NetworkSimplex
-from .solver import load_problem, save_result, solve_many, solve_min_cost_flow
+from .solver import load_problem, save_result, solve_many, solve_min_cost_flow, solve_scenarios
 from .utils import BottleneckArc, InfeasibleCut, UnboundedRay, ValidationResult, compute_bottleneck_arcs, validate_flow
 
 __all__ = [
@@ -42,6 +42,7 @@ __all__ = [
     "InvalidProblemError", "IterationLimitError", "NetworkSolverError", "NumericalInstabilityError",
     "SolverConfigurationError", "UnboundedProblemError", "NetworkSimplex", "load_problem", "save_result",
     "solve_many",
+    "solve_scenarios",
     "solve_min_cost_flow",
     "BottleneckArc", "ValidationResult", "compute_bottleneck_arcs", "validate_flow", "InfeasibleCut", "UnboundedRay", "SupplyRange",
 ]

@@ -2563,3 +2563,46 @@ MCF_HD McfFrngArc mcf_frng_arc(int32_t state, int64_t cap, int64_t flow, int64_t
     r.rate = rc;
     return r;
 }
+
+// ---- mcf_fork / mcf_restore: the arithmetic of the copy kernel (k_fork in mcf_engine.hip; csrc/mcf_fork_host.cpp runs the
+// same functions from plain loops).  The copy is a list of segments (one device array each) cut into chunks of
+// MCF_FORK_CHUNK bytes = one 16-byte access per lane of a 256-lane workgroup; a work item is (chunk, group of up to
+// MCF_FORK_GROUP destinations): the workgroup loads the chunk once and stores it to every destination of the group from its
+// registers.  Items are dealt to the workgroups by a grid-stride loop, so no length, count or grid size is assumed.
+#define MCF_FORK_THREADS 256
+#define MCF_FORK_CHUNK (MCF_FORK_THREADS * 16)
+#define MCF_FORK_GROUP 8
+struct McfForkSeg {
+    const char* src;     // the source array
+    int64_t bytes;       // its length (any value: the last bytes % 16 are copied byte by byte)
+    int64_t chunk0;      // chunks of the segments before this one
+    int32_t slot;        // the destination array is dst_table[destination * slots + slot]
+    int32_t pad;
+};
+MCF_HD int64_t mcf_fork_chunks(int64_t bytes) { return bytes > 0 ? (bytes + MCF_FORK_CHUNK - 1) / MCF_FORK_CHUNK : 0; }
+MCF_HD int64_t mcf_fork_tail_start(int64_t bytes) { return bytes & ~(int64_t)15; }   // the 16-byte accesses cover [0, this)
+MCF_HD int64_t mcf_fork_groups(int64_t count) { return (count + MCF_FORK_GROUP - 1) / MCF_FORK_GROUP; }
+MCF_HD int64_t mcf_fork_items(int64_t total_chunks, int64_t count) { return total_chunks * mcf_fork_groups(count); }
+// item -> (chunk, first and one-past-last destination): consecutive items are consecutive chunks of one destination group
+MCF_HD void mcf_fork_item(int64_t item, int64_t total_chunks, int64_t count, int64_t* chunk, int64_t* d_lo, int64_t* d_hi) {
+    const int64_t g = item / total_chunks;
+    *chunk = item - g * total_chunks;
+    *d_lo = g * MCF_FORK_GROUP;
+    *d_hi = (g + 1) * MCF_FORK_GROUP < count ? (g + 1) * MCF_FORK_GROUP : count;
+}
+// the segment that holds `chunk` (chunk < total): the last one whose chunk0 <= chunk among those that have chunks at all
+MCF_HD int32_t mcf_fork_find(const McfForkSeg* seg, int32_t nseg, int64_t chunk) {
+    int32_t lo = 0, hi = nseg - 1;
+    while (lo < hi) {   // invariant: the answer lies in [lo, hi]
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (seg[mid].chunk0 <= chunk) lo = mid; else hi = mid - 1;
+    }
+    return lo;   // (never an empty segment: one shares its chunk0 with the segment after it, and the search takes the last)
+}
+// What lane `lane` copies of chunk `k` of a segment of `bytes` bytes: *vec = byte offset of its 16-byte access or -1,
+// *tail = offset of its single byte or -1.  The tail [mcf_fork_tail_start, bytes) belongs to the last chunk's first lanes.
+MCF_HD void mcf_fork_lane(int64_t bytes, int64_t k, int32_t lane, int64_t* vec, int64_t* tail) {
+    const int64_t off = k * MCF_FORK_CHUNK + (int64_t)lane * 16, t0 = mcf_fork_tail_start(bytes);
+    *vec = off + 16 <= t0 ? off : -1;
+    *tail = (k == mcf_fork_chunks(bytes) - 1 && t0 + lane < bytes) ? t0 + lane : -1;
+}

@@ -2553,6 +2553,39 @@ __global__ void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
 }
 
+// ------------------------------------------------------------------ k_fork: the device copy of mcf_fork / mcf_restore
+// One launch writes every state array of every destination handle: a grid-stride loop over (chunk, destination group)
+// items (mcf_core.h: mcf_fork_*).  A chunk is read once -- 16 bytes per lane, the last bytes % 16 of a segment one byte per
+// lane -- and stored from registers to up to MCF_FORK_GROUP destinations, so that `count` forks read the source about
+// count / MCF_FORK_GROUP times (from L2 after the first) instead of count times.  NT: non-temporal stores, for copies larger
+// than the Infinity Cache, whose lines nobody reads again before they are evicted (chosen by size, MCF_FORK_NT = 0 / 1 forces;
+// measured: profiles/fork_scenarios.txt).
+typedef unsigned int fork_u32x4 __attribute__((ext_vector_type(4)));
+template <bool NT>
+__global__ __launch_bounds__(MCF_FORK_THREADS) void k_fork(const McfForkSeg* __restrict__ seg, int32_t nseg, int64_t total_chunks,
+                                                           char* const* __restrict__ dst_table, int64_t count) {
+    const int64_t items = mcf_fork_items(total_chunks, count);
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        int64_t chunk, d_lo, d_hi;
+        mcf_fork_item(item, total_chunks, count, &chunk, &d_lo, &d_hi);
+        const int32_t si = mcf_fork_find(seg, nseg, chunk);   // (uniform per workgroup)
+        const McfForkSeg sg = seg[si];
+        int64_t vec, tail;
+        mcf_fork_lane(sg.bytes, chunk - sg.chunk0, (int32_t)threadIdx.x, &vec, &tail);
+        if (vec >= 0) {
+            const fork_u32x4 x = *reinterpret_cast<const fork_u32x4*>(sg.src + vec);
+            for (int64_t d = d_lo; d < d_hi; ++d) {
+                fork_u32x4* q = reinterpret_cast<fork_u32x4*>(dst_table[d * nseg + sg.slot] + vec);
+                if (NT) __builtin_nontemporal_store(x, q); else *q = x;
+            }
+        }
+        if (tail >= 0) {
+            const char x = sg.src[tail];
+            for (int64_t d = d_lo; d < d_hi; ++d) dst_table[d * nseg + sg.slot][tail] = x;
+        }
+    }
+}
+
 #include "mcf_passes_dev.h"
 
 }  // namespace
@@ -2599,6 +2632,18 @@ struct mcf_handle {
     McfCtx* h_ctx = nullptr;   // pinned
     McfCand* h_one = nullptr;  // pinned
     McfView view{};
+    // Every device array of the solver state, recorded by the one place that allocates them (alloc_wire); mcf_add_arcs keeps the
+    // lengths current.  mcf_fork / mcf_restore copy the `state` ones and compare the lengths; the others are scratch that every
+    // pivot writes before it reads.
+    struct DevArray { void** field; size_t bytes; bool state; const char* name; };
+    std::vector<DevArray> arrays;
+    bool scan_ok = false, want_vkey = false, want_dirty = false, want_candx = false;   // what decide_geometry chose
+    bool rc_partial = false;
+    int32_t key_mode = 0;        // McfView::key_mode as decided from the options
+    // what mcf_restore compares: every value that decides which arrays exist and how long they are (shape_of; the array
+    // lengths themselves are compared from `arrays`)
+    std::vector<std::pair<const char*, int64_t>> shape;
+    bool dx_filled = false;      // the Devex granule table was uploaded (once)
     int price_blocks = 1;
     int apply_blocks = 1;
     int32_t climb_budget = INT32_MAX;  // round trips the cycle climb may take before the scan takes over
@@ -2905,16 +2950,15 @@ int upload_image(mcf_handle* h) {
         if (dalloc(&h->d_full_tab, MCF_NUM_BUCKETS * 2) != hipSuccess) { h->err = "hipMalloc slice table"; return MCF_E_ALLOC; }
         HIP_TRY(h, hipMemcpy(h->d_full_tab, tab, sizeof tab, hipMemcpyHostToDevice));
     }
-    if (h->opt.rule == MCF_RULE_DEVEX_BLOCK && !h->d_dx) {  // granule table, once
+    if (h->d_dx && !h->dx_filled) {  // granule table, once
         McfDevex* dx = new (std::nothrow) McfDevex();
         if (!dx) { h->err = "host allocation"; return MCF_E_ALLOC; }
         std::memset(dx, 0, sizeof *dx);
         mcf_devex_fill_granules(dx, im.bucket_off);
-        hipError_t de = dalloc(&h->d_dx, 1);
-        if (de == hipSuccess) de = hipMemcpy(h->d_dx, dx, sizeof *dx, hipMemcpyHostToDevice);
+        const hipError_t de = hipMemcpy(h->d_dx, dx, sizeof *dx, hipMemcpyHostToDevice);
         delete dx;
-        if (de != hipSuccess) { h->err = "hipMalloc / copy granule table"; return MCF_E_ALLOC; }
-        h->view.dx = h->d_dx;
+        if (de != hipSuccess) { h->err = "copy granule table"; return MCF_E_HIP; }
+        h->dx_filled = true;
     }
     HIP_TRY(h, hipMemcpyAsync(h->d_ctx, h->h_ctx, sizeof(McfCtx), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -3247,9 +3291,542 @@ bool small_reserve(int device, uint32_t total) {
     return true;
 }
 
+// ====================================================================== mcf_create in three parts
+// decide_geometry: everything that decides which arrays exist, how long they are and which kernels run, from the image and
+// the options (and the environment's A/B switches);  alloc_wire: the one place that allocates the solver's device arrays
+// and wires McfView;  upload_image (above): the start state.  mcf_fork runs alloc_wire on a copy of the source's image,
+// options and geometry (inherit_geometry: nothing is read from the environment again) and a device copy in place of the upload.
+std::vector<std::pair<const char*, int64_t>> shape_of(const mcf_handle* h) {
+    return {{"n", h->im.n}, {"m", h->im.m}, {"padded m", h->im.m_pad}, {"device", h->device}, {"rule", h->opt.rule}, {"key_mode", h->key_mode},
+            {"engine path (fused LDS loop)", h->small}, {"fused loop width", h->small_threads}, {"engine path (persistent mid loop)", h->mid},
+            {"tree layout", h->bpl}, {"tree block shift", h->bpl_shift}, {"tree blocks", h->bpl_cap}, {"dense tree blocks", h->bpl_dense},
+            {"tree update grid", h->bpl_grid}, {"cycle scan", h->scan_ok}, {"resident reduced costs", h->rc_able}, {"key codes", h->want_vkey},
+            {"dirty marks", h->want_dirty}, {"candidate cache", h->want_candx}, {"arc priorities", h->d_prio != nullptr},
+            {"pricing grid", h->price_blocks}, {"apply grid", h->apply_blocks}, {"reduced-cost update grid", h->rcupd_blocks},
+            {"overlapped graphs", h->overlap_cfg}, {"shard_count", h->shards}, {"own stream", h->stream_owned}};
+}
+
+void decide_geometry(mcf_handle* h) {
+    const McfHostImage& im = h->im;
+    const mcf_options& opt = h->opt;
+    const int64_t m = im.m;
+    {
+        // Tree layout: the blocked preorder list (mcf_core.h) from kBplMinNodes nodes on -- below that the dense array's block
+        // permutation moves few enough positions, and the persistent loops keep the dense array anyway.
+        // tree_blocks: 0 = auto, -1 = dense array, k >= 2 = blocks of 2^k slots;  tree_pool: spare blocks (0 = auto, -1 = none).
+        const bool forced = opt.tree_blocks > 0, never = opt.tree_blocks < 0;
+        h->bpl = !never && opt.mid_loop <= 0 && opt.overlap_update <= 0 && (forced || im.n_nodes >= kBplMinNodes);
+        if (h->bpl) {
+            int32_t sh = 0, cap = 0, dense = 0;
+            mcf_bpl_geometry(im.n_nodes, forced ? opt.tree_blocks : 0, opt.tree_pool, &sh, &cap, &dense);
+            h->bpl_shift = sh; h->bpl_cap = cap; h->bpl_dense = dense;
+            // (a large grid costs dispatch time on every pivot: 1 M / 16 M, 256 -> 64 workgroups: k_update_bpl 7.5 -> 6.0 us, +4 % pivots/s)
+            int g = (cap + 7) / 8;
+            if (g > 64) g = 64;
+            if (const char* ge = std::getenv("MCF_BPL_GRID")) { const int vv = std::atoi(ge); if (vv >= 1 && vv <= 4096) g = vv; }   // A/B switch
+            if (g < 1) g = 1;
+            while ((cap + g - 1) / g > kBplTouchedCap) g *= 2;
+            h->bpl_grid = g;
+        }
+    }
+    {
+        // 8 * k workgroups, one group of k per XCD head bucket (formula shared with the CPU emulation)
+        h->price_blocks = mcf_price_blocks(m, h->shards, opt.price_blocks);
+        const int64_t ab = ((int64_t)im.n_nodes + kApplyThreads - 1) / kApplyThreads;
+        int max_ab = kMaxApplyBlocks;
+        if (const char* ab_env = std::getenv("MCF_APPLY_BLOCKS")) { const int vv = std::atoi(ab_env); if (vv >= 64 && vv <= 4096) max_ab = vv; }   // A/B switch
+        h->apply_blocks = (int)(ab < max_ab ? ab : max_ab);
+    }
+    h->stream_owned = im.n > kPooledMaxNodes;
+    h->key_mode = opt.key_mode > 0 ? opt.key_mode : (opt.forward_first ? MCF_KEY_FORWARD_FIRST : MCF_KEY_PLAIN);
+    // the fused small-instance path: its LDS plan, and the kernels' dynamic-LDS limit raised to it (refused: the three-kernel GPU path)
+    h->small = !h->bpl && !opt.no_fused && !opt.profile && h->shards == 1 &&
+               small_plan(im.m_pad, im.arcw.size(), im.n_nodes, opt.rule == MCF_RULE_DEVEX_BLOCK, &h->small_layout) &&
+               small_reserve(h->device, h->small_layout.total);
+    if (h->small) { h->small_threads = small_threads_for(im.n_nodes, opt.rule); h->small_narrow_ok = small_narrow_allowed(); }
+    // position-space subtree sizes for the cycle scan: every handle but the LDS-resident ones
+    h->scan_ok = opt.cycle_scan >= 0 && im.n_nodes <= kScanMaxNodes && !h->small;  // -1: never scan
+    // cycle search: how many round trips the one-lane climb takes before the workgroup-wide scan over
+    // preorder positions finishes the cycle.  Auto = none: measured on MI355X (profiles/r01_f_*), scanning
+    // at once beats every hybrid from 256 to 65 536 nodes -- a dependent global round trip per tree level
+    // costs more than the whole scan's ~4 -- by 1.1x (netgen_8_08a) to 4.5x (goto_8_16a, cycles of ~450 arcs).
+    if (!h->scan_ok && !(h->bpl && opt.cycle_scan >= 0)) h->climb_budget = INT32_MAX;
+    else if (opt.cycle_scan > 0) h->climb_budget = opt.cycle_scan - 1;
+    else h->climb_budget = 0;
+    // resident reduced costs for everything that does not take the fused LDS path
+    h->rcached = !h->small && !opt.no_rcache && im.m > 0;
+    h->rc_able = h->rcached;
+    // a rank patches only the reduced costs it sweeps -- for the rules whose sweeps cover a FIXED share of every bucket.
+    // Devex cuts the block first and the shard second (so that the union over ranks does not depend on the rank
+    // count), and blocks move and resize: there every rank keeps all reduced costs exact, as a single GPU does.
+    h->rc_partial = h->rcached && h->shards > 1 && opt.rule != MCF_RULE_DEVEX_BLOCK;
+    if (h->rcached) {
+        const int64_t rb = ((int64_t)im.n_nodes + 15) / 16;  // one 16-lane group per node of the largest possible T2
+        int max_rb = kMaxRcupdBlocks;
+        if (const char* re = std::getenv("MCF_RCUPD_BLOCKS")) { const int vv = std::atoi(re); if (vv >= 1 && vv <= 4096) max_rb = vv; }   // A/B switch
+        h->rcupd_blocks = (int)(rb < max_rb ? (rb > 0 ? rb : 1) : max_rb);
+    }
+    // persistent single-workgroup loop: the tree work of one pivot must be small enough for one CU, and so must
+    // the arcs it prices per pivot (a Devex block / the whole arc list for Dantzig; the candidate list's full
+    // sweeps stay on the grid)
+    {
+        int64_t per_pivot_arcs = 0;
+        if (opt.rule == MCF_RULE_DEVEX_BLOCK) {
+            McfCtx probe;  // the largest block the tuner may grow to (mcf_core.h: never beyond MCF_TUNER_MAX_ARCS or the initial size)
+            std::memset(&probe, 0, sizeof probe);
+            mcf_init_block_state(&probe, opt.rule, im.m, opt.block_size);
+            per_pivot_arcs = im.m * probe.max_granules / MCF_GRANULES;
+        } else if (opt.rule == MCF_RULE_DANTZIG_FULL) {
+            per_pivot_arcs = im.m;
+        }
+        // (the candidate list never gains from the loop -- its full sweeps run on the grid either way -- and stays on the graph)
+        const bool fits = im.n_nodes <= kMidMaxNodes && per_pivot_arcs <= kMidMaxArcsPerPivot && opt.rule != MCF_RULE_CANDIDATE_LIST;
+        h->mid = !h->bpl && h->rcached && h->scan_ok && h->shards == 1 && !opt.profile && opt.mid_loop >= 0 && (fits || opt.mid_loop > 0);
+    }
+    // overlapped graphs (build_graph), on request only: the idea -- on large trees the permutation outlasts the reduced-cost
+    // patch, so the next pricing could hide beside it -- loses to the cost of the two cross-queue edges per pivot
+    // (netgen_8_14a 55 K -> 33 K pivots/s, 1 M / 16 M 26 K -> 22 K; profiles/r02_ab_overlapped_graph.txt)
+    {
+        const bool able = !h->bpl && h->rcached && !h->small && !h->mid && h->shards == 1 && !opt.profile && opt.rule != MCF_RULE_CANDIDATE_LIST;
+        h->overlap = able && opt.overlap_update > 0;
+        h->overlap_cfg = h->overlap;
+    }
+    // compressed Dantzig keys for the grid sweeps of the Dantzig / candidate-list rules (4 B per arc instead of 9)
+    // They pay where a sweep reads the whole shard and is bandwidth-bound: full (non-incremental) sweeps of the Dantzig rule
+    // from kIncrementalMinArcs arcs on (1 M / 16 M: sweep 24 -> 14 us).  Keeping the codes exact costs the reduced-cost patch a state
+    // byte and a 4-byte store per patched arc (k_update +1..3 us per pivot), which a candidate-list handle (one sweep per ~33
+    // pivots) or an incremental sweep (1 % of the arcs re-read per pivot) never earns back.  compressed_keys: 1 = on, -1 = off.
+    const bool keys_auto = opt.rule == MCF_RULE_DANTZIG_FULL && opt.full_sweeps > 0 && im.m >= kIncrementalMinArcs;
+    h->want_vkey = h->rcached && !h->mid && opt.rule != MCF_RULE_DEVEX_BLOCK && h->key_mode == MCF_KEY_PLAIN &&
+                   (opt.compressed_keys > 0 || (opt.compressed_keys == 0 && keys_auto));
+    if (h->want_vkey) {
+        const char* nt_env = std::getenv("MCF_NT_SWEEP");   // A/B switch: 0 / 1 force, unset = by size
+        h->nt_sweep = nt_env ? nt_env[0] == '1' : (im.m_pad / (h->shards > 0 ? h->shards : 1)) * 4 > (int64_t)200 * 1024 * 1024;
+    }
+    // incremental pricing for the rules whose sweeps cover the whole shard (Dantzig, candidate list); not for the
+    // persistent loop, whose instances are far too small for it (its kernel compiles the marking away)
+    // (auto: only where a sweep is a large part of a pivot -- below ~4 M arcs the flag look-up in front of every
+    // sweep and the marking in k_update cost more than the skipped blocks save: netgen_8_14a 52.7 K -> 46.7 K pivots/s;
+    // at 16 M arcs: 23.9 K -> 37 K)
+    h->want_dirty = h->rcached && !h->mid && opt.rule != MCF_RULE_DEVEX_BLOCK && (opt.full_sweeps < 0 || (opt.full_sweeps == 0 && im.m >= kIncrementalMinArcs));
+    // candidate cache: the grid path of the candidate-list rule on one GPU, keys that need nothing but the reduced cost
+    h->want_candx = opt.rule == MCF_RULE_CANDIDATE_LIST && h->shards == 1 && !h->small && !h->mid && !opt.profile && h->key_mode <= MCF_KEY_FORWARD_FIRST &&
+                    h->price_blocks <= 2 * kPivotThreads && !std::getenv("MCF_NO_CANDX");
+    // pivots back to back (k_pivot_run): candidate-list handles on the blocked list that keep the candidate cache
+    h->run_pairs_cfg = 0;
+    // Opt-in: measured at 1M/16M (first 300 K pivots, same box) 30.9-35.7 K pivots/s in the run shape against 41.1 K in the
+    // pivot+update pair shape -- one workgroup's phase A over 8-20 K blocks costs more than the launches it saves.
+    const char* run_env = std::getenv("MCF_PIVOT_RUN");
+    const int want_run = opt.pivot_run > 0 ? opt.pivot_run : (run_env ? std::atoi(run_env) : 0);
+    if (h->bpl && h->want_candx && want_run > 0 && opt.use_graph && !std::getenv("MCF_NO_RUN")) h->run_pairs_cfg = want_run;
+    h->run_pairs = h->run_pairs_cfg;
+    {
+        // auto: candidate lists (one sweep per ~33 pivots) on large instances (from 100 000 nodes: measured at 1 M / 16 M) from an
+        // average |T2| of 384 nodes, Devex there from 1 500; never for the Dantzig rule, whose every pivot sweeps all arcs, for
+        // shards (their driver owns the launches) or the persistent loops.  rc_drop: -1 = never, k > 0 = that threshold.
+        int64_t thr = 0;
+        if (h->rcached && !h->mid && !h->small && h->shards == 1 && opt.key_mode == 0 && !opt.forward_first) {
+            if (opt.rc_drop > 0) thr = opt.rc_drop;
+            else if (opt.rc_drop == 0 && im.n_nodes >= 100000)
+                // (Devex block search sweeps one block per pivot: the dearer sweep is paid every time, so it waits for larger
+                //  subtrees -- 1 M / 16 M: 139.8 s without, 134.0 / 134.8 s with a threshold of 1 500 / 384)
+                thr = opt.rule == MCF_RULE_CANDIDATE_LIST ? 384 : (opt.rule == MCF_RULE_DEVEX_BLOCK ? 1500 : 0);
+            if (opt.rule == MCF_RULE_DANTZIG_FULL) thr = 0;
+        }
+        if (const char* env = std::getenv("MCF_RC_DROP")) { const long vv = std::atol(env); thr = vv > 0 ? vv : 0; }   // A/B switch
+        h->rc_drop_subtree = h->rcached && h->shards == 1 ? thr : 0;
+    }
+}
+
+// the geometry of `src` as it stands (mcf_add_arcs keeps the pricing grid and grows the LDS plan), for a handle of its image
+void inherit_geometry(mcf_handle* h, const mcf_handle* src) {
+    h->bpl = src->bpl; h->bpl_shift = src->bpl_shift; h->bpl_cap = src->bpl_cap; h->bpl_dense = src->bpl_dense; h->bpl_grid = src->bpl_grid;
+    h->price_blocks = src->price_blocks; h->apply_blocks = src->apply_blocks; h->rcupd_blocks = src->rcupd_blocks;
+    h->stream_owned = h->im.n > kPooledMaxNodes;
+    h->key_mode = src->key_mode;
+    h->small = src->small; h->small_threads = src->small_threads; h->small_narrow_ok = src->small_narrow_ok; h->small_layout = src->small_layout;
+    h->scan_ok = src->scan_ok; h->climb_budget = src->climb_budget;
+    h->rc_able = src->rc_able; h->rcached = src->rc_able; h->rc_partial = src->rc_partial;
+    h->mid = src->mid;
+    h->overlap_cfg = src->overlap_cfg; h->overlap = src->overlap_cfg;
+    h->want_vkey = src->want_vkey; h->nt_sweep = src->nt_sweep; h->want_dirty = src->want_dirty; h->want_candx = src->want_candx;
+    h->run_pairs_cfg = src->run_pairs_cfg; h->run_pairs = src->run_pairs_cfg;
+    h->rc_drop_subtree = src->rc_drop_subtree;
+}
+
+template <typename T>
+hipError_t take(mcf_handle* h, T** field, size_t count, const char* name, bool state) {
+    const hipError_t e = dalloc(field, count);
+    if (e == hipSuccess) h->arrays.push_back({reinterpret_cast<void**>(field), count * sizeof(T), state, name});
+    return e;
+}
+
+// a handle that captures graphs needs a stream nobody else captures on: only the persistent-loop paths that launch plain
+// kernels keep a borrowed stream
+hipError_t own_stream_if_captured(mcf_handle* h) {
+    if (h->stream_owned || h->small || (h->mid && h->opt.rule != MCF_RULE_CANDIDATE_LIST)) return hipSuccess;
+    hipStream_t own = nullptr;
+    const hipError_t e = hipStreamCreateWithFlags(&own, hipStreamNonBlocking);
+    if (e != hipSuccess) return e;
+    h->stream = own;
+    h->stream_owned = true;
+    return hipSuccess;
+}
+
+// Part two.  from_image: mcf_create -- the arrays that never change after creation (adjacency, priorities, the header of the
+// incremental sweeps) are filled from the host and the ones a kernel may read before it writes are cleared; otherwise
+// (mcf_fork) the device copy fills every state array.  State arrays (copied by a fork) and scratch are told apart here:
+// scratch is what every pivot writes before it reads -- the two cycle sides and their records (path, ppos, rec), the
+// permutation's segment table (seg) and the list of shrunken subtrees (chg) are written by the pivot's walk / finish and
+// consumed by the same pivot's update; cand_aux and one are the buffers of mcf_price_once and the read-back of one candidate.
+// On failure the caller frees the handle (free_all); *what names the step.
+hipError_t alloc_wire(mcf_handle* h, bool from_image, const char** what) {
+    const McfHostImage& im = h->im;
+    const mcf_options& opt = h->opt;
+    hipError_t e;
+#define ALLOC_TRY(step, expr) do { if ((e = (expr)) != hipSuccess) { *what = step; return e; } } while (0)
+    ALLOC_TRY("hipStreamCreate", h->stream_owned ? hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) : pool_stream(h->device, &h->stream));
+    const size_t N = im.n_nodes;
+    const bool S = true, X = false;   // state / scratch
+    ALLOC_TRY("hipMalloc tail", take(h, &h->d_tail, im.m_pad, "tail", S));
+    ALLOC_TRY("hipMalloc head", take(h, &h->d_head, im.m_pad, "head", S));
+    ALLOC_TRY("hipMalloc cost", take(h, &h->d_cost, im.m_pad, "cost", S));
+    ALLOC_TRY("hipMalloc orig", take(h, &h->d_orig, im.m_pad, "orig", S));
+    ALLOC_TRY("hipMalloc state", take(h, &h->d_state, im.m_pad, "state", S));
+    ALLOC_TRY("hipMalloc weight", take(h, &h->d_weight, im.m_pad, "weight", S));
+    ALLOC_TRY("hipMalloc arcw", take(h, &h->d_arcw, im.arcw.size(), "arcw", S));
+    ALLOC_TRY("hipMalloc pi", take(h, &h->d_pi, N, "pi", S));
+    ALLOC_TRY("hipMalloc node", take(h, &h->d_node, N, "node", S));
+    const size_t bpl_slots = h->bpl ? ((size_t)h->bpl_cap << h->bpl_shift) + 4 : 0;   // slots per arena (+4: groups of four)
+    // (+4: the cycle scan reads the nodes in aligned groups of four, like the sizes)
+    ALLOC_TRY("hipMalloc order", take(h, &h->d_order0, h->bpl ? bpl_slots : N + 4, "order0", S));
+    ALLOC_TRY("hipMalloc order", take(h, &h->d_order1, h->bpl ? bpl_slots : N + 4, "order1", S));
+    ALLOC_TRY("hipMalloc pos", take(h, &h->d_pos0, N, "pos0", S));
+    ALLOC_TRY("hipMalloc pos", take(h, &h->d_pos1, h->bpl ? 1 : N, "pos1", S));
+    ALLOC_TRY("hipMalloc path", take(h, &h->d_path1, N, "path1", X));
+    ALLOC_TRY("hipMalloc path", take(h, &h->d_path2, N, "path2", X));
+    ALLOC_TRY("hipMalloc path", take(h, &h->d_ppos1, h->bpl ? 2 * N : N, "ppos1", X));   // (blocked list: positions, then slots)
+    ALLOC_TRY("hipMalloc path", take(h, &h->d_ppos2, h->bpl ? 2 * N : N, "ppos2", X));
+    ALLOC_TRY("hipMalloc rec", take(h, &h->d_rec1, N, "rec1", X));
+    ALLOC_TRY("hipMalloc rec", take(h, &h->d_rec2, N, "rec2", X));
+    ALLOC_TRY("hipMalloc seg", take(h, &h->d_seg, 2 * N + 2, "seg", X));
+    ALLOC_TRY("hipMalloc ctx", take(h, &h->d_ctx, 1, "ctx", S));
+    ALLOC_TRY("hipMalloc cand", take(h, &h->d_cand, kMaxPriceBlocks, "cand", S));
+    ALLOC_TRY("hipMalloc cand", take(h, &h->d_cand_aux, kMaxPriceBlocks, "cand_aux", X));
+    if (from_image) ALLOC_TRY("hipMemset cand", hipMemset(h->d_cand, 0xff, kMaxPriceBlocks * sizeof(McfCand)));
+    ALLOC_TRY("hipMalloc one", take(h, &h->d_one, 1, "one", X));
+    ALLOC_TRY("hipMalloc swept", take(h, &h->d_swept, kMaxPriceBlocks, "swept", S));
+    {   // pinned: the control block's host copy and the one-candidate read-back buffer (one pooled slot)
+        char* slot = nullptr;
+        ALLOC_TRY("hipHostMalloc", pinned_take(&slot));
+        h->h_ctx = reinterpret_cast<McfCtx*>(slot);
+        h->h_one = reinterpret_cast<McfCand*>(slot + ((sizeof(McfCtx) + 63) & ~(size_t)63));
+    }
+
+    McfView& v = h->view;
+    v.n_nodes = im.n_nodes;
+    v.m = im.m;
+    v.tail = h->d_tail; v.head = h->d_head; v.cost = h->d_cost; v.orig = h->d_orig; v.state = h->d_state;
+    for (int x = 0; x <= MCF_NUM_BUCKETS; ++x) v.bucket_off[x] = im.bucket_off[x];
+    v.weight = opt.rule == MCF_RULE_DEVEX_BLOCK ? h->d_weight : nullptr;
+    v.dx = nullptr;
+    if (opt.rule == MCF_RULE_DEVEX_BLOCK) {   // granule table + touched-weight list (the table is filled by upload_image, once)
+        ALLOC_TRY("hipMalloc granule table", take(h, &h->d_dx, 1, "devex", S));
+        v.dx = h->d_dx;
+    }
+    // key variant of the Dantzig / candidate-list sweep (the reference's specialised entering rules, mcf_core.h: mcf_dantzig_key)
+    v.key_mode = h->key_mode;
+    v.prio = nullptr;
+    if (v.key_mode == MCF_KEY_PRIORITY) {
+        ALLOC_TRY("hipMalloc priority", take(h, &h->d_prio, im.m_pad, "priority", S));
+        if (from_image) {
+            std::vector<int8_t> pr((size_t)im.m_pad, 0);   // the caller's order -> engine order
+            for (int64_t i = 0; i < im.m; ++i) pr[(size_t)i] = (int8_t)(opt.arc_priority[im.orig[(size_t)i]] & 3);
+            ALLOC_TRY("hipMemcpy priority", hipMemcpy(h->d_prio, pr.data(), pr.size(), hipMemcpyHostToDevice));
+        }
+        v.prio = h->d_prio;
+    }
+    v.arcw = h->d_arcw; v.pi = h->d_pi; v.node = h->d_node;
+    v.order[0] = h->d_order0; v.order[1] = h->d_order1;
+    v.posbuf[0] = h->d_pos0; v.posbuf[1] = h->d_pos1;
+    v.psz[0] = nullptr; v.psz[1] = nullptr;
+    v.reach = nullptr; v.chg = nullptr;
+    v.path1 = h->d_path1; v.path2 = h->d_path2; v.ppos1 = h->d_ppos1; v.ppos2 = h->d_ppos2; v.rec1 = h->d_rec1; v.rec2 = h->d_rec2; v.seg = h->d_seg; v.ctx = h->d_ctx;
+
+    v.bmeta[0] = v.bmeta[1] = nullptr; v.bext[0] = v.bext[1] = nullptr; v.blk_shift = 0; v.blk_cap = 0; v.ncandx = 0; v.candx = nullptr;
+    if (h->bpl) {
+        // the two slot arenas (sizes; node ids are d_order0/1), the block records (two copies) and extents (one per arena),
+        // and the scratch the scan spills flagged blocks to
+        ALLOC_TRY("hipMalloc psz", take(h, &h->d_psz0, bpl_slots, "psz0", S));
+        ALLOC_TRY("hipMalloc psz", take(h, &h->d_psz1, bpl_slots, "psz1", S));
+        if (from_image) { ALLOC_TRY("hipMemset psz", hipMemset(h->d_psz0, 0, bpl_slots * 4)); ALLOC_TRY("hipMemset psz", hipMemset(h->d_psz1, 0, bpl_slots * 4)); }
+        for (int a = 0; a < 2; ++a) {
+            ALLOC_TRY("hipMalloc block records", take(h, &h->d_bmeta[a], (size_t)h->bpl_cap + 2, a ? "bmeta1" : "bmeta0", S));
+            ALLOC_TRY("hipMalloc block extents", take(h, &h->d_bext[a], (size_t)h->bpl_cap, a ? "bext1" : "bext0", S));
+            v.bmeta[a] = h->d_bmeta[a]; v.bext[a] = h->d_bext[a];
+        }
+        const size_t nchg = std::max(N, 2 * (size_t)h->bpl_cap + 2);
+        ALLOC_TRY("hipMalloc chg", take(h, &h->d_chg, nchg, "chg", X));
+        v.psz[0] = h->d_psz0; v.psz[1] = h->d_psz1;
+        v.chg = h->d_chg;
+        v.blk_shift = h->bpl_shift; v.blk_cap = h->bpl_cap;
+    } else if (h->scan_ok) {
+        const size_t NP = (N + MCF_REACH_BLOCK - 1) / MCF_REACH_BLOCK * MCF_REACH_BLOCK + 4;  // whole coarse blocks (+4: groups of four)
+        ALLOC_TRY("hipMalloc psz", take(h, &h->d_psz0, NP, "psz0", S));
+        ALLOC_TRY("hipMalloc psz", take(h, &h->d_psz1, NP, "psz1", S));
+        if (from_image) { ALLOC_TRY("hipMemset psz", hipMemset(h->d_psz0, 0, NP * 4)); ALLOC_TRY("hipMemset psz", hipMemset(h->d_psz1, 0, NP * 4)); }
+        v.psz[0] = h->d_psz0; v.psz[1] = h->d_psz1;
+        ALLOC_TRY("hipMalloc reach", take(h, &h->d_reach, NP / MCF_REACH_BLOCK + 8, "reach", S));   // (+8: read four at a time)
+        if (from_image) ALLOC_TRY("hipMemset reach", hipMemset(h->d_reach, 0, (NP / MCF_REACH_BLOCK + 8) * 4));
+        ALLOC_TRY("hipMalloc chg", take(h, &h->d_chg, N, "chg", X));
+        v.reach = h->d_reach; v.chg = h->d_chg;
+    }
+    if (h->rc_able) {
+        if (from_image) mcf_build_rcache(h->im, h->rc_partial ? h->shard : 0, h->rc_partial ? h->shards : 1);
+        v.rc_partial = h->rc_partial ? 1 : 0;
+        ALLOC_TRY("hipMalloc rcache", take(h, &h->d_rcache, im.m_pad, "rcache", S));
+        ALLOC_TRY("hipMalloc adj_off", take(h, &h->d_adj_off, im.adj_off.size(), "adj_off", S));
+        // (the image gives its adjacency up once it is on the device: its length is 2 m either way)
+        ALLOC_TRY("hipMalloc adj", take(h, &h->d_adj, from_image ? im.adj.size() : (size_t)(2 * im.m), "adj", S));
+        if (from_image) {
+            ALLOC_TRY("copy adj_off", hipMemcpy(h->d_adj_off, im.adj_off.data(), im.adj_off.size() * 8, hipMemcpyHostToDevice));
+            ALLOC_TRY("copy adj", hipMemcpy(h->d_adj, im.adj.data(), im.adj.size() * 8, hipMemcpyHostToDevice));
+            h->im.adj.clear(); h->im.adj.shrink_to_fit();  // the device copy is the only one needed from here on
+        }
+        v.rcache = h->d_rcache; v.adj_off = h->d_adj_off; v.adj = h->d_adj;
+    } else {
+        v.rcache = nullptr; v.adj_off = nullptr; v.adj = nullptr; v.rc_partial = 0;
+    }
+    if (h->overlap_cfg) ALLOC_TRY("hipStreamCreate", hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
+    v.vkey = nullptr;
+    v.vk_bigm = im.big_m;
+    v.vk_half = 1 << (opt.vkey_half_log2 > 0 && opt.vkey_half_log2 <= 28 ? opt.vkey_half_log2 : 28);
+    if (h->want_vkey) {
+        ALLOC_TRY("hipMalloc vkey", take(h, &h->d_vkey, im.m_pad, "vkey", S));
+        v.vkey = h->d_vkey;
+    }
+    v.dirty = nullptr;
+    if (h->want_dirty) {
+        static_assert(MCF_MAX_PRICE_BLOCKS == kMaxPriceBlocks, "flag array size");
+        ALLOC_TRY("hipMalloc dirty", take(h, &h->d_dirty, 1, "dirty", S));
+        if (from_image) {
+            McfDirty head;  // (the flags are raised by upload_image)
+            head.nlb = h->price_blocks / MCF_NUM_BUCKETS;
+            for (int x = 0; x < MCF_NUM_BUCKETS; ++x) {
+                int64_t lo, hi;
+                mcf_bucket_slice(im.bucket_off, x, h->shard, h->shards, 0, 1, &lo, &hi);
+                head.lo[x] = (int32_t)lo; head.hi[x] = (int32_t)hi;
+            }
+            ALLOC_TRY("copy dirty", hipMemcpy(h->d_dirty, &head, offsetof(McfDirty, flag), hipMemcpyHostToDevice));
+        }
+        v.dirty = h->d_dirty;
+    }
+    v.candx = nullptr; v.ncandx = 0;
+    if (h->want_candx) {
+        ALLOC_TRY("hipMalloc candidate records", take(h, &h->d_candx, kMaxPriceBlocks, "candx", S));
+        if (from_image) ALLOC_TRY("hipMemset candidate records", hipMemset(h->d_candx, 0xff, kMaxPriceBlocks * sizeof(McfCandX)));
+        v.candx = h->d_candx; v.ncandx = h->price_blocks;
+    }
+#undef ALLOC_TRY
+    return hipSuccess;
+}
+
 }  // namespace
 
 #include "mcf_passes_host.h"
+
+// ====================================================================== mcf_fork / mcf_restore (include/mcf.h)
+namespace {
+
+// The host half of a fork: every field of the handle a later call reads and that is state, not geometry.  (The image is
+// assigned by the caller: a fork needs it before it allocates.)  Captured graphs are not copied -- they carry the view by
+// value -- and neither is the scratch of the post-solve passes, nor the index mcf_update_costs builds on first use.
+void fork_host_state(mcf_handle* f, const mcf_handle* src) {
+    *f->h_ctx = *src->h_ctx;
+    f->ctx_current = true;
+    f->external_driver = src->external_driver;
+    f->stats = src->stats;
+    f->total_cap = src->total_cap;
+    f->solved_once = src->solved_once;
+    f->run_pairs = src->run_pairs; f->run_low = src->run_low; f->run_seen = src->run_seen;
+    f->rc_dropped = src->rc_dropped; f->rcached = src->rcached; f->overlap = src->overlap;
+    f->sw_pivots = src->sw_pivots; f->sw_subtree = src->sw_subtree;
+    f->shard_arcs = src->shard_arcs; f->priced_per_pass = src->priced_per_pass;
+    f->dx_filled = f->d_dx != nullptr;
+    McfView& v = f->view;
+    v.n_nodes = f->im.n_nodes; v.m = f->im.m;
+    for (int x = 0; x <= MCF_NUM_BUCKETS; ++x) v.bucket_off[x] = f->im.bucket_off[x];
+    v.vk_bigm = src->view.vk_bigm; v.vk_half = src->view.vk_half;
+    // a handle that dropped its reduced costs keeps the arrays and prices from the potentials (mcf_solve)
+    v.rcache = src->rc_dropped || !f->rc_able ? nullptr : f->d_rcache;
+    v.vkey = src->rc_dropped ? nullptr : f->d_vkey;
+    v.dirty = src->rc_dropped ? nullptr : f->d_dirty;
+    f->uc_inv.clear(); f->uc_stamp.clear();
+}
+
+// The device half: one launch of k_fork over the state arrays of `src` into the `count` handles of dst (same geometry: their
+// array lists were made by the same alloc_wire).  MCF_FORK_MEMCPY=1 (A/B switch, read at the call): one hipMemcpyAsync per
+// array and destination instead.  MCF_FORK_NT = 0 / 1 forces plain / non-temporal stores (default: by the size of a fork).
+int fork_device_copy(mcf_handle* src, mcf_handle* const* dst, int32_t count, mcf_fork_report* rep) {
+    std::vector<McfForkSeg> segs;
+    int64_t chunks = 0, bytes = 0;
+    for (const mcf_handle::DevArray& a : src->arrays) {
+        if (!a.state) continue;
+        McfForkSeg sg;
+        sg.src = static_cast<const char*>(*a.field); sg.bytes = (int64_t)a.bytes; sg.chunk0 = chunks; sg.slot = (int32_t)segs.size(); sg.pad = 0;
+        chunks += mcf_fork_chunks(sg.bytes);
+        bytes += sg.bytes;
+        segs.push_back(sg);
+    }
+    const size_t nseg = segs.size();
+    std::vector<char*> table((size_t)count * nseg);
+    for (int32_t d = 0; d < count; ++d) {
+        size_t slot = 0;
+        for (const mcf_handle::DevArray& a : dst[d]->arrays) {
+            if (!a.state) continue;
+            if (slot >= nseg || (int64_t)a.bytes != segs[slot].bytes) { src->err = "internal: array lists of a fork differ"; return MCF_E_INTERNAL; }
+            table[(size_t)d * nseg + slot++] = static_cast<char*>(*a.field);
+        }
+        if (slot != nseg) { src->err = "internal: array lists of a fork differ"; return MCF_E_INTERNAL; }
+    }
+    hipStream_t s = src->stream;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    char* d_tab = nullptr;
+    const size_t seg_bytes = (nseg * sizeof(McfForkSeg) + 15) & ~(size_t)15, tab_bytes = table.size() * sizeof(char*);
+    auto done = [&](int code, const char* what) {
+        (void)hipStreamSynchronize(s);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        (void)hipFree(d_tab);
+        if (code != MCF_OK) { (void)hipGetLastError(); src->err = what; }
+        return code;
+    };
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) return done(MCF_E_HIP, "hipEventCreate");
+    const char* mc = std::getenv("MCF_FORK_MEMCPY");
+    const bool by_memcpy = mc && mc[0] == '1';
+    if (!by_memcpy) {
+        if (hipMalloc(reinterpret_cast<void**>(&d_tab), seg_bytes + tab_bytes + 16) != hipSuccess) return done(MCF_E_ALLOC, "hipMalloc of the copy's segment table");
+        if (hipMemcpyAsync(d_tab, segs.data(), nseg * sizeof(McfForkSeg), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(d_tab + seg_bytes, table.data(), tab_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)   // (pageable sources)
+            return done(MCF_E_HIP, "upload of the copy's segment table");
+    }
+    if (hipEventRecord(ev[0], s) != hipSuccess) return done(MCF_E_HIP, "hipEventRecord");
+    if (by_memcpy) {
+        for (int32_t d = 0; d < count; ++d)
+            for (size_t i = 0; i < nseg; ++i)
+                if (segs[i].bytes > 0 && hipMemcpyAsync(table[(size_t)d * nseg + i], segs[i].src, (size_t)segs[i].bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                    return done(MCF_E_HIP, "hipMemcpyAsync of an array");
+    } else if (chunks > 0) {
+        // Store flavour, as measured on MI355X (profiles/fork_scenarios.txt): a fork of 152 MB -- source plus destination
+        // larger than the Infinity Cache -- takes 0.067 ms with non-temporal stores against 0.071 ms with plain ones; the
+        // small forks of a scenario batch are read again at once by their edits and solves and keep plain stores.
+        const char* nt_env = std::getenv("MCF_FORK_NT");
+        const bool nt = nt_env ? nt_env[0] == '1' : bytes > ((int64_t)128 << 20);
+        const int64_t items = mcf_fork_items(chunks, count);
+        const unsigned grid = (unsigned)(items < 2048 ? items : 2048);   // 8 workgroups per CU; the rest by the grid-stride loop
+        const McfForkSeg* d_seg = reinterpret_cast<const McfForkSeg*>(d_tab);
+        char* const* d_dst = reinterpret_cast<char* const*>(d_tab + seg_bytes);
+        if (nt) hipLaunchKernelGGL(k_fork<true>, dim3(grid), dim3(MCF_FORK_THREADS), 0, s, d_seg, (int32_t)nseg, chunks, d_dst, (int64_t)count);
+        else hipLaunchKernelGGL(k_fork<false>, dim3(grid), dim3(MCF_FORK_THREADS), 0, s, d_seg, (int32_t)nseg, chunks, d_dst, (int64_t)count);
+        if (hipGetLastError() != hipSuccess) return done(MCF_E_HIP, "launch of the copy kernel");
+    }
+    if (hipEventRecord(ev[1], s) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess) return done(MCF_E_HIP, "the device copy failed");
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
+    if (rep) { rep->count = count; rep->segments = (int64_t)nseg; rep->bytes_per_fork = bytes; rep->device_ms = ms; }
+    return done(MCF_OK, "");
+}
+
+int fork_check_src(mcf_handle* src, const char* who) {
+    if (src->shards != 1) {
+        src->err = std::string(who) + ": handle was created with shard_count > 1; sharded handles cannot be forked";
+        return MCF_E_STATE;
+    }
+    HIP_TRY(src, hipSetDevice(src->device));
+    HIP_TRY(src, hipStreamSynchronize(src->stream));
+    return sync_ctx(src, src->stream);   // (reads the control block; writes nothing the solver reads)
+}
+
+}  // namespace
+
+int mcf_fork(mcf_handle* src, int32_t count, mcf_handle** out, mcf_fork_report* report) {
+    if (!src || !out || count < 0) { g_create_error = "mcf_fork: null src / out or count < 0"; if (src) src->err = g_create_error; return MCF_E_BAD_ARG; }
+    if (report) std::memset(report, 0, sizeof *report);
+    if (count == 0) return MCF_OK;
+    for (int32_t i = 0; i < count; ++i) out[i] = nullptr;
+    int rc = fork_check_src(src, "mcf_fork");
+    if (rc) { g_create_error = src->err; return rc; }
+    auto undo = [&](int code, const std::string& msg) {
+        for (int32_t i = 0; i < count; ++i) if (out[i]) { free_all(out[i]); delete out[i]; out[i] = nullptr; }
+        (void)hipGetLastError();
+        g_create_error = msg; src->err = msg;
+        return code;
+    };
+    for (int32_t i = 0; i < count; ++i) {
+        mcf_handle* f = new (std::nothrow) mcf_handle();
+        if (!f) return undo(MCF_E_ALLOC, "mcf_fork: host allocation");
+        out[i] = f;
+        try { f->im = src->im; } catch (const std::bad_alloc&) { return undo(MCF_E_ALLOC, "mcf_fork: host allocation of the image"); }
+        f->opt = src->opt;
+        f->opt.arc_priority = nullptr;   // (the source's pointer was only valid during mcf_create)
+        f->device = src->device;
+        f->shards = src->shards; f->shard = src->shard;
+        inherit_geometry(f, src);
+        const char* what = "";
+        const hipError_t e = alloc_wire(f, false, &what);
+        if (e != hipSuccess) return undo(e == hipErrorOutOfMemory ? MCF_E_ALLOC : MCF_E_HIP, std::string("mcf_fork: ") + what + ": " + hipGetErrorString(e));
+        if (own_stream_if_captured(f) != hipSuccess) return undo(MCF_E_HIP, "mcf_fork: hipStreamCreate");
+        fork_host_state(f, src);
+        f->shape = src->shape;
+    }
+    rc = fork_device_copy(src, out, count, report);
+    if (rc) return undo(rc, "mcf_fork: " + src->err);
+    return MCF_OK;
+}
+
+int mcf_restore(mcf_handle* const* dst, int32_t count, mcf_handle* src, mcf_fork_report* report) {
+    if (!src || !dst || count < 0) { if (src) src->err = "mcf_restore: null dst or count < 0"; return MCF_E_BAD_ARG; }
+    if (report) std::memset(report, 0, sizeof *report);
+    for (int32_t i = 0; i < count; ++i) {
+        if (!dst[i] || dst[i] == src) { src->err = "mcf_restore: a destination is null or the source itself"; return MCF_E_BAD_ARG; }
+        for (int32_t j = 0; j < i; ++j) if (dst[j] == dst[i]) { src->err = "mcf_restore: a destination is named twice"; return MCF_E_BAD_ARG; }
+    }
+    if (count == 0) return MCF_OK;
+    if (src->shards != 1) { src->err = "mcf_restore: handle was created with shard_count > 1; sharded handles cannot be forked"; return MCF_E_STATE; }
+    for (int32_t i = 0; i < count; ++i) {
+        const mcf_handle* d = dst[i];
+        const char* field = nullptr;
+        for (size_t k = 0; k < src->shape.size() && !field; ++k)
+            if (d->shape.size() != src->shape.size() || d->shape[k].second != src->shape[k].second) field = src->shape[k].first;
+        for (size_t k = 0; k < src->arrays.size() && !field; ++k)
+            if (d->arrays.size() != src->arrays.size() || d->arrays[k].bytes != src->arrays[k].bytes) field = src->arrays[k].name;
+        if (field) {
+            src->err = "mcf_restore: destination " + std::to_string(i) + " has another shape than the source: " + field;
+            return MCF_E_STATE;
+        }
+    }
+    int rc = fork_check_src(src, "mcf_restore");
+    if (rc) return rc;
+    for (int32_t i = 0; i < count; ++i) {   // host allocation first: nothing has changed if it fails
+        try { dst[i]->im = src->im; } catch (const std::bad_alloc&) { src->err = "mcf_restore: host allocation of the image"; return MCF_E_ALLOC; }
+    }
+    for (int32_t i = 0; i < count; ++i) HIP_TRY(src, hipStreamSynchronize(dst[i]->stream));
+    rc = fork_device_copy(src, dst, count, report);
+    if (rc) return rc;
+    for (int32_t i = 0; i < count; ++i) {
+        mcf_handle* f = dst[i];
+        f->opt = src->opt;
+        f->opt.arc_priority = nullptr;
+        f->climb_budget = src->climb_budget; f->rc_drop_subtree = src->rc_drop_subtree; f->run_pairs_cfg = src->run_pairs_cfg;
+        f->small_layout = src->small_layout; f->small_narrow_ok = src->small_narrow_ok; f->nt_sweep = src->nt_sweep;
+        fork_host_state(f, src);
+        drop_graph(f);   // (rebuilt on first use)
+        // scratch of the post-solve passes that caches the instance: filled again on first use
+        lazy_release({{&f->d_ct_supply, 0}, {&f->d_ct_adj_off, 0}, {&f->d_ct_adj, 0}});
+        f->err.clear();
+    }
+    return MCF_OK;
+}
 
 // ====================================================================== C ABI
 extern "C" {
@@ -3313,273 +3890,20 @@ int mcf_create(int32_t n, int64_t m, const int32_t* tail, const int32_t* head, c
         delete h;
         return MCF_E_BAD_ARG;
     }
-    const McfHostImage& im = h->im;
-    {
-        // Tree layout: the blocked preorder list (mcf_core.h) from kBplMinNodes nodes on -- below that the dense array's block
-        // permutation moves few enough positions, and the persistent loops keep the dense array anyway.
-        // tree_blocks: 0 = auto, -1 = dense array, k >= 2 = blocks of 2^k slots;  tree_pool: spare blocks (0 = auto, -1 = none).
-        const bool forced = opt.tree_blocks > 0, never = opt.tree_blocks < 0;
-        h->bpl = !never && opt.mid_loop <= 0 && opt.overlap_update <= 0 && (forced || im.n_nodes >= kBplMinNodes);
-        if (h->bpl) {
-            int32_t sh = 0, cap = 0, dense = 0;
-            mcf_bpl_geometry(im.n_nodes, forced ? opt.tree_blocks : 0, opt.tree_pool, &sh, &cap, &dense);
-            h->bpl_shift = sh; h->bpl_cap = cap; h->bpl_dense = dense;
-            // (a large grid costs dispatch time on every pivot: 1 M / 16 M, 256 -> 64 workgroups: k_update_bpl 7.5 -> 6.0 us, +4 % pivots/s)
-            int g = (cap + 7) / 8;
-            if (g > 64) g = 64;
-            if (const char* ge = std::getenv("MCF_BPL_GRID")) { const int vv = std::atoi(ge); if (vv >= 1 && vv <= 4096) g = vv; }   // A/B switch
-            if (g < 1) g = 1;
-            while ((cap + g - 1) / g > kBplTouchedCap) g *= 2;
-            h->bpl_grid = g;
-        }
-    }
-    {
-        // 8 * k workgroups, one group of k per XCD head bucket (formula shared with the CPU emulation)
-        h->price_blocks = mcf_price_blocks(m, h->shards, opt.price_blocks);
-        const int64_t ab = ((int64_t)im.n_nodes + kApplyThreads - 1) / kApplyThreads;
-        int max_ab = kMaxApplyBlocks;
-        if (const char* ab_env = std::getenv("MCF_APPLY_BLOCKS")) { const int vv = std::atoi(ab_env); if (vv >= 64 && vv <= 4096) max_ab = vv; }   // A/B switch
-        h->apply_blocks = (int)(ab < max_ab ? ab : max_ab);
-    }
-
-    auto fail = [&](const char* what, hipError_t e) {
-        g_create_error = std::string(what) + ": " + hipGetErrorString(e);
+    decide_geometry(h);
+    const char* what = "";
+    hipError_t e = alloc_wire(h, true, &what);
+    auto fail = [&](const char* step, hipError_t err) {
+        g_create_error = std::string(step) + ": " + hipGetErrorString(err);
         free_all(h);
         delete h;
-        return e == hipErrorOutOfMemory ? MCF_E_ALLOC : MCF_E_HIP;
+        return err == hipErrorOutOfMemory ? MCF_E_ALLOC : MCF_E_HIP;
     };
-    hipError_t e;
-    h->stream_owned = n > kPooledMaxNodes;
-    if ((e = h->stream_owned ? hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) : pool_stream(h->device, &h->stream)) != hipSuccess) return fail("hipStreamCreate", e);
-    const size_t N = im.n_nodes;
-    if ((e = dalloc(&h->d_tail, im.m_pad)) != hipSuccess) return fail("hipMalloc tail", e);
-    if ((e = dalloc(&h->d_head, im.m_pad)) != hipSuccess) return fail("hipMalloc head", e);
-    if ((e = dalloc(&h->d_cost, im.m_pad)) != hipSuccess) return fail("hipMalloc cost", e);
-    if ((e = dalloc(&h->d_orig, im.m_pad)) != hipSuccess) return fail("hipMalloc orig", e);
-    if ((e = dalloc(&h->d_state, im.m_pad)) != hipSuccess) return fail("hipMalloc state", e);
-    if ((e = dalloc(&h->d_weight, im.m_pad)) != hipSuccess) return fail("hipMalloc weight", e);
-    if ((e = dalloc(&h->d_arcw, im.arcw.size())) != hipSuccess) return fail("hipMalloc arcw", e);
-    if ((e = dalloc(&h->d_pi, N)) != hipSuccess) return fail("hipMalloc pi", e);
-    if ((e = dalloc(&h->d_node, N)) != hipSuccess) return fail("hipMalloc node", e);
-    const size_t bpl_slots = h->bpl ? ((size_t)h->bpl_cap << h->bpl_shift) + 4 : 0;   // slots per arena (+4: groups of four)
-    // (+4: the cycle scan reads the nodes in aligned groups of four, like the sizes)
-    if ((e = dalloc(&h->d_order0, h->bpl ? bpl_slots : N + 4)) != hipSuccess) return fail("hipMalloc order", e);
-    if ((e = dalloc(&h->d_order1, h->bpl ? bpl_slots : N + 4)) != hipSuccess) return fail("hipMalloc order", e);
-    if ((e = dalloc(&h->d_pos0, N)) != hipSuccess) return fail("hipMalloc pos", e);
-    if ((e = dalloc(&h->d_pos1, h->bpl ? 1 : N)) != hipSuccess) return fail("hipMalloc pos", e);
-    if ((e = dalloc(&h->d_path1, N)) != hipSuccess) return fail("hipMalloc path", e);
-    if ((e = dalloc(&h->d_path2, N)) != hipSuccess) return fail("hipMalloc path", e);
-    if ((e = dalloc(&h->d_ppos1, h->bpl ? 2 * N : N)) != hipSuccess) return fail("hipMalloc path", e);   // (blocked list: positions, then slots)
-    if ((e = dalloc(&h->d_ppos2, h->bpl ? 2 * N : N)) != hipSuccess) return fail("hipMalloc path", e);
-    if ((e = dalloc(&h->d_rec1, N)) != hipSuccess) return fail("hipMalloc rec", e);
-    if ((e = dalloc(&h->d_rec2, N)) != hipSuccess) return fail("hipMalloc rec", e);
-    if ((e = dalloc(&h->d_seg, 2 * N + 2)) != hipSuccess) return fail("hipMalloc seg", e);
-    if ((e = dalloc(&h->d_ctx, 1)) != hipSuccess) return fail("hipMalloc ctx", e);
-    if ((e = dalloc(&h->d_cand, kMaxPriceBlocks)) != hipSuccess) return fail("hipMalloc cand", e);
-    if ((e = dalloc(&h->d_cand_aux, kMaxPriceBlocks)) != hipSuccess) return fail("hipMalloc cand", e);
-    if ((e = hipMemset(h->d_cand, 0xff, kMaxPriceBlocks * sizeof(McfCand))) != hipSuccess) return fail("hipMemset cand", e);
-    if ((e = dalloc(&h->d_one, 1)) != hipSuccess) return fail("hipMalloc one", e);
-    if ((e = dalloc(&h->d_swept, kMaxPriceBlocks)) != hipSuccess) return fail("hipMalloc swept", e);
-    {   // pinned: the control block's host copy and the one-candidate read-back buffer (one pooled slot)
-        char* slot = nullptr;
-        if ((e = pinned_take(&slot)) != hipSuccess) return fail("hipHostMalloc", e);
-        h->h_ctx = reinterpret_cast<McfCtx*>(slot);
-        h->h_one = reinterpret_cast<McfCand*>(slot + ((sizeof(McfCtx) + 63) & ~(size_t)63));
-    }
-
-    McfView& v = h->view;
-    v.n_nodes = im.n_nodes;
-    v.m = im.m;
-    v.tail = h->d_tail; v.head = h->d_head; v.cost = h->d_cost; v.orig = h->d_orig; v.state = h->d_state;
-    for (int x = 0; x <= MCF_NUM_BUCKETS; ++x) v.bucket_off[x] = im.bucket_off[x];
-    v.weight = opt.rule == MCF_RULE_DEVEX_BLOCK ? h->d_weight : nullptr;
-    v.dx = nullptr;  // (allocated and filled by upload_image for the Devex rule)
-    // key variant of the Dantzig / candidate-list sweep (the reference's specialised entering rules, mcf_core.h: mcf_dantzig_key)
-    v.key_mode = opt.key_mode > 0 ? opt.key_mode : (opt.forward_first ? MCF_KEY_FORWARD_FIRST : MCF_KEY_PLAIN);
-    v.prio = nullptr;
-    if (v.key_mode == MCF_KEY_PRIORITY) {
-        std::vector<int8_t> pr((size_t)im.m_pad, 0);   // the caller's order -> engine order
-        for (int64_t i = 0; i < im.m; ++i) pr[(size_t)i] = (int8_t)(opt.arc_priority[im.orig[(size_t)i]] & 3);
-        if ((e = dalloc(&h->d_prio, im.m_pad)) != hipSuccess) return fail("hipMalloc priority", e);
-        if ((e = hipMemcpy(h->d_prio, pr.data(), pr.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy priority", e);
-        v.prio = h->d_prio;
-    }
-    v.arcw = h->d_arcw; v.pi = h->d_pi; v.node = h->d_node;
-    v.order[0] = h->d_order0; v.order[1] = h->d_order1;
-    v.posbuf[0] = h->d_pos0; v.posbuf[1] = h->d_pos1;
-    v.psz[0] = nullptr; v.psz[1] = nullptr;
-    v.reach = nullptr; v.chg = nullptr;
-    v.path1 = h->d_path1; v.path2 = h->d_path2; v.ppos1 = h->d_ppos1; v.ppos2 = h->d_ppos2; v.rec1 = h->d_rec1; v.rec2 = h->d_rec2; v.seg = h->d_seg; v.ctx = h->d_ctx;
-
-    // the fused small-instance path: its LDS plan, and the kernels' dynamic-LDS limit raised to it (refused: the three-kernel GPU path)
-    h->small = !h->bpl && !opt.no_fused && !opt.profile && h->shards == 1 &&
-               small_plan(im.m_pad, im.arcw.size(), im.n_nodes, opt.rule == MCF_RULE_DEVEX_BLOCK, &h->small_layout) &&
-               small_reserve(h->device, h->small_layout.total);
-    if (h->small) { h->small_threads = small_threads_for(im.n_nodes, opt.rule); h->small_narrow_ok = small_narrow_allowed(); }
-    // position-space subtree sizes for the cycle scan: every handle but the LDS-resident ones
-    const bool scan_ok = opt.cycle_scan >= 0 && im.n_nodes <= kScanMaxNodes && !h->small;  // -1: never scan
-    v.bmeta[0] = v.bmeta[1] = nullptr; v.bext[0] = v.bext[1] = nullptr; v.blk_shift = 0; v.blk_cap = 0; v.ncandx = 0; v.candx = nullptr;
-    if (h->bpl) {
-        // the two slot arenas (sizes; node ids are d_order0/1), the block records (two copies) and extents (one per arena),
-        // and the scratch the scan spills flagged blocks to
-        if ((e = dalloc(&h->d_psz0, bpl_slots)) != hipSuccess) return fail("hipMalloc psz", e);
-        if ((e = dalloc(&h->d_psz1, bpl_slots)) != hipSuccess) return fail("hipMalloc psz", e);
-        if ((e = hipMemset(h->d_psz0, 0, bpl_slots * 4)) != hipSuccess || (e = hipMemset(h->d_psz1, 0, bpl_slots * 4)) != hipSuccess) return fail("hipMemset psz", e);
-        for (int a = 0; a < 2; ++a) {
-            if ((e = dalloc(&h->d_bmeta[a], (size_t)h->bpl_cap + 2)) != hipSuccess) return fail("hipMalloc block records", e);
-            if ((e = dalloc(&h->d_bext[a], (size_t)h->bpl_cap)) != hipSuccess) return fail("hipMalloc block extents", e);
-            v.bmeta[a] = h->d_bmeta[a]; v.bext[a] = h->d_bext[a];
-        }
-        const size_t nchg = std::max(N, 2 * (size_t)h->bpl_cap + 2);
-        if ((e = dalloc(&h->d_chg, nchg)) != hipSuccess) return fail("hipMalloc chg", e);
-        v.psz[0] = h->d_psz0; v.psz[1] = h->d_psz1;
-        v.chg = h->d_chg;
-        v.blk_shift = h->bpl_shift; v.blk_cap = h->bpl_cap;
-    } else if (scan_ok) {
-        const size_t NP = (N + MCF_REACH_BLOCK - 1) / MCF_REACH_BLOCK * MCF_REACH_BLOCK + 4;  // whole coarse blocks (+4: groups of four)
-        if ((e = dalloc(&h->d_psz0, NP)) != hipSuccess) return fail("hipMalloc psz", e);
-        if ((e = dalloc(&h->d_psz1, NP)) != hipSuccess) return fail("hipMalloc psz", e);
-        if ((e = hipMemset(h->d_psz0, 0, NP * 4)) != hipSuccess || (e = hipMemset(h->d_psz1, 0, NP * 4)) != hipSuccess) return fail("hipMemset psz", e);
-        v.psz[0] = h->d_psz0; v.psz[1] = h->d_psz1;
-        if ((e = dalloc(&h->d_reach, NP / MCF_REACH_BLOCK + 8)) != hipSuccess) return fail("hipMalloc reach", e);   // (+8: read four at a time)
-        if ((e = hipMemset(h->d_reach, 0, (NP / MCF_REACH_BLOCK + 8) * 4)) != hipSuccess) return fail("hipMemset reach", e);
-        if ((e = dalloc(&h->d_chg, N)) != hipSuccess) return fail("hipMalloc chg", e);
-        v.reach = h->d_reach; v.chg = h->d_chg;
-    }
-    // cycle search: how many round trips the one-lane climb takes before the workgroup-wide scan over
-    // preorder positions finishes the cycle.  Auto = none: measured on MI355X (profiles/r01_f_*), scanning
-    // at once beats every hybrid from 256 to 65 536 nodes -- a dependent global round trip per tree level
-    // costs more than the whole scan's ~4 -- by 1.1x (netgen_8_08a) to 4.5x (goto_8_16a, cycles of ~450 arcs).
-    if (!scan_ok && !(h->bpl && opt.cycle_scan >= 0)) h->climb_budget = INT32_MAX;
-    else if (opt.cycle_scan > 0) h->climb_budget = opt.cycle_scan - 1;
-    else h->climb_budget = 0;
-    // resident reduced costs for everything that does not take the fused LDS path
-    h->rcached = !h->small && !opt.no_rcache && im.m > 0;
-    if (h->rcached) {
-        // a rank patches only the reduced costs it sweeps -- for the rules whose sweeps cover a FIXED share of every bucket.
-        // Devex cuts the block first and the shard second (so that the union over ranks does not depend on the rank
-        // count), and blocks move and resize: there every rank keeps all reduced costs exact, as a single GPU does.
-        const bool partial = h->shards > 1 && opt.rule != MCF_RULE_DEVEX_BLOCK;
-        mcf_build_rcache(h->im, partial ? h->shard : 0, partial ? h->shards : 1);
-        v.rc_partial = partial ? 1 : 0;
-        if ((e = dalloc(&h->d_rcache, im.m_pad)) != hipSuccess) return fail("hipMalloc rcache", e);
-        if ((e = dalloc(&h->d_adj_off, im.adj_off.size())) != hipSuccess) return fail("hipMalloc adj_off", e);
-        if ((e = dalloc(&h->d_adj, im.adj.size())) != hipSuccess) return fail("hipMalloc adj", e);
-        if ((e = hipMemcpy(h->d_adj_off, im.adj_off.data(), im.adj_off.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail("copy adj_off", e);
-        if ((e = hipMemcpy(h->d_adj, im.adj.data(), im.adj.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail("copy adj", e);
-        h->im.adj.clear(); h->im.adj.shrink_to_fit();  // the device copy is the only one needed from here on
-        v.rcache = h->d_rcache; v.adj_off = h->d_adj_off; v.adj = h->d_adj;
-        const int64_t rb = ((int64_t)im.n_nodes + 15) / 16;  // one 16-lane group per node of the largest possible T2
-        int max_rb = kMaxRcupdBlocks;
-        if (const char* re = std::getenv("MCF_RCUPD_BLOCKS")) { const int vv = std::atoi(re); if (vv >= 1 && vv <= 4096) max_rb = vv; }   // A/B switch
-        h->rcupd_blocks = (int)(rb < max_rb ? (rb > 0 ? rb : 1) : max_rb);
-    } else {
-        v.rcache = nullptr; v.adj_off = nullptr; v.adj = nullptr; v.rc_partial = 0;
-    }
-    // persistent single-workgroup loop: the tree work of one pivot must be small enough for one CU, and so must
-    // the arcs it prices per pivot (a Devex block / the whole arc list for Dantzig; the candidate list's full
-    // sweeps stay on the grid)
-    {
-        int64_t per_pivot_arcs = 0;
-        if (opt.rule == MCF_RULE_DEVEX_BLOCK) {
-            McfCtx probe;  // the largest block the tuner may grow to (mcf_core.h: never beyond MCF_TUNER_MAX_ARCS or the initial size)
-            std::memset(&probe, 0, sizeof probe);
-            mcf_init_block_state(&probe, opt.rule, im.m, opt.block_size);
-            per_pivot_arcs = im.m * probe.max_granules / MCF_GRANULES;
-        } else if (opt.rule == MCF_RULE_DANTZIG_FULL) {
-            per_pivot_arcs = im.m;
-        }
-        // (the candidate list never gains from the loop -- its full sweeps run on the grid either way -- and stays on the graph)
-        const bool fits = im.n_nodes <= kMidMaxNodes && per_pivot_arcs <= kMidMaxArcsPerPivot && opt.rule != MCF_RULE_CANDIDATE_LIST;
-        h->mid = !h->bpl && h->rcached && scan_ok && h->shards == 1 && !opt.profile && opt.mid_loop >= 0 && (fits || opt.mid_loop > 0);
-    }
-    // overlapped graphs (build_graph), on request only: the idea -- on large trees the permutation outlasts the reduced-cost
-    // patch, so the next pricing could hide beside it -- loses to the cost of the two cross-queue edges per pivot
-    // (netgen_8_14a 55 K -> 33 K pivots/s, 1 M / 16 M 26 K -> 22 K; profiles/r02_ab_overlapped_graph.txt)
-    {
-        const bool able = !h->bpl && h->rcached && !h->small && !h->mid && h->shards == 1 && !opt.profile && opt.rule != MCF_RULE_CANDIDATE_LIST;
-        h->overlap = able && opt.overlap_update > 0;
-        h->overlap_cfg = h->overlap;
-        if (h->overlap && (e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
-    }
-    // compressed Dantzig keys for the grid sweeps of the Dantzig / candidate-list rules (4 B per arc instead of 9)
-    v.vkey = nullptr;
-    v.vk_bigm = im.big_m;
-    v.vk_half = 1 << (opt.vkey_half_log2 > 0 && opt.vkey_half_log2 <= 28 ? opt.vkey_half_log2 : 28);
-    // They pay where a sweep reads the whole shard and is bandwidth-bound: full (non-incremental) sweeps of the Dantzig rule
-    // from kIncrementalMinArcs arcs on (1 M / 16 M: sweep 24 -> 14 us).  Keeping the codes exact costs the reduced-cost patch a state
-    // byte and a 4-byte store per patched arc (k_update +1..3 us per pivot), which a candidate-list handle (one sweep per ~33
-    // pivots) or an incremental sweep (1 % of the arcs re-read per pivot) never earns back.  compressed_keys: 1 = on, -1 = off.
-    const bool keys_auto = opt.rule == MCF_RULE_DANTZIG_FULL && opt.full_sweeps > 0 && im.m >= kIncrementalMinArcs;
-    if (h->rcached && !h->mid && opt.rule != MCF_RULE_DEVEX_BLOCK && v.key_mode == MCF_KEY_PLAIN &&
-        (opt.compressed_keys > 0 || (opt.compressed_keys == 0 && keys_auto))) {
-        if ((e = dalloc(&h->d_vkey, im.m_pad)) != hipSuccess) return fail("hipMalloc vkey", e);
-        v.vkey = h->d_vkey;
-        const char* nt_env = std::getenv("MCF_NT_SWEEP");   // A/B switch: 0 / 1 force, unset = by size
-        h->nt_sweep = nt_env ? nt_env[0] == '1' : (im.m_pad / (h->shards > 0 ? h->shards : 1)) * 4 > (int64_t)200 * 1024 * 1024;
-    }
-    // incremental pricing for the rules whose sweeps cover the whole shard (Dantzig, candidate list); not for the
-    // persistent loop, whose instances are far too small for it (its kernel compiles the marking away)
-    v.dirty = nullptr;
-    // (auto: only where a sweep is a large part of a pivot -- below ~4 M arcs the flag look-up in front of every
-    // sweep and the marking in k_update cost more than the skipped blocks save: netgen_8_14a 52.7 K -> 46.7 K pivots/s;
-    // at 16 M arcs: 23.9 K -> 37 K)
-    if (h->rcached && !h->mid && opt.rule != MCF_RULE_DEVEX_BLOCK && (opt.full_sweeps < 0 || (opt.full_sweeps == 0 && im.m >= kIncrementalMinArcs))) {
-        static_assert(MCF_MAX_PRICE_BLOCKS == kMaxPriceBlocks, "flag array size");
-        if ((e = dalloc(&h->d_dirty, 1)) != hipSuccess) return fail("hipMalloc dirty", e);
-        McfDirty head;  // (the flags are raised by upload_image)
-        head.nlb = h->price_blocks / MCF_NUM_BUCKETS;
-        for (int x = 0; x < MCF_NUM_BUCKETS; ++x) {
-            int64_t lo, hi;
-            mcf_bucket_slice(im.bucket_off, x, h->shard, h->shards, 0, 1, &lo, &hi);
-            head.lo[x] = (int32_t)lo; head.hi[x] = (int32_t)hi;
-        }
-        if ((e = hipMemcpy(h->d_dirty, &head, offsetof(McfDirty, flag), hipMemcpyHostToDevice)) != hipSuccess) return fail("copy dirty", e);
-        v.dirty = h->d_dirty;
-    }
-    // candidate cache: the grid path of the candidate-list rule on one GPU, keys that need nothing but the reduced cost
-    v.candx = nullptr; v.ncandx = 0;
-    if (opt.rule == MCF_RULE_CANDIDATE_LIST && h->shards == 1 && !h->small && !h->mid && !opt.profile && v.key_mode <= MCF_KEY_FORWARD_FIRST &&
-        h->price_blocks <= 2 * kPivotThreads && !std::getenv("MCF_NO_CANDX")) {
-        if ((e = dalloc(&h->d_candx, kMaxPriceBlocks)) != hipSuccess) return fail("hipMalloc candidate records", e);
-        if ((e = hipMemset(h->d_candx, 0xff, kMaxPriceBlocks * sizeof(McfCandX))) != hipSuccess) return fail("hipMemset candidate records", e);
-        v.candx = h->d_candx; v.ncandx = h->price_blocks;
-    }
-    // pivots back to back (k_pivot_run): candidate-list handles on the blocked list that keep the candidate cache
-    h->run_pairs_cfg = 0;
-    // Opt-in: measured at 1M/16M (first 300 K pivots, same box) 30.9-35.7 K pivots/s in the run shape against 41.1 K in the
-    // pivot+update pair shape -- one workgroup's phase A over 8-20 K blocks costs more than the launches it saves.
-    const char* run_env = std::getenv("MCF_PIVOT_RUN");
-    const int want_run = opt.pivot_run > 0 ? opt.pivot_run : (run_env ? std::atoi(run_env) : 0);
-    if (h->bpl && v.candx && want_run > 0 && opt.use_graph && !std::getenv("MCF_NO_RUN")) h->run_pairs_cfg = want_run;
-    h->run_pairs = h->run_pairs_cfg;
-    h->rc_able = h->rcached;
-    {
-        // auto: candidate lists (one sweep per ~33 pivots) on large instances (from 100 000 nodes: measured at 1 M / 16 M) from an
-        // average |T2| of 384 nodes, Devex there from 1 500; never for the Dantzig rule, whose every pivot sweeps all arcs, for
-        // shards (their driver owns the launches) or the persistent loops.  rc_drop: -1 = never, k > 0 = that threshold.
-        int64_t thr = 0;
-        if (h->rcached && !h->mid && !h->small && h->shards == 1 && opt.key_mode == 0 && !opt.forward_first) {
-            if (opt.rc_drop > 0) thr = opt.rc_drop;
-            else if (opt.rc_drop == 0 && im.n_nodes >= 100000)
-                // (Devex block search sweeps one block per pivot: the dearer sweep is paid every time, so it waits for larger
-                //  subtrees -- 1 M / 16 M: 139.8 s without, 134.0 / 134.8 s with a threshold of 1 500 / 384)
-                thr = opt.rule == MCF_RULE_CANDIDATE_LIST ? 384 : (opt.rule == MCF_RULE_DEVEX_BLOCK ? 1500 : 0);
-            if (opt.rule == MCF_RULE_DANTZIG_FULL) thr = 0;
-        }
-        if (const char* env = std::getenv("MCF_RC_DROP")) { const long vv = std::atol(env); thr = vv > 0 ? vv : 0; }   // A/B switch
-        h->rc_drop_subtree = h->rcached && h->shards == 1 ? thr : 0;
-    }
+    if (e != hipSuccess) return fail(what, e);
     const int rc = upload_image(h);   // (ends with a synchronisation of h->stream)
     if (rc != MCF_OK) { g_create_error = h->err; free_all(h); delete h; return rc; }
-    // A handle that captures graphs needs a stream nobody else captures on: only the persistent-loop paths that launch
-    // plain kernels keep the borrowed stream.
-    if (!h->stream_owned && !(h->small || (h->mid && opt.rule != MCF_RULE_CANDIDATE_LIST))) {
-        hipStream_t own = nullptr;
-        if ((e = hipStreamCreateWithFlags(&own, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
-        h->stream = own;
-        h->stream_owned = true;
-    }
+    if ((e = own_stream_if_captured(h)) != hipSuccess) return fail("hipStreamCreate", e);
+    h->shape = shape_of(h);
     *out = h;
     return MCF_OK;
 }

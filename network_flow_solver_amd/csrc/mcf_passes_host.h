@@ -690,7 +690,7 @@ int mcf_add_arcs(mcf_handle* h, int64_t count, const int32_t* tail, const int32_
 
     // ---- device memory: the upload buffers (freed on return) and the new arrays (the handle's once every pass has completed)
     std::vector<void*> temps;
-    struct Fresh { void** field; void* ptr; };
+    struct Fresh { void** field; void* ptr; size_t bytes; };
     std::vector<Fresh> fresh;
     auto give_up = [&](int code, const char* what) {
         (void)hipStreamSynchronize(s);
@@ -711,7 +711,7 @@ int mcf_add_arcs(mcf_handle* h, int64_t count, const int32_t* tail, const int32_
         *p = nullptr;
         if (!alloc_ok || !*field) return;
         if (dalloc(p, cnt) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; alloc_ok = false; return; }
-        fresh.push_back({reinterpret_cast<void**>(field), *p});
+        fresh.push_back({reinterpret_cast<void**>(field), *p, cnt * sizeof(**p)});
     };
     int64_t *t_nkey, *t_ncap, *t_npos, *t_epn, *t_epe, *t_epv;
     int32_t *t_ntail, *t_nhead, *t_ncost, *t_norig, *t_emap;
@@ -833,7 +833,10 @@ int mcf_add_arcs(mcf_handle* h, int64_t count, const int32_t* tail, const int32_
 
     // ---- every pass has completed: the handle takes the new arrays over (the old ones are freed at the end: a free synchronises)
     std::vector<void*> old_arrays;
-    for (const Fresh& f : fresh) { old_arrays.push_back(*f.field); *f.field = f.ptr; }
+    for (const Fresh& f : fresh) {
+        old_arrays.push_back(*f.field); *f.field = f.ptr;
+        for (mcf_handle::DevArray& a : h->arrays) if (a.field == f.field) a.bytes = f.bytes;   // (what mcf_fork copies and mcf_restore compares)
+    }
     fresh.clear();
     McfView& v = h->view;
     v.m = m2;
@@ -859,6 +862,7 @@ int mcf_add_arcs(mcf_handle* h, int64_t count, const int32_t* tail, const int32_
     for (int x = 0; x <= MCF_NUM_BUCKETS; ++x) im.bucket_off[x] = nim.bucket_off[x];
     im.m = m2; im.m_pad = m_pad2; im.big_m = big_m;
     if (h->small) h->small_layout = L2;
+    h->shape = shape_of(h);
     drop_graph(h);   // (captured graphs carry the view by value)
     h->uc_inv.clear(); h->uc_stamp.clear();   // (rebuilt for the new m on their next use)
     // ---- device passes, part two (its own event pair): the small tables, potentials when big-M grew, the new arcs' reduced

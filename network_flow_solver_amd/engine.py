@@ -33,7 +33,7 @@ ABI_SYMBOLS = (
     "mcf_enqueue_price", "mcf_enqueue_pivot", "mcf_shard_info", "mcf_enqueue_price_list", "mcf_enqueue_pivots", "mcf_poll", "mcf_set_max_pivots", "mcf_time_pricing",
     "mcf_time_copy", "mcf_get_tree", "mcf_get_reduced_costs", "mcf_get_pricing_keys", "mcf_get_weights", "mcf_dimacs_scan", "mcf_dimacs_load", "mcf_last_error", "mcf_destroy", "mcf_abi_version", "mcf_device_count",
     "mcf_certify", "mcf_bottlenecks", "mcf_update_rhs", "mcf_certify_ray", "mcf_certify_cut", "mcf_add_arcs",
-    "mcf_cost_ranges", "mcf_small_narrow_ok", "mcf_supply_ranges", "mcf_capacity_ranges", "mcf_update_rhs_dual",
+    "mcf_cost_ranges", "mcf_small_narrow_ok", "mcf_supply_ranges", "mcf_capacity_ranges", "mcf_update_rhs_dual", "mcf_fork", "mcf_restore",
 )
 RANGE_INF = (1 << 63) - 1   # MCF_RANGE_INF: no arc limits this side of a cost, supply or capacity range
 # mcf_certify: check groups and verdicts (include/mcf.h)
@@ -139,6 +139,13 @@ class McfArcsReport(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class McfForkReport(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_int64), ("segments", ctypes.c_int64), ("bytes_per_fork", ctypes.c_int64), ("device_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def _int128(v) -> int:
     return (int(v[0]) << 64) + (int(v[1]) & ((1 << 64) - 1))
 
@@ -238,6 +245,11 @@ def load_library():
     lib.mcf_certify_ray.argtypes = [vp, ctypes.c_int64, i64p, ctypes.c_int64, ctypes.POINTER(McfRay)]
     lib.mcf_certify_cut.argtypes = [vp, i8p, i8p, ctypes.POINTER(McfCut)]
     lib.mcf_cost_ranges.argtypes = [vp, ctypes.c_int64, i64p, i64p, i64p, ctypes.POINTER(McfRangesReport)]
+    if hasattr(lib, "mcf_fork"):   # (an A/B library built from an earlier commit lacks it: MCF_HIP_LIB)
+        lib.mcf_fork.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(vp), ctypes.POINTER(McfForkReport)]
+        lib.mcf_fork.restype = ctypes.c_int
+        lib.mcf_restore.argtypes = [ctypes.POINTER(vp), ctypes.c_int32, vp, ctypes.POINTER(McfForkReport)]
+        lib.mcf_restore.restype = ctypes.c_int
     if hasattr(lib, "mcf_small_narrow_ok"):   # (an A/B library built from an earlier commit lacks it: MCF_HIP_LIB)
         lib.mcf_small_narrow_ok.argtypes = [ctypes.c_int64, ctypes.c_int64, i64p]
         lib.mcf_small_narrow_ok.restype = ctypes.c_int
@@ -542,6 +554,34 @@ class McfEngine:
             self.m += k
         return rep.as_dict()
 
+    def _wrap(self, handle) -> "McfEngine":
+        """An engine object round an existing handle that holds this engine's instance (``mcf_fork``).  The numpy copies are
+        shared until one side changes them: both sides then copy first, as after taking a caller's arrays."""
+        e = object.__new__(McfEngine)
+        e._lib, e._h = self._lib, handle
+        e.n, e.m, e.rule, e.key_mode = self.n, self.m, self.rule, self.key_mode
+        e.tail, e.head, e.cost, e.cap, e.supply = self.tail, self.head, self.cost, self.cap, self.supply
+        e._arc_priority = self._arc_priority
+        e._cost_private = e._rhs_private = False
+        self._cost_private = self._rhs_private = False   # (the arrays now have a second reader: copy on the next change)
+        return e
+
+    def fork(self, count: int = 1, report: dict | None = None) -> list["McfEngine"]:
+        """``count`` new engines, each a complete copy of this one's resident state made on the device (``mcf_fork``): they
+        answer every query as this engine does and go on pivoting exactly as it would.  This engine is only read.
+        ``report`` (a dict) receives the fields of ``mcf_fork_report``."""
+        if not hasattr(self._lib, "mcf_fork"):
+            raise EngineUnavailableError(f"{LIB_PATH} does not export mcf_fork (a library built from an earlier commit)")
+        count = int(count)
+        out = (ctypes.c_void_p * max(count, 1))()
+        rep = McfForkReport()
+        rc = self._lib.mcf_fork(self._h, count, out, ctypes.byref(rep))
+        if rc != 0:
+            raise EngineError(rc, (self._lib.mcf_last_error(None) or b"").decode())
+        if report is not None:
+            report.update(rep.as_dict())
+        return [self._wrap(ctypes.c_void_p(out[i])) for i in range(count)]
+
     def last_error(self) -> str:
         return (self._lib.mcf_last_error(self._h) or b"").decode()
 
@@ -780,6 +820,26 @@ def dimacs_load(path: str):
         raise InvalidProblemError(err.value.decode())
     k = m.value
     return n.value, tail[:k], head[:k], lower[:k], cap[:k], cost[:k], supply
+
+
+def restore(engines, src: McfEngine) -> dict:
+    """Bring ``engines`` -- existing engines of ``src``'s shape, e.g. its earlier forks -- back to ``src``'s resident state
+    without allocating (``mcf_restore``).  Returns the fields of ``mcf_fork_report``."""
+    engines = list(engines)
+    lib = src._lib
+    if not hasattr(lib, "mcf_restore"):
+        raise EngineUnavailableError(f"{LIB_PATH} does not export mcf_restore (a library built from an earlier commit)")
+    hs = (ctypes.c_void_p * max(len(engines), 1))(*[e._h.value if e is not None and e._h is not None else None for e in engines])
+    rep = McfForkReport()
+    src._check(lib.mcf_restore(hs, len(engines), src._h, ctypes.byref(rep)))
+    for e in engines:
+        e.n, e.m, e.rule, e.key_mode = src.n, src.m, src.rule, src.key_mode
+        e.tail, e.head, e.cost, e.cap, e.supply = src.tail, src.head, src.cost, src.cap, src.supply
+        e._arc_priority = src._arc_priority
+        e._cost_private = e._rhs_private = False
+    if engines:
+        src._cost_private = src._rhs_private = False
+    return rep.as_dict()
 
 
 def solve_batch(engines, max_pivots=None) -> float:

@@ -363,6 +363,30 @@ def map_rhs_changes(flat: FlatProblem, supplies, capacities, tolerance: float):
     return s_idx, s_int, s_val, c_idx, c_int, c_val
 
 
+SCENARIO_KEYS = ("costs", "supplies", "capacities")
+
+
+def map_scenario(flat: FlatProblem, scenario, tolerance: float) -> dict:
+    """One what-if scenario -> the integer edit arrays of its parts.  ``scenario`` is a mapping with any of ``costs``,
+    ``supplies``, ``capacities``, each in the format of the matching ``NetworkSimplex.update_*`` method (``map_cost_changes``,
+    ``map_rhs_changes``); an empty scenario is an empty cost change.  Returns ``{"costs": map_cost_changes(...) or None,
+    "supplies": map_rhs_changes(flat, supplies, None, ...) or None, "capacities": map_rhs_changes(flat, None, capacities, ...)
+    or None}``.  Pure, no device: an unknown key or an invalid edit raises ``InvalidProblemError`` and nothing is returned."""
+    if not hasattr(scenario, "keys"):
+        raise InvalidProblemError("a scenario is a mapping with any of 'costs', 'supplies', 'capacities'")
+    unknown = [k for k in scenario.keys() if k not in SCENARIO_KEYS]
+    if unknown:
+        raise InvalidProblemError(f"scenario has unknown key {unknown[0]!r}; known: {', '.join(SCENARIO_KEYS)}")
+    out = {"costs": None, "supplies": None, "capacities": None}
+    if scenario.get("costs") is not None:
+        out["costs"] = map_cost_changes(flat, scenario["costs"], tolerance)
+    if scenario.get("supplies") is not None:
+        out["supplies"] = map_rhs_changes(flat, scenario["supplies"], None, tolerance)
+    if scenario.get("capacities") is not None:
+        out["capacities"] = map_rhs_changes(flat, None, scenario["capacities"], tolerance)
+    return out
+
+
 def map_arc_additions(flat: FlatProblem, arcs, tolerance: float, directed: bool = True) -> dict:
     """New arcs in the caller's terms -> the engine's arrays, by flatten's own per-arc transformation: cost and flow scales of
     the resident instance, the lower-bound shift (simplex.py:403-428), the undirected expansion (data.py:162-223).  Pure:
@@ -624,6 +648,20 @@ class NetworkSimplex:
             return True
         self.logger.warning(f"{self.engine.last_error()}. Falling back to cold start.")
         return False
+
+    def fork(self, count: int = 1) -> list["NetworkSimplex"]:
+        """``count`` solvers on forked engines (``mcf_fork``): each holds a complete copy of this solver's resident state, made on
+        the device, and goes on exactly as this one would -- edit and re-solve it without touching this one.  ``flat``,
+        ``problem`` and the maps are shared by reference (the update methods replace them, they never mutate them); the next
+        ``solve()`` of a fork reports the pivots of that call.  Close a fork's engine when done (``fork.engine.close()``)."""
+        out = []
+        for eng in self.engine.fork(count):
+            sv = copy.copy(self)
+            sv.engine = eng
+            sv.stats = dict(self.stats)
+            sv._engine_kwargs = dict(self._engine_kwargs)
+            out.append(sv)
+        return out
 
     def update_costs(self, changes) -> int:
         """Change arc costs and keep the solved state: the basis that is resident on the device stays, its potentials and

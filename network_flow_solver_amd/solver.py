@@ -4,6 +4,8 @@ from __future__ import annotations
 
 from pathlib import Path
 
+import numpy as np
+
 from .data import Basis, FlowResult, NetworkProblem, ProgressCallback, SoAProblem, SolverOptions
 from .io import load_problem as _load_problem_file
 from .io import save_result as _save_result_file
@@ -82,6 +84,51 @@ def solve_many(problems, options: SolverOptions | None = None, max_iterations: i
         for sv in solvers:
             if sv is not None:
                 sv.engine.close()
+
+
+def solve_scenarios(solver: NetworkSimplex, scenarios, max_iterations: int | None = None, return_exceptions: bool = False) -> list:
+    """What-if scenarios from one solved state: ``solver`` is forked on the device once per scenario (``mcf_fork``), every
+    fork takes its scenario's edits -- a dict with any of ``costs``, ``supplies``, ``capacities`` in the formats of
+    ``update_costs`` / ``update_supplies`` / ``update_capacities``, applied in that order; an empty dict changes nothing -- and
+    the forks are re-solved, side by side in one ``mcf_solve_batch`` where they run as one persistent workgroup.  Result ``k``
+    is the ``FlowResult`` scenario ``k``'s solver returns from ``solve()``; its ``iterations`` are the pivots of the re-solve.
+    ``UnboundedProblemError`` is raised unless ``return_exceptions`` (then it takes the scenario's place).  Every scenario is
+    checked before any fork is made (``map_scenario``); ``solver`` itself is only read.  The reference's counterpart is a
+    loop of re-solves from scratch (examples/sensitivity_analysis_example.py, examples/incremental_resolving_example.py)."""
+    from . import engine as _engine
+    from .simplex import map_scenario
+
+    scenarios = list(scenarios)
+    for sc in scenarios:
+        map_scenario(solver.flat, sc, solver.tolerance)
+    if not scenarios:
+        return []
+    forks = solver.fork(len(scenarios))
+    out: list = [None] * len(scenarios)
+    try:
+        empty = (np.zeros(0, np.int64), np.zeros(0)) if solver.flat.soa else {}
+        for sv, sc in zip(forks, scenarios):
+            if sc.get("costs") is not None or (sc.get("supplies") is None and sc.get("capacities") is None):
+                sv.update_costs(sc["costs"] if sc.get("costs") is not None else empty)
+            if sc.get("supplies") is not None:
+                sv.update_supplies(sc["supplies"])
+            if sc.get("capacities") is not None:
+                sv.update_capacities(sc["capacities"])
+        batched = [k for k, sv in enumerate(forks) if sv.engine.stats()["pricing_mode"] in (2, 3)]
+        if batched:
+            _engine.solve_batch([forks[k].engine for k in batched], [forks[k].default_budget(max_iterations) for k in batched])
+        in_batch = set(batched)
+        for k, sv in enumerate(forks):
+            try:
+                out[k] = sv._collect() if k in in_batch else sv.solve(max_iterations=max_iterations)
+            except Exception as exc:  # noqa: BLE001  (UnboundedProblemError)
+                if not return_exceptions:
+                    raise
+                out[k] = exc
+        return out
+    finally:
+        for sv in forks:
+            sv.engine.close()
 
 
 def load_problem(path: str | Path) -> NetworkProblem:
