@@ -347,11 +347,7 @@ struct McfBlkMeta {
 #define MCF_LOC_SLOT (MCF_LOC_ARENA - 1)
 #define MCF_EXT_FLAG (1 << 24)           // bext: a subtree that starts in the block shrank, rrel is due for re-indexing
 #define MCF_BLK_COPIES 2                 // copy blocks reserved per pivot (a block is cut at most at the hole T2 leaves and at the insertion point)
-#if defined(MCF_NO_BPL)   // A/B build: what do the blocked list's branches cost the dense paths?
-#define MCF_HAS_BPL(v) false
-#else
 #define MCF_HAS_BPL(v) ((v).bmeta[0] != nullptr)
-#endif
 
 // Raw views the core functions operate on (device pointers in the kernels,
 // host pointers in the emulation build).

@@ -137,7 +137,7 @@ __device__ __forceinline__ void block_argmax_all(int64_t& key, int64_t& arc) {
 
 // A value every lane of the wave holds alike.  SCALAR: moved to scalar registers (64-bit values in two halves) -- branches on
 // it are scalar branches, and it costs no vector register across the loop; !SCALAR: left where the compiler has it.
-// (Which of the two the fused LDS loop asks for depends on its width, see SmallScalarControl.)
+// (Which of the two the fused LDS loop asks for depends on its width, see small_scalar_control.)
 template <bool SCALAR> __device__ __forceinline__ int32_t uni32(int32_t x) {
     if constexpr (SCALAR) return __builtin_amdgcn_readfirstlane(x);
     else return x;
@@ -1243,6 +1243,18 @@ __device__ __forceinline__ void arm_ctx(McfCtx* c, int64_t cap) {
     if (c->status == MCF_PIVOT_LIMIT && c->pivots < cap) c->status = MCF_RUNNING;
 }
 
+// Devex: the granule range [bg0, bg1) of the current block; every other rule: all granules
+__device__ __forceinline__ void devex_block_granules(const McfCtx& c, bool devex, int32_t& bg0, int32_t& bg1) {
+    int32_t lo = 0, hi = MCF_GRANULES;
+    if (devex) {
+        const int32_t bg = c.block_granules;
+        lo = (int32_t)c.block_index * bg;
+        if (lo >= MCF_GRANULES) lo = 0;
+        hi = lo + bg < MCF_GRANULES ? lo + bg : MCF_GRANULES;
+    }
+    bg0 = lo; bg1 = hi;
+}
+
 // The candidate-list rule's full sweep done by ONE workgroup (batched persistent loops: no grid to go back to): wave w
 // plays the pricing workgroups w, w + nwaves, ... of the grid sweep -- the same arc sets (workgroup lb * 8 + x: the groups of
 // four arcs g_lo(x) + lb * 256 + [0, 256) + j * nlb * 256 of bucket x, as in k_price_rc / mcf_price_block_of), the same keys,
@@ -1320,13 +1332,8 @@ __device__ __forceinline__ void solve_mid_body(const McfView& g, int32_t rule, M
         // uniform control values are read BEFORE a barrier: lane 0 rewrites them later in this very iteration
         const int32_t status_now = S.ctx.status;
         const int32_t minor_left = S.ctx.minor_left;
-        int32_t bg0 = 0, bg1 = MCF_GRANULES;  // Devex: granule range of the current block
-        if (devex) {
-            const int32_t bg = S.ctx.block_granules;
-            bg0 = (int32_t)S.ctx.block_index * bg;
-            if (bg0 >= MCF_GRANULES) bg0 = 0;
-            bg1 = bg0 + bg < MCF_GRANULES ? bg0 + bg : MCF_GRANULES;
-        }
+        int32_t bg0, bg1;
+        devex_block_granules(S.ctx, devex, bg0, bg1);
         __syncthreads();
         if (status_now != MCF_RUNNING) break;
         MCF_PSTAMP(0);
@@ -1570,47 +1577,24 @@ constexpr int kSmallCycleMaxNodes = 1024;  // node-parallel cycle search up to t
 // Arcs of a head bucket that one lane keeps in registers (tail, head, cost, orig: 4 VGPRs each).  THREADS / 8 lanes share a
 // bucket, so 320 (256 lanes) / 384 (1 024 lanes) arcs per bucket are register-resident -- netgen_8_08a's buckets hold
 // 256 +- 20 -- and the rest of a fuller bucket is priced from LDS.
-// A/B builds of the loop's parts (scripts/stamps_small.py before / after): -DMCF_SMALL_LDS_SWEEP prices every arc from LDS,
-// -DMCF_SMALL_SERIAL_RATIO leaves the ratio tests to lane 0.
-#if defined(MCF_SMALL_LDS_SWEEP)
-constexpr bool kRegSweep = false;
-#else
-constexpr bool kRegSweep = true;
-#endif
+constexpr int small_reg_arcs(int threads) { return threads == 256 ? 10 : 3; }
 // Where every wave keeps its copy of the control block: one wave per SIMD (256 lanes) has 512 vector registers to itself and
 // leaves the control block where the compiler puts it; forced into the ~100 scalar registers, control block, pivot
 // descriptor and the view's pointers do not fit, and their spills (v_writelane / v_readlane inside the loop) cost more than
 // the mailbox did: 5.60 us per pivot against 4.80, the parent's 5.60.  Four waves per SIMD (1 024 lanes) have
 // 128 vector registers each, nearly all in use: there the control block goes to scalar registers, or it would spill to
 // scratch memory.
-template <int THREADS> struct SmallScalarControl { static constexpr bool value = THREADS > 256; };
-template <int THREADS> struct SmallRegArcs { static constexpr int value = THREADS <= 256 ? 10 : (THREADS <= 512 ? 5 : 3); };
+constexpr bool small_scalar_control(int threads) { return threads > 256; }
 // Dantzig with the plain sweep deals the arcs evenly, not per head bucket (mcf_core.h: mcf_even_arc): lane t prices the engine
 // arcs bucket_off[0] + t + slot * THREADS.  netgen_8_08a's buckets hold 229 .. 299 arcs -- 8 .. 10 slots of 32 lanes, so every
 // wave ran all ten unrolled slots -- where 2 048 arcs over 256 lanes are 8.  The front kernels' loop is compiled for two slot
-// counts, kReg and SmallRegArcsFew (2 048 arcs' worth), and the launch's constant arc count picks one (mcf_even_reg_slots: a
-// uniform branch).  In the front kernels only, where the deal is a compile-time constant: in the general kernels -- Dantzig with
-// 64-bit keys beside Devex and the candidate list, which keeps the deal per bucket since its list is each bucket's best -- the
-// stride becomes a run-time value, and Devex and the candidate list, which never deal evenly, measured 1.5 - 3 % slower over
-// whole solves with it; they keep the deal per bucket and the one sweep of kReg slots.
-// A/B builds: -DMCF_SMALL_BUCKET_DEAL deals per bucket in every kernel, as before; -DMCF_SMALL_EVEN_GENERAL deals evenly under
-// Dantzig in the general kernels too; -DMCF_SMALL_EVEN_ALL_SLOTS deals evenly but always runs kReg slots.
-template <int THREADS, bool FRONT> struct SmallEvenDeal {
-#if defined(MCF_SMALL_BUCKET_DEAL)
-    static constexpr bool value = false;
-#elif defined(MCF_SMALL_EVEN_GENERAL)
-    static constexpr bool value = true;
-#else
-    static constexpr bool value = FRONT;
-#endif
-};
-#if defined(MCF_SMALL_EVEN_ALL_SLOTS)
-template <int THREADS, bool FRONT> struct SmallRegArcsFew { static constexpr int value = SmallRegArcs<THREADS>::value; };
-#else
-template <int THREADS, bool FRONT> struct SmallRegArcsFew {
-    static constexpr int value = !FRONT ? SmallRegArcs<THREADS>::value : (THREADS <= 256 ? 8 : (THREADS <= 512 ? 4 : 2));
-};
-#endif
+// counts, small_reg_arcs and small_reg_arcs_few (2 048 arcs' worth), and the launch's constant arc count picks one
+// (mcf_even_reg_slots: a uniform branch).  In the front kernels only, where the deal is a compile-time constant: in the general
+// kernels -- Dantzig with 64-bit keys beside Devex and the candidate list, which keeps the deal per bucket since its list is each
+// bucket's best -- the stride becomes a run-time value, and Devex and the candidate list, which never deal evenly, measured
+// 1.5 - 3 % slower over whole solves with it (profiles/small_loop_regs_whole_solves.txt); they keep the deal per
+// bucket and the one sweep of small_reg_arcs slots.
+constexpr int small_reg_arcs_few(int threads, bool front) { return !front ? small_reg_arcs(threads) : (threads == 256 ? 8 : 2); }
 template <int N> struct SmallSlots { static constexpr int value = N; };
 
 template <int THREADS>
@@ -1670,44 +1654,32 @@ struct SmallCycleAcc {
 // common ancestor at every pivot: the passes run over the real nodes only, one pass instead of two at 256 real nodes and 256
 // lanes.  At 256 lanes only: at 1 024 lanes, where 257 tree nodes are one pass either way, the kernels without the join measured
 // 80 - 470 cycles per pivot SLOWER than with it (profiles/small_loop_back_stamps.txt), so they keep it.
-// A/B build: -DMCF_SMALL_JOIN files the common ancestors, looks the join up and passes over the root at every width, as before.
-#if defined(MCF_SMALL_JOIN)
-template <int THREADS> struct SmallSearchJoin { static constexpr bool value = true; };
-#else
-template <int THREADS> struct SmallSearchJoin { static constexpr bool value = THREADS != 256; };
-#endif
+constexpr bool small_search_join(int threads) { return threads != 256; }
 
 // Ratio test of one side over res[0 .. n), by all 64 lanes of a wave.  !LAST: strictly smaller wins, the lowest index among
 // equal residuals (d = MCF_INF, k = -1 when nothing is below MCF_INF); LAST: smaller or equal wins, the highest index.
 // A side whose residuals are all MCF_INF or below 2^32 - 1 (mcf_ratio_narrow_ok; one ballot over all its strides makes that a
 // uniform test) is reduced on 32-bit keys: one v_min_u32 with a DPP operand per step where the 64-bit reduction takes two moves,
 // a 64-bit compare and two selects.  Lanes past the end hold the key of MCF_INF and stay out of the winner's ballot.  Any other
-// side takes the 64-bit reduction; d and k are the same either way.  A/B build: -DMCF_SMALL_RATIO64 never takes the 32-bit path.
-#if defined(MCF_SMALL_RATIO64)
-constexpr bool kRatioNarrow = false;
-#else
-constexpr bool kRatioNarrow = true;
-#endif
+// side takes the 64-bit reduction; d and k are the same either way (profiles/small_loop_reduce_stamps.txt).
 template <bool LAST>
 __device__ __forceinline__ void small_ratio_side(const int64_t* res, int32_t n, int64_t* d_out, int32_t* k_out) {
     const int32_t lane = (int32_t)(threadIdx.x & 63);
     int64_t d = MCF_INF;
     int32_t k = -1;
-    if (kRatioNarrow) {
-        const int64_t r0 = lane < n ? res[lane] : MCF_INF;
-        bool wide = !mcf_ratio_narrow_ok(r0);
-        for (int32_t i = 64 + lane; i < n; i += 64) wide |= !mcf_ratio_narrow_ok(res[i]);
-        if (__ballot(wide) == 0) {
-            for (int32_t base = 0; base < n; base += 64) {   // (uniform, as below)
-                const int32_t i = base + lane;
-                const uint32_t key = mcf_ratio_key32(base == 0 ? r0 : (i < n ? res[i] : MCF_INF));
-                const uint32_t mn = mcf_wave_min_u32(key);
-                const uint64_t mask = __ballot(i < n && key == mn);
-                mcf_ratio_take<LAST>(mcf_ratio_unkey32(mn), mask, base, d, k);
-            }
-            *d_out = d; *k_out = k;
-            return;
+    const int64_t r0 = lane < n ? res[lane] : MCF_INF;
+    bool wide = !mcf_ratio_narrow_ok(r0);
+    for (int32_t i = 64 + lane; i < n; i += 64) wide |= !mcf_ratio_narrow_ok(res[i]);
+    if (__ballot(wide) == 0) {
+        for (int32_t base = 0; base < n; base += 64) {   // (uniform, as below)
+            const int32_t i = base + lane;
+            const uint32_t key = mcf_ratio_key32(base == 0 ? r0 : (i < n ? res[i] : MCF_INF));
+            const uint32_t mn = mcf_wave_min_u32(key);
+            const uint64_t mask = __ballot(i < n && key == mn);
+            mcf_ratio_take<LAST>(mcf_ratio_unkey32(mn), mask, base, d, k);
         }
+        *d_out = d; *k_out = k;
+        return;
     }
     for (int32_t base = 0; base < n; base += 64) {   // (uniform; one trip unless the path is longer than a wave)
         const int32_t i = base + lane;
@@ -1724,19 +1696,15 @@ __device__ __forceinline__ void small_ratio_side(const int64_t* res, int32_t n, 
 // depth with selects on `au`, computes ONE residual -- the arc loses flow when (up arc) == (first side) -- and stores once: the same
 // words with the same values as one branch per side, but a wave that holds ancestors of both end points no longer runs two
 // bodies one after the other.  At 256 lanes only: the 1 024-lane front kernel measured 135 cycles per pivot SLOWER with it
-// (profiles/small_loop_reduce_stamps.txt).  A/B build: -DMCF_SMALL_TWO_BRANCHES keeps one branch per side at every width.
-#if defined(MCF_SMALL_TWO_BRANCHES)
-template <int THREADS> struct SmallSearchOneBranch { static constexpr bool value = false; };
-#else
-template <int THREADS> struct SmallSearchOneBranch { static constexpr bool value = THREADS == 256; };
-#endif
+// (profiles/small_loop_reduce_stamps.txt), and keeps one branch per side.
+constexpr bool small_search_one_branch(int threads) { return threads == 256; }
 
 // `cy` as mcf_pivot_begin_t<true> left it (in registers, uniform); on return the finished cycle, uniform in every wave.
 template <int THREADS>
 __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycleAcc& A, int64_t* scratch, McfCycle& cy) {
-    constexpr bool kScalar = SmallScalarControl<THREADS>::value;
-    constexpr bool kSearchJoin = SmallSearchJoin<THREADS>::value;
-    constexpr bool kSearchOneBranch = SmallSearchOneBranch<THREADS>::value;
+    constexpr bool kScalar = small_scalar_control(THREADS);
+    constexpr bool kSearchJoin = small_search_join(THREADS);
+    constexpr bool kSearchOneBranch = small_search_one_branch(THREADS);
     const McfCtx* c = v.ctx;   // (the caller's registers)
     const int32_t* pcur = c->cur ? v.posbuf[1] : v.posbuf[0];
     const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth;
@@ -1792,12 +1760,6 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
     int32_t n1 = 0, n2 = 0;
     int64_t d1, d2;
     int32_t k1, k2;
-#if defined(MCF_SMALL_SERIAL_RATIO)   // A/B build: the counts and both ratio tests as scalar loops (every lane alike)
-    for (int32_t q = 0; q < THREADS / 64; ++q) { n1 += A.c1[q]; n2 += A.c2[q]; }
-    d1 = MCF_INF; d2 = MCF_INF; k1 = -1; k2 = -1;
-    for (int32_t i = 0; i < n1; ++i) { const int64_t r = res1[i]; if (r < d1) { d1 = r; k1 = i; } }
-    for (int32_t i = 0; i < n2; ++i) { const int64_t r = res2[i]; if (r <= d2) { d2 = r; k2 = i; } }
-#else
     {
         constexpr int kWaves = THREADS / 64;
         const int32_t lane = (int32_t)(threadIdx.x & 63);
@@ -1809,7 +1771,6 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         small_ratio_side<false>(res1, n1, &d1, &k1);
         small_ratio_side<true>(res2, n2, &d2, &k2);
     }
-#endif
     cy.d1 = uni64<kScalar>(d1); cy.k1 = uni32<kScalar>(k1); cy.d2 = uni64<kScalar>(d2); cy.k2 = uni32<kScalar>(k2);
     cy.n1 = n1; cy.n2 = n2;
     if (kSearchJoin) {
@@ -1885,56 +1846,11 @@ __device__ __forceinline__ void half_wave_argmax(int64_t& key, int64_t& arc) {
 }
 
 // ---- the front of a pivot on the plain register sweep: 32-bit keys, and an arg-max that hands the candidate over.
-// A/B builds (scripts/stamps_small.py): -DMCF_SMALL_NO_NARROW never takes the 32-bit sweep, -DMCF_SMALL_NO_HANDOVER keeps
-// block_argmax_all and begin's look-ups, -DMCF_SMALL_NO_WX hands the record over but lets begin look the arc up all the same.
-#if defined(MCF_SMALL_NO_NARROW)
-constexpr bool kNarrowSweep = false;
-#else
-constexpr bool kNarrowSweep = true;
-#endif
-#if defined(MCF_SMALL_NO_HANDOVER)
-constexpr bool kHandover = false;
-#else
-constexpr bool kHandover = true;
-#endif
-#if defined(MCF_SMALL_NO_WX)
-constexpr bool kBeginWx = false;
-#else
-constexpr bool kBeginWx = true;
-#endif
-// The front kernel's arg-max.  A/B build: -DMCF_SMALL_ARGMAX64 reduces the packed key in one 64-bit max per wave, not in 32-bit
-// stages.
-#if defined(MCF_SMALL_ARGMAX64)
-constexpr bool kArgmaxStaged = false;
-#else
-constexpr bool kArgmaxStaged = true;
-#endif
-// ---- the back of a pivot.  A/B builds: -DMCF_SMALL_NO_BESIDE runs the finish pass on all lanes and the apply pass behind a
-// barrier, from the segment table; -DMCF_SMALL_FRONT_WEIGHT leaves the Devex pointers of the front kernel's view to the run time.
-#if defined(MCF_SMALL_NO_BESIDE)
-constexpr bool kFinishBeside = false;
-#else
-constexpr bool kFinishBeside = true;
-#endif
-#if defined(MCF_SMALL_FRONT_WEIGHT)
-constexpr bool kFrontNoDevex = false;
-#else
-constexpr bool kFrontNoDevex = true;
-#endif
 // The pivot descriptor in the LDS image: at 256 lanes the general kernel carries it in registers across the loop and lane 0 stores
 // it once behind the loop (small_desc_store_all: -280 to -340 cycles per pivot under Devex and the candidate list, 0 B scratch);
 // the front kernel keeps lane 0's per-pivot stores (small_desc_store: -85 there, inside the repeat spread), and so do the
-// 1 024-lane kernels, where carrying it spilled.  A/B builds: -DMCF_SMALL_DESC_PER_PIVOT stores per pivot in every
-// kernel, -DMCF_SMALL_DESC_ONCE once in the 256-lane front kernel too.
-template <int THREADS, bool FRONT> struct SmallDescOnce {
-#if defined(MCF_SMALL_DESC_PER_PIVOT)
-    static constexpr bool value = false;
-#elif defined(MCF_SMALL_DESC_ONCE)
-    static constexpr bool value = THREADS == 256;
-#else
-    static constexpr bool value = THREADS == 256 && !FRONT;
-#endif
-};
+// 1 024-lane kernels, where carrying it spilled (profiles/small_loop_back_stamps.txt).
+constexpr bool small_desc_once(int threads, bool front) { return threads == 256 && !front; }
 // What a lane remembers of its best arc besides the key: end points and slot in one word -- tail | head << 11 | slot << 22,
 // slot q = the lane's q-th arc, engine index r_lo + q * r_step (the lanes' stride: THREADS under the even deal) -- the invariant
 // part precomputed per register arc; bit 31 is the state's sign (set: -1, the arc sits at capacity).  11 bits per node and 9 per slot cover every instance of the LDS plan
@@ -2034,27 +1950,11 @@ template <bool SCALAR> __device__ __forceinline__ void uni_cycle(McfCycle& y) {
     y.r0u = uni_node<SCALAR>(y.r0u); y.r0w = uni_node<SCALAR>(y.r0w); y.small = uni32<SCALAR>(y.small);
 }
 
-// The whole solve of one LDS-resident instance by one workgroup of THREADS lanes (k_solve_small: one instance per launch;
-// k_solve_small_batch: one instance per workgroup of the launch)
-// FRONT: the kernel of a Dantzig solve with the plain key whose reduced costs fit 32 bits (small_front_for on the host) -- the
-// narrow register sweep, the arg-max that hands the winner over, begin in one round trip; rule, sweep and key width are
-// compile-time constants there.  !FRONT: every other rule, key mode and range, with 64-bit keys.  Two kernels, not one kernel
-// with a per-launch switch: with both fronts in one loop the 64-bit path, Devex and the candidate list all lost 2 - 5 %
-// (profiles/small_loop_front_stamps.txt, DESIGN.md).
-template <int THREADS, bool FRONT>
-__device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLayout& L, int32_t rule_in,
-                                                 McfCand* __restrict__ list, int64_t cap, char* smem, McfCtx* host_ctx) {
-    const int32_t rule = FRONT ? (int32_t)MCF_RULE_DANTZIG : rule_in;
-#ifdef MCF_STAMPS
-    unsigned long long stamps_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last_ = __builtin_amdgcn_s_memtime();
-    unsigned long long last_wave_ = 0;
-    if (threadIdx.x == 0) { for (int i = 0; i < 24; ++i) mcf_stamp_acc[i] = 0; mcf_stamp_last = last_; }
-#endif
-    const uint32_t m_pad4 = (uint32_t)((g.m + 1023) / 1024 * 1024) * 4u;
-    const uint32_t m_padb = m_pad4 >> 2;
-    const uint32_t N = (uint32_t)g.n_nodes;
-    const uint32_t arcw_b = (uint32_t)(g.m + N - 1) * 16u;
+// ------------------------------------------------------------------ the stages of solve_small_body, in the order it runs them
+// The view of the LDS image: every array the loop follows points into `smem`; what it never follows is nulled, which folds
+// the branches on it away.
+template <bool FRONT>
+__device__ __forceinline__ McfView small_map_view(const McfView& g, const SmallLayout& L, char* smem) {
     McfView v = g;
     v.tail = reinterpret_cast<const int32_t*>(smem + L.tail);
     v.head = reinterpret_cast<const int32_t*>(smem + L.head);
@@ -2084,39 +1984,212 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     v.rcache = nullptr; v.adj_off = nullptr;   // (a handle on this path keeps no resident reduced costs, mcf_create: folds their branches away)
     // the front kernel is Dantzig's: no weights, no Devex state (small_front_for refuses a view that carries weights) -- the
     // Devex branches of mcf_pivot_decide and of the finish pass fold away
-    if constexpr (FRONT && kFrontNoDevex) { v.weight = nullptr; v.dx = nullptr; }
+    if constexpr (FRONT) { v.weight = nullptr; v.dx = nullptr; }
+    return v;
+}
 
-    // (All fourteen arrays' loads in flight together -- one fused loop, 4- or 16-byte loads -- was measured SLOWER than these
-    //  plain loops: 131 / 125 us against 117 us per 20-pivot launch.)
-    copy_words<THREADS>(smem + L.tail, g.tail, m_pad4);
-    copy_words<THREADS>(smem + L.head, g.head, m_pad4);
-    copy_words<THREADS>(smem + L.cost, g.cost, m_pad4);
-    copy_words<THREADS>(smem + L.orig, g.orig, m_pad4);
-    copy_words<THREADS>(smem + L.state, g.state, m_padb);
-    if (v.weight) copy_words<THREADS>(smem + L.weight, g.weight, m_pad4);
-    copy_words<THREADS>(smem + L.arcw, g.arcw, arcw_b);
-    copy_words<THREADS>(smem + L.pi, g.pi, N * 8u);
-    copy_words<THREADS>(smem + L.node, g.node, N * 16u);
-    copy_words<THREADS>(smem + L.order0, g.order[0], N * 4u);
-    copy_words<THREADS>(smem + L.order1, g.order[1], N * 4u);
-    copy_words<THREADS>(smem + L.pos0, g.posbuf[0], N * 4u);
-    copy_words<THREADS>(smem + L.pos1, g.posbuf[1], N * 4u);
-    copy_words<THREADS>(smem + L.ctx, g.ctx, (uint32_t)sizeof(McfCtx));
+// The image's arrays, one list for both ways: IN copies all of them into LDS, !IN copies back those a launch can change (the
+// arcs' end points, costs and ids never do).
+// (All fourteen arrays' loads in flight together -- one fused loop, 4- or 16-byte loads -- was measured SLOWER than these
+//  plain loops: 131 / 125 us against 117 us per 20-pivot launch.)
+struct SmallSizes { uint32_t m_pad4, m_padb, N, arcw_b; };   // bytes of a 4-byte and a 1-byte arc array, tree nodes, bytes of arcw
+__device__ __forceinline__ SmallSizes small_sizes(const McfView& g) {
+    SmallSizes z;
+    z.m_pad4 = (uint32_t)((g.m + 1023) / 1024 * 1024) * 4u;
+    z.m_padb = z.m_pad4 >> 2;
+    z.N = (uint32_t)g.n_nodes;
+    z.arcw_b = (uint32_t)(g.m + z.N - 1) * 16u;
+    return z;
+}
+template <int THREADS, bool IN>
+__device__ __forceinline__ void small_copy_image(const McfView& g, const SmallLayout& L, char* smem, bool weights, const SmallSizes& z) {
+    const uint32_t m_pad4 = z.m_pad4, m_padb = z.m_padb, N = z.N, arcw_b = z.arcw_b;
+    auto both = [&](void* glob, uint32_t off, uint32_t bytes) {
+        if (IN) copy_words<THREADS>(smem + off, glob, bytes);
+        else copy_words<THREADS>(glob, smem + off, bytes);
+    };
+    if (IN) {
+        copy_words<THREADS>(smem + L.tail, g.tail, m_pad4);
+        copy_words<THREADS>(smem + L.head, g.head, m_pad4);
+        copy_words<THREADS>(smem + L.cost, g.cost, m_pad4);
+        copy_words<THREADS>(smem + L.orig, g.orig, m_pad4);
+    }
+    both(g.state, L.state, m_padb);
+    if (weights) both(g.weight, L.weight, m_pad4);
+    both(g.arcw, L.arcw, arcw_b);
+    both(g.pi, L.pi, N * 8u);
+    both(g.node, L.node, N * 16u);
+    both(g.order[0], L.order0, N * 4u);
+    both(g.order[1], L.order1, N * 4u);
+    both(g.posbuf[0], L.pos0, N * 4u);
+    both(g.posbuf[1], L.pos1, N * 4u);
+    both(g.ctx, L.ctx, (uint32_t)sizeof(McfCtx));
+}
+
+// Devex: the host-made granule table in LDS (blocks move and resize under the tuner); other rules: whole buckets
+template <int THREADS>
+__device__ __forceinline__ void small_load_granules(const McfView& g, bool devex, int32_t (&gran)[MCF_NUM_BUCKETS][MCF_GRANULES + 1]) {
+    if (devex) {
+        for (int q = threadIdx.x; q < MCF_NUM_BUCKETS * (MCF_GRANULES + 1); q += THREADS)
+            (&gran[0][0])[q] = (&g.dx->gran[0][0])[q];
+    } else if (threadIdx.x < MCF_NUM_BUCKETS) {
+        gran[threadIdx.x][0] = (int32_t)g.bucket_off[threadIdx.x];
+        gran[threadIdx.x][MCF_GRANULES] = (int32_t)g.bucket_off[threadIdx.x + 1];
+    }
+}
+// arcs one sweep prices: over the eight buckets, the arcs below each granule boundary (Devex: the block's share follows from
+// two entries; other rules sweep whole buckets: a constant of the launch)
+__device__ __forceinline__ void small_sum_granules(bool devex, const int32_t (&gran)[MCF_NUM_BUCKETS][MCF_GRANULES + 1],
+                                                   int32_t (&gsum)[MCF_GRANULES + 1]) {
+    if (threadIdx.x <= MCF_GRANULES && (devex || threadIdx.x == 0 || threadIdx.x == MCF_GRANULES)) {
+        int32_t sum = 0;
+        for (int x = 0; x < MCF_NUM_BUCKETS; ++x) sum += gran[x][threadIdx.x];
+        gsum[threadIdx.x] = sum;
+    }
+}
+
+// ---- arg-max (the front kernels), handing the winner over.  32-bit keys: no tie loop; the winning lane writes the wave's
+// slot -- packed key, engine index, info word: 16 bytes.  After the caller's one barrier every wave reads the slots by broadcast
+// and picks the winner itself with plain compares -- no second reduction -- and unpacks the candidate record (wx) begin would
+// otherwise look up.  The slots are rewritten by the next iteration's arg-max, which the apply barrier (or the barrier of an
+// iteration that pivots on nothing) orders behind these reads.
+__device__ __forceinline__ void small_handover_publish(uint64_t nbest, int64_t arc, uint32_t info, SmallWaveSlot* slot) {
+    const int32_t lane = (int32_t)(threadIdx.x & 63), wave = (int32_t)(threadIdx.x >> 6);
+    // in 32-bit stages: the largest violation; if one lane holds it, that lane wins, else the largest ~id among the
+    // lanes that do.  The winner's own packed key IS the 64-bit maximum.
+    const uint32_t vmx = mcf_wave_max_u32(mcf_argmax_viol(nbest));
+    const bool any = vmx != 0;
+    bool win = mcf_argmax_viol(nbest) == vmx;
+    const uint64_t tied = __ballot(win);
+    if (any && (tied & (tied - 1))) {   // (uniform: several lanes share the violation)
+        const uint32_t imx = mcf_wave_max_u32(mcf_argmax_second(nbest, vmx));
+        win = win && (uint32_t)nbest == imx;
+    }
+    if (any ? win : lane == 0) slot[wave] = SmallWaveSlot{any ? nbest : 0, (int32_t)(arc & 0xffffffff), info};
+}
+template <int THREADS>
+__device__ __forceinline__ void small_handover_pick(const SmallWaveSlot* slot, int64_t& key, int64_t& arc, McfCandX& wx) {
+    constexpr int kWaves = THREADS / 64;
+    constexpr bool kScalar = small_scalar_control(THREADS);
+    const int32_t lane = (int32_t)(threadIdx.x & 63);
+    SmallWaveSlot b;
+    if constexpr (kWaves <= 4) {   // one round trip, kWaves reads
+        SmallWaveSlot sl[kWaves];
+#pragma unroll
+        for (int q = 0; q < kWaves; ++q) sl[q] = slot[q];
+        b = sl[0];
+#pragma unroll
+        for (int q = 1; q < kWaves; ++q) if (sl[q].key > b.key) b = sl[q];
+    } else {   // sixteen waves: lane q takes slot q, one more max names the winning lane, scalar lane reads fetch the rest
+        const SmallWaveSlot mine = slot[lane < kWaves ? lane : 0];
+        const uint64_t k = lane < kWaves ? mine.key : 0;
+        b.key = (uint64_t)mcf_wave_max64((int64_t)k);
+        const int32_t w = (int32_t)__builtin_ctzll((unsigned long long)__ballot(k == b.key));
+        b.e = __builtin_amdgcn_readlane(mine.e, w);
+        b.info = (uint32_t)__builtin_amdgcn_readlane((int32_t)mine.info, w);
+    }
+    key = (int64_t)(b.key >> 32);
+    if (key > 0) {
+        wx = small_record(b.info, key, (int32_t)~(uint32_t)b.key, b.e);
+        arc = wx.arc;
+    } else { key = 0; arc = -1; }
+    key = uni64<kScalar>(key); arc = uni64<kScalar>(arc);
+    wx.rc = uni64<kScalar>(wx.rc); wx.tail = uni32<kScalar>(wx.tail); wx.head = uni32<kScalar>(wx.head); wx.state = uni32<kScalar>(wx.state);
+}
+
+// ---- cycle search: the end points as begin read them, uniform, and every running field of the cycle started at them
+template <bool SCALAR> __device__ __forceinline__ void small_cycle_ends(McfCycle& cy) {
+    cy.r0u = uni_node<SCALAR>(cy.r0u); cy.r0w = uni_node<SCALAR>(cy.r0w);
+    cy.ru = cy.r0u; cy.rw = cy.r0w;
+    cy.p0u = uni32<SCALAR>(cy.p0u); cy.p0w = uni32<SCALAR>(cy.p0w);
+    cy.s0u = cy.p0u; cy.s0w = cy.p0w; cy.pu = cy.p0u; cy.pw = cy.p0w; cy.su = cy.p0u; cy.sw = cy.p0w;
+}
+// ---- apply: block permutation of the preorder array + potential shift, the descriptor straight from registers, the
+// sources from the recorded stem (mcf_apply_source_paths)
+template <int THREADS> __device__ __forceinline__ void small_apply(const McfView& v, const McfCtx& cx) {
+    if (!cx.apply) return;
+    const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
+    const McfNode* const srec = cx.pv_result == 1 ? v.rec1 : v.rec2;
+    const int32_t* const spos = cx.pv_result == 1 ? v.ppos1 : v.ppos2;
+    for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one_paths(v, cx, srec, spos, j);
+    for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
+        if (j < lo || j >= hi) mcf_apply_one_paths(v, cx, srec, spos, j);
+}
+
+// ---- at the budget: is any arc still eligible?  (simplex.py:1678-1699; saves the host a pricing pass + three syncs)
+// Three barriers inside, taken by every lane or by none (the status is the LDS image's).
+template <int THREADS> __device__ __forceinline__ void small_budget_check(const McfView& v, const McfView& g, McfCtx* c, int& s_any) {
+    if (c->status == MCF_PIVOT_LIMIT && !c->limit_checked) {
+        if (threadIdx.x == 0) s_any = 0;
+        __syncthreads();
+        int any = 0;
+        for (int64_t i = threadIdx.x; i < g.m && !any; i += THREADS)
+            if (v.state[i] && mcf_violation(v, i) > 0) any = 1;
+        if (any) s_any = 1;
+        __syncthreads();
+        if (threadIdx.x == 0) { if (s_any) c->limit_checked = 1; else c->status = MCF_OPTIMAL; }
+        __syncthreads();
+    }
+}
+
+// The whole solve of one LDS-resident instance by one workgroup of THREADS lanes (k_solve_small: one instance per launch;
+// k_solve_small_batch: one instance per workgroup of the launch)
+// FRONT: the kernel of a Dantzig solve with the plain key whose reduced costs fit 32 bits (small_front_for on the host) -- the
+// narrow register sweep, the arg-max that hands the winner over, begin in one round trip; rule, sweep and key width are
+// compile-time constants there.  !FRONT: every other rule, key mode and range, with 64-bit keys.  Two kernels, not one kernel
+// with a per-launch switch: with both fronts in one loop the 64-bit path, Devex and the candidate list all lost 2 - 5 %
+// (profiles/small_loop_front_stamps.txt, DESIGN.md).
+// ---- control in registers.  Every wave carries the control block itself -- a private McfCtx whose fields live in scalar
+// registers -- and takes every scalar decision of a pivot itself, from broadcast LDS reads: mcf_pivot_begin_t,
+// mcf_pivot_decide, mcf_pivot_finish and mcf_apply_one run on that private copy (v.ctx points to it), the very functions
+// of the other paths.  Nothing goes through an LDS mailbox, no wave waits for lane 0, and the barriers that only ordered
+// "lane 0 wrote, everybody reads" are gone.  The LDS image is written once after the loop.
+// THE RULE that replaces those barriers: between two barriers no wave reads an LDS location that a faster wave can write
+// before the next barrier.  Its instances here:
+//   * the parallel search's residual / by-depth scratch has LDS of its own, not the segment table's (the general finish pass
+//     fills that table; the one that runs here leaves it alone);
+//   * finish and apply run between the SAME two barriers, the finish pass in the last wave (mcf_pivot_finish_t<true>), the
+//     apply pass in every wave (mcf_apply_one_paths), and touch disjoint LDS words.  Finish reads the recorded paths (path /
+//     rec / ppos, ordered by the search barrier) and the descriptor in registers; it writes arcw[].flow, state[], the Devex
+//     weights, node[].size along both sides and node[stem[i]].{parent, pred, size} -- never a depth word, never the segment
+//     table.  Apply reads order[cur] and the same recorded paths (its sources come from them: mcf_apply_source_paths); it
+//     reads and writes pi[] and node[].depth and writes order[cur ^ 1] and pos[cur ^ 1].  A wave that still runs its ratio
+//     tests or decides reads the residual scratch, the per-wave counts and the recorded paths: nothing either pass writes.
+//     The end-of-iteration barrier orders both passes' stores before the next sweep, begin and search;
+//   * the end points' records and positions (r0u / r0w / p0u / p0w) are begin's reads, taken before the search barrier:
+//     the finish pass rewrites node[u_in];
+//   * begin reads arcw[e].flow and state[e], finish writes them: all of begin's reads precede the search barrier;
+//   * an iteration that pivots on nothing (empty Devex block, exhausted list, budget, optimal) takes one barrier before
+//     it continues: the next iteration rewrites the per-wave arg-max slots and the candidate list;
+//   * the front kernel's per-wave slots (key + the winner's record) are written before the arg-max barrier, read right
+//     behind it by every wave, and rewritten only by the next iteration's arg-max: the apply barrier, or the barrier of an
+//     iteration that pivots on nothing, lies between.
+// Rule-specific bookkeeping in memory -- the entering arc's Devex weight and the list of touched weights -- is stored by
+// mcf_pivot_decide with the same value from every lane; nothing reads it before the next barrier.  A tuner step
+// (block_granules / num_blocks) is computed in every wave alike.
+// Every __shared__ variable of the loop is declared here and handed to the stages: the LDS offsets are this function's.
+template <int THREADS, bool FRONT>
+__device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLayout& L, int32_t rule_in,
+                                                 McfCand* __restrict__ list, int64_t cap, char* smem, McfCtx* host_ctx) {
+    static_assert(THREADS == 256 || THREADS == 1024, "the two widths the loop is tuned and instantiated for");
+    const int32_t rule = FRONT ? (int32_t)MCF_RULE_DANTZIG : rule_in;
+#ifdef MCF_STAMPS
+    unsigned long long stamps_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long last_ = __builtin_amdgcn_s_memtime();
+    unsigned long long last_wave_ = 0;
+    if (threadIdx.x == 0) { for (int i = 0; i < 24; ++i) mcf_stamp_acc[i] = 0; mcf_stamp_last = last_; }
+#endif
+    const SmallSizes sizes = small_sizes(g);
+    McfView v = small_map_view<FRONT>(g, L, smem);
+    small_copy_image<THREADS, true>(g, L, smem, v.weight != nullptr, sizes);
     __syncthreads();
     STAMP(0);
 
     McfCtx* const c = v.ctx;   // the LDS image of the control block: read once below, written once after the loop
     if (threadIdx.x == 0) arm_ctx(c, cap);  // (what k_ctl does for the other paths; visible after the barrier below)
-    // Devex: the host-made granule table in LDS (blocks move and resize under the tuner); other rules: whole buckets
     __shared__ int32_t s_gran[MCF_NUM_BUCKETS][MCF_GRANULES + 1];
     const bool devex = !FRONT && rule == MCF_RULE_DEVEX_BLOCK && g.dx;
-    if (devex) {
-        for (int q = threadIdx.x; q < MCF_NUM_BUCKETS * (MCF_GRANULES + 1); q += THREADS)
-            (&s_gran[0][0])[q] = (&g.dx->gran[0][0])[q];
-    } else if (threadIdx.x < MCF_NUM_BUCKETS) {
-        s_gran[threadIdx.x][0] = (int32_t)g.bucket_off[threadIdx.x];
-        s_gran[threadIdx.x][MCF_GRANULES] = (int32_t)g.bucket_off[threadIdx.x + 1];
-    }
+    small_load_granules<THREADS>(g, devex, s_gran);
     // candidate-list rule: the list is the best arc of each head bucket (= of each of the 8 pricing
     // workgroups the three-kernel path would use at this size); minor iterations re-price just
     // those 8 arcs.  The list survives between launches in `list` (global).
@@ -2124,21 +2197,15 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     __shared__ int64_t s_lk[MCF_NUM_BUCKETS], s_la[MCF_NUM_BUCKETS];
     if (listing && threadIdx.x < MCF_NUM_BUCKETS) { s_lk[threadIdx.x] = list[threadIdx.x].key; s_la[threadIdx.x] = list[threadIdx.x].arc; }
     __syncthreads();   // arm_ctx, the granule table and the list -> every lane's reads below and in the loop
-    // arcs one sweep prices: over the eight buckets, the arcs below each granule boundary (Devex: the block's share follows from
-    // two entries; other rules sweep whole buckets: a constant of the launch)
     __shared__ int32_t s_gsum[MCF_GRANULES + 1];
-    if (threadIdx.x <= MCF_GRANULES && (devex || threadIdx.x == 0 || threadIdx.x == MCF_GRANULES)) {
-        int32_t sum = 0;
-        for (int x = 0; x < MCF_NUM_BUCKETS; ++x) sum += s_gran[x][threadIdx.x];
-        s_gsum[threadIdx.x] = sum;
-    }
+    small_sum_granules(devex, s_gran, s_gsum);
     __syncthreads();   // the sums -> every wave's reads (once here, and per sweep under Devex)
-    constexpr bool kScalar = SmallScalarControl<THREADS>::value;
+    constexpr bool kScalar = small_scalar_control(THREADS);
     const int64_t priced_all = uni32<kScalar>(s_gsum[MCF_GRANULES] - s_gsum[0]);
 
     // ---- lane map of the sweep: THREADS / 8 lanes per head bucket, all eight buckets at once
     constexpr int kPer = THREADS / MCF_NUM_BUCKETS;
-    constexpr int kReg = SmallRegArcs<THREADS>::value;
+    constexpr int kReg = small_reg_arcs(THREADS);
     static_assert(kPer == 32 || kPer % 64 == 0, "a head bucket's lanes are half a wave or whole waves");
     const int px = threadIdx.x / kPer, pl = threadIdx.x % kPer;
     const int sweep = FRONT ? (int)kSweepPlain
@@ -2149,11 +2216,11 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     int32_t r_tail[kReg], r_head[kReg], r_cost[kReg], r_orig[kReg];
     uint32_t r_info[kReg];   // (small_info: what the arg-max hands over to begin)
     int32_t r_n = 0;   // slots in use
-    // The front kernels: the even deal over all arcs (SmallEvenDeal, a compile-time constant); the general ones: per head bucket.
+    // The front kernels: the even deal over all arcs (a compile-time constant); the general ones: per head bucket.
     // r_step apart either way, and slot q of a lane is engine arc r_lo + q * r_step.
-    constexpr int kRegFew = SmallRegArcsFew<THREADS, FRONT>::value;
+    constexpr int kRegFew = small_reg_arcs_few(THREADS, FRONT);
     static_assert(kRegFew <= kReg, "the shorter unrolled sweep is a prefix of the longer");
-    const bool even = SmallEvenDeal<THREADS, FRONT>::value && kRegSweep && sweep == kSweepPlain && rule == MCF_RULE_DANTZIG;
+    const bool even = FRONT && sweep == kSweepPlain && rule == MCF_RULE_DANTZIG;
     const int32_t r_step = even ? THREADS : kPer;
     const int32_t r_lo = even ? mcf_even_arc(s_gran[0][0], (int32_t)threadIdx.x, 0, THREADS) : s_gran[px][0] + pl;
     const int32_t r_hi = even ? s_gran[MCF_NUM_BUCKETS - 1][MCF_GRANULES] : s_gran[px][MCF_GRANULES];
@@ -2161,46 +2228,19 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
 #pragma unroll
     for (int k = 0; k < kReg; ++k) {
         const int32_t i = r_lo + k * r_step;
-        const bool on = kRegSweep && sweep == kSweepPlain && i < r_hi;
+        const bool on = sweep == kSweepPlain && i < r_hi;
         r_tail[k] = on ? v.tail[i] : 0; r_head[k] = on ? v.head[i] : 0; r_cost[k] = on ? v.cost[i] : 0; r_orig[k] = on ? v.orig[i] : 0;
         r_info[k] = small_info(r_tail[k], r_head[k], k);
         r_n += on ? 1 : 0;
     }
     // The front (compile-time): 32-bit keys on the plain register sweep, and with them the arg-max that hands the winner's
-    // record to begin.  64-bit keys price, reduce and begin as before.
-    const bool reg_plain = kRegSweep && sweep == kSweepPlain;
+    // record to begin.  64-bit keys price from registers or LDS, reduce with block_argmax_all and let begin look the arc up.
+    const bool reg_plain = sweep == kSweepPlain;
     constexpr bool nar = FRONT;
-    constexpr bool kDescOnce = SmallDescOnce<THREADS, FRONT>::value;
-    constexpr bool hand = FRONT && kHandover;
+    constexpr bool kDescOnce = small_desc_once(THREADS, FRONT);
+    constexpr bool hand = FRONT;
     const int32_t* const pi32 = reinterpret_cast<const int32_t*>(v.pi);   // low words of the potentials
-    // ---- control in registers.  Every wave carries the control block itself -- a private McfCtx whose fields live in scalar
-    // registers -- and takes every scalar decision of a pivot itself, from broadcast LDS reads: mcf_pivot_begin_t,
-    // mcf_pivot_decide, mcf_pivot_finish and mcf_apply_one run on that private copy (v.ctx points to it), the very functions
-    // of the other paths.  Nothing goes through an LDS mailbox, no wave waits for lane 0, and the barriers that only ordered
-    // "lane 0 wrote, everybody reads" are gone.  The LDS image is written once after the loop.
-    // THE RULE that replaces those barriers: between two barriers no wave reads an LDS location that a faster wave can write
-    // before the next barrier.  Its instances here:
-    //   * the parallel search's residual / by-depth scratch has LDS of its own, not the segment table's (the general finish pass
-    //     fills that table; the one that runs here leaves it alone);
-    //   * finish and apply run between the SAME two barriers, the finish pass in the last wave (mcf_pivot_finish_t<true>), the
-    //     apply pass in every wave (mcf_apply_one_paths), and touch disjoint LDS words.  Finish reads the recorded paths (path /
-    //     rec / ppos, ordered by the search barrier) and the descriptor in registers; it writes arcw[].flow, state[], the Devex
-    //     weights, node[].size along both sides and node[stem[i]].{parent, pred, size} -- never a depth word, never the segment
-    //     table.  Apply reads order[cur] and the same recorded paths (its sources come from them: mcf_apply_source_paths); it
-    //     reads and writes pi[] and node[].depth and writes order[cur ^ 1] and pos[cur ^ 1].  A wave that still runs its ratio
-    //     tests or decides reads the residual scratch, the per-wave counts and the recorded paths: nothing either pass writes.
-    //     The end-of-iteration barrier orders both passes' stores before the next sweep, begin and search;
-    //   * the end points' records and positions (r0u / r0w / p0u / p0w) are begin's reads, taken before the search barrier:
-    //     the finish pass rewrites node[u_in];
-    //   * begin reads arcw[e].flow and state[e], finish writes them: all of begin's reads precede the search barrier;
-    //   * an iteration that pivots on nothing (empty Devex block, exhausted list, budget, optimal) takes one barrier before
-    //     it continues: the next iteration rewrites the per-wave arg-max slots and the candidate list;
-    //   * the front kernel's per-wave slots (key + the winner's record) are written before the arg-max barrier, read right
-    //     behind it by every wave, and rewritten only by the next iteration's arg-max: the apply barrier, or the barrier of an
-    //     iteration that pivots on nothing, lies between.
-    // Rule-specific bookkeeping in memory -- the entering arc's Devex weight and the list of touched weights -- is stored by
-    // mcf_pivot_decide with the same value from every lane; nothing reads it before the next barrier.  A tuner step
-    // (block_granules / num_blocks) is computed in every wave alike.
+    // ---- control in registers (see above): a private copy of the control block in every wave
     McfCtx cx = *c;            // (broadcast reads; the fields the loop never touches are dead after this)
     small_ctx_uniform<kScalar>(cx);
     cx.max_pivots = uni64<kScalar>(cx.max_pivots); cx.minor_cap = uni32<kScalar>(cx.minor_cap); cx.auto_tune = uni32<kScalar>(cx.auto_tune);
@@ -2211,16 +2251,12 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     __shared__ McfCycle s_cy;   // the two-lane climb's result (the rare path: shallow end points, trees above kSmallCycleMaxNodes)
     __shared__ int s_ok;
     __shared__ SmallCycleAcc s_acc;
+    __shared__ SmallWaveSlot s_slot[THREADS / 64];               // the handing-over arg-max's per-wave slots (front kernels)
     for (;;) {
         if (cx.status != MCF_RUNNING) break;   // (uniform: every wave leaves together)
         const bool minor = listing && cx.minor_left > 0;
-        int32_t bg0 = 0, bg1 = MCF_GRANULES;  // Devex: granule range of the current block
-        if (devex) {
-            const int32_t bg = cx.block_granules;
-            bg0 = (int32_t)cx.block_index * bg;
-            if (bg0 >= MCF_GRANULES) bg0 = 0;
-            bg1 = bg0 + bg < MCF_GRANULES ? bg0 + bg : MCF_GRANULES;
-        }
+        int32_t bg0, bg1;
+        devex_block_granules(cx, devex, bg0, bg1);
         // ---- price: the arc set of k_price for shard 0 of 1
         int64_t key = 0, arc = -1;
         McfCandX wx;   // the winner's record (hand)
@@ -2290,8 +2326,8 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         STAMP(1);
         // ---- arg-max: (key, arc) uniform in every wave afterwards
         if (listing) {
-            if (!minor) {   // the list: each head bucket's best
-                if constexpr (kPer >= 64) {
+            if (!minor) {
+                if constexpr (kPer >= 64) {   // the list: each head bucket's best
                     constexpr int kWpb = kPer / 64;   // waves per bucket
                     __shared__ int64_t s_wk[THREADS / 64], s_wa[THREADS / 64];
                     wave_argmax(key, arc);
@@ -2320,57 +2356,10 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
                 if (key <= 0) { key = 0; arc = -1; }
             }
             wave_argmax(key, arc);
-        } else if (hand) {
-            // 32-bit keys: one 64-bit max per wave, no tie loop; the winning lane writes the wave's slot -- packed key, engine
-            // index, info word: 16 bytes.  After the one barrier every wave reads the slots by broadcast and picks the winner
-            // itself with plain compares -- no second reduction -- and unpacks the candidate record (wx) begin would otherwise
-            // look up.  The slots are rewritten by the next iteration's arg-max, which the apply barrier (or the barrier of an
-            // iteration that pivots on nothing) orders behind these reads.
-            constexpr int kWaves = THREADS / 64;
-            __shared__ SmallWaveSlot s_slot[kWaves];
-            const int32_t lane = (int32_t)(threadIdx.x & 63), wave = (int32_t)(threadIdx.x >> 6);
-            bool any, win;
-            if constexpr (kArgmaxStaged) {
-                // in 32-bit stages: the largest violation; if one lane holds it, that lane wins, else the largest ~id among the
-                // lanes that do.  The winner's own packed key IS the 64-bit maximum.
-                const uint32_t vmx = mcf_wave_max_u32(mcf_argmax_viol(nbest));
-                any = vmx != 0;
-                win = mcf_argmax_viol(nbest) == vmx;
-                const uint64_t tied = __ballot(win);
-                if (any && (tied & (tied - 1))) {   // (uniform: several lanes share the violation)
-                    const uint32_t imx = mcf_wave_max_u32(mcf_argmax_second(nbest, vmx));
-                    win = win && (uint32_t)nbest == imx;
-                }
-            } else {
-                const uint64_t mx = (uint64_t)mcf_wave_max64((int64_t)nbest);
-                any = (mx >> 32) != 0;
-                win = nbest == mx;
-            }
-            if (any ? win : lane == 0) s_slot[wave] = SmallWaveSlot{any ? nbest : 0, (int32_t)(arc & 0xffffffff), info};
+        } else if constexpr (FRONT) {
+            small_handover_publish(nbest, arc, info, s_slot);
             __syncthreads();   // per-wave slots -> every wave's pick
-            SmallWaveSlot b;
-            if constexpr (kWaves <= 4) {   // one round trip, kWaves reads
-                SmallWaveSlot sl[kWaves];
-#pragma unroll
-                for (int q = 0; q < kWaves; ++q) sl[q] = s_slot[q];
-                b = sl[0];
-#pragma unroll
-                for (int q = 1; q < kWaves; ++q) if (sl[q].key > b.key) b = sl[q];
-            } else {   // sixteen waves: lane q takes slot q, one more max names the winning lane, scalar lane reads fetch the rest
-                const SmallWaveSlot mine = s_slot[lane < kWaves ? lane : 0];
-                const uint64_t k = lane < kWaves ? mine.key : 0;
-                b.key = (uint64_t)mcf_wave_max64((int64_t)k);
-                const int32_t w = (int32_t)__builtin_ctzll((unsigned long long)__ballot(k == b.key));
-                b.e = __builtin_amdgcn_readlane(mine.e, w);
-                b.info = (uint32_t)__builtin_amdgcn_readlane((int32_t)mine.info, w);
-            }
-            key = (int64_t)(b.key >> 32);
-            if (key > 0) {
-                wx = small_record(b.info, key, (int32_t)~(uint32_t)b.key, b.e);
-                arc = wx.arc;
-            } else { key = 0; arc = -1; }
-            key = uni64<kScalar>(key); arc = uni64<kScalar>(arc);
-            wx.rc = uni64<kScalar>(wx.rc); wx.tail = uni32<kScalar>(wx.tail); wx.head = uni32<kScalar>(wx.head); wx.state = uni32<kScalar>(wx.state);
+            small_handover_pick<THREADS>(s_slot, key, arc, wx);
         } else {
             block_argmax_all<THREADS>(key, arc);
         }
@@ -2384,7 +2373,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         // points' records, positions and potentials -- two.  The records the decision will need are fetched here (WITH_CY).
         McfCycle cy;
         bool go;
-        if constexpr (hand && kBeginWx) go = mcf_pivot_begin_t<true>(v, key, arc, rule, &wx, &cy);
+        if constexpr (hand) go = mcf_pivot_begin_t<true>(v, key, arc, rule, &wx, &cy);
         else go = mcf_pivot_begin_t<true>(v, key, arc, rule, nullptr, &cy);
         small_ctx_uniform<kScalar>(cx);
         MCF_PSTAMP(13);
@@ -2394,20 +2383,13 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             STAMP(5);
             continue;
         }
-        cy.r0u = uni_node<kScalar>(cy.r0u); cy.r0w = uni_node<kScalar>(cy.r0w);
-        cy.ru = cy.r0u; cy.rw = cy.r0w;
-        cy.p0u = uni32<kScalar>(cy.p0u); cy.p0w = uni32<kScalar>(cy.p0w);
-        cy.s0u = cy.p0u; cy.s0w = cy.p0w; cy.pu = cy.p0u; cy.pw = cy.p0w; cy.su = cy.p0u; cy.sw = cy.p0w;
+        small_cycle_ends<kScalar>(cy);
         const int32_t deep = cy.r0u.depth > cy.r0w.depth ? cy.r0u.depth : cy.r0w.depth;
         // Cycle search: every lane takes nodes (small_cycle_parallel) while the tree is small enough; else lanes 0 and 1 climb
         // one side each (pivot_climb_2lanes) and every wave reads their result.
         // (end points that hang close to the root -- the first pivots of a cold start -- are climbed: a level or two of
         //  LDS round trips beat the parallel search's fixed cost: 144 K vs 126 K pivots/s over the first 25 pivots)
-#if defined(MCF_SMALL_CLIMB)   // A/B build: always the two-lane climb
-        if (false) {
-#else
         if (v.n_nodes <= kSmallCycleMaxNodes && deep > 3) {
-#endif
             small_cycle_parallel<THREADS>(v, s_acc, scratch, cy);   // (one barrier inside)
             MCF_PSTAMP(15);
             mcf_pivot_decide(v, mcf_view_paths(v), cy);
@@ -2430,38 +2412,16 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         MCF_PSTAMP(16);
         STAMP(3);
         // (no barrier: the finish pass reads the recorded paths, which the search barrier ordered, and the descriptor in registers)
-        if constexpr (kFinishBeside) {
-            // finish and apply between the same two barriers: the LAST wave alone finishes (uniform per wave; the pass needs
-            // n1 + n2 and k + 1 lanes, about ten on netgen_8_08a) while the others apply; it then takes the apply positions from
-            // lo + THREADS - 64 on, which most pivots do not have.  See THE RULE above for why the two never meet.
-            if ((int32_t)threadIdx.x >= THREADS - 64) {
-                MCF_LAST_WAVE_BEGIN();
-                mcf_pivot_finish_t<true>(v, mcf_view_paths(v), (int32_t)threadIdx.x - (THREADS - 64), 64);
-                MCF_LAST_WAVE_STAMP();
-            }
-            STAMP(4);
-            // ---- apply: block permutation of the preorder array + potential shift, the descriptor straight from registers, the
-            // sources from the recorded stem (mcf_apply_source_paths)
-            if (cx.apply) {
-                const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
-                const McfNode* const srec = cx.pv_result == 1 ? v.rec1 : v.rec2;
-                const int32_t* const spos = cx.pv_result == 1 ? v.ppos1 : v.ppos2;
-                for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one_paths(v, cx, srec, spos, j);
-                for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
-                    if (j < lo || j >= hi) mcf_apply_one_paths(v, cx, srec, spos, j);
-            }
-        } else {
-            mcf_pivot_finish(v, mcf_view_paths(v), threadIdx.x, THREADS);
-            __syncthreads();   // the finish pass's segment table and node records -> the apply pass
-            STAMP(4);
-            // ---- apply: block permutation of the preorder array + potential shift, the descriptor straight from registers
-            if (cx.apply) {
-                const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
-                for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one(v, cx, j);
-                for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
-                    if (j < lo || j >= hi) mcf_apply_one(v, cx, j);
-            }
+        // finish and apply between the same two barriers: the LAST wave alone finishes (uniform per wave; the pass needs
+        // n1 + n2 and k + 1 lanes, about ten on netgen_8_08a) while the others apply; it then takes the apply positions from
+        // lo + THREADS - 64 on, which most pivots do not have.  See THE RULE above for why the two never meet.
+        if ((int32_t)threadIdx.x >= THREADS - 64) {
+            MCF_LAST_WAVE_BEGIN();
+            mcf_pivot_finish_t<true>(v, mcf_view_paths(v), (int32_t)threadIdx.x - (THREADS - 64), 64);
+            MCF_LAST_WAVE_STAMP();
         }
+        STAMP(4);
+        small_apply<THREADS>(v, cx);
         __syncthreads();   // the apply pass's order / position / potential / depth stores and the finish pass's flows and states
                            // -> the next iteration's sweep, begin and search
         cx.apply = 0;
@@ -2474,30 +2434,9 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     }
     v.ctx = c;
     __syncthreads();   // the LDS control block -> the budget check and the copy-out
-
-    // at the budget: is any arc still eligible?  (simplex.py:1678-1699; saves the host a pricing pass + three syncs)
-    if (c->status == MCF_PIVOT_LIMIT && !c->limit_checked) {
-        __shared__ int s_any;
-        if (threadIdx.x == 0) s_any = 0;
-        __syncthreads();
-        int any = 0;
-        for (int64_t i = threadIdx.x; i < g.m && !any; i += THREADS)
-            if (v.state[i] && mcf_violation(v, i) > 0) any = 1;
-        if (any) s_any = 1;
-        __syncthreads();
-        if (threadIdx.x == 0) { if (s_any) c->limit_checked = 1; else c->status = MCF_OPTIMAL; }
-        __syncthreads();
-    }
-    copy_words<THREADS>(g.state, smem + L.state, m_padb);
-    if (v.weight) copy_words<THREADS>(g.weight, smem + L.weight, m_pad4);
-    copy_words<THREADS>(g.arcw, smem + L.arcw, arcw_b);
-    copy_words<THREADS>(g.pi, smem + L.pi, N * 8u);
-    copy_words<THREADS>(g.node, smem + L.node, N * 16u);
-    copy_words<THREADS>(g.order[0], smem + L.order0, N * 4u);
-    copy_words<THREADS>(g.order[1], smem + L.order1, N * 4u);
-    copy_words<THREADS>(g.posbuf[0], smem + L.pos0, N * 4u);
-    copy_words<THREADS>(g.posbuf[1], smem + L.pos1, N * 4u);
-    copy_words<THREADS>(g.ctx, smem + L.ctx, (uint32_t)sizeof(McfCtx));
+    __shared__ int s_any;
+    small_budget_check<THREADS>(v, g, c, s_any);   // (three barriers inside, when at the budget)
+    small_copy_image<THREADS, false>(g, L, smem, v.weight != nullptr, sizes);
     // ... and straight into the host's pinned copy: the host then only waits for the stream, no read-back copy
     if (host_ctx) copy_words<THREADS>(host_ctx, smem + L.ctx, (uint32_t)sizeof(McfCtx));
     if (listing && threadIdx.x < MCF_NUM_BUCKETS) list[threadIdx.x] = McfCand{s_lk[threadIdx.x], s_la[threadIdx.x]};
@@ -3234,7 +3173,7 @@ bool small_plan(int64_t m_pad, size_t arcw_count, int32_t n_nodes, bool devex, S
 // reduces over 4 waves instead of 16 and meets 4 arrivals at each barrier; four waves per SIMD (1 024 lanes) hide the LDS round
 // trips of a sweep that reads its arcs from LDS (Devex) and of the passes over a larger tree -- but since every wave takes the
 // scalar decisions of a pivot itself, sixteen waves repeat them on four SIMDs and keep the control block in scalar registers
-// that spill (SmallScalarControl): 256 lanes won at 65, 257 and 514 tree nodes under every rule, by 0.5 to 1.8 us per pivot.
+// that spill (small_scalar_control): 256 lanes won at 65, 257 and 514 tree nodes under every rule, by 0.5 to 1.8 us per pivot.
 // MCF_SMALL_THREADS = 256 / 1024 forces a width, for mcf_solve (read at mcf_create) and for mcf_solve_batch (read at the call).
 int small_threads_forced() {   // 0: no valid MCF_SMALL_THREADS
     if (const char* st = std::getenv("MCF_SMALL_THREADS")) {
@@ -3268,7 +3207,16 @@ int32_t small_narrow_for(const McfHostImage& im, bool allowed) {
 // sets the view's Devex pointers to null at compile time: a view that carries weights never takes it (mcf_create gives weights
 // to MCF_RULE_DEVEX_BLOCK only, so this refuses nothing today -- it states what the kernel relies on).
 bool small_front_for(int32_t narrow, int32_t rule, int32_t key_mode, const McfView& view) {
-    return kNarrowSweep && kRegSweep && narrow != 0 && rule == MCF_RULE_DANTZIG && key_mode == MCF_KEY_PLAIN && !view.weight && !view.dx;
+    return narrow != 0 && rule == MCF_RULE_DANTZIG && key_mode == MCF_KEY_PLAIN && !view.weight && !view.dx;
+}
+// The instantiation for a width (256 unless 1 024 is forced) and a front, one instance per launch / one per workgroup.
+auto small_kernel(int threads, bool front) {
+    if (threads == 1024) return front ? k_solve_small<1024, true> : k_solve_small<1024, false>;
+    return front ? k_solve_small<256, true> : k_solve_small<256, false>;
+}
+auto small_batch_kernel(int threads, bool front) {
+    if (threads == 1024) return front ? k_solve_small_batch<1024, true> : k_solve_small_batch<1024, false>;
+    return front ? k_solve_small_batch<256, true> : k_solve_small_batch<256, false>;
 }
 
 // The dynamic-LDS limit of the fused kernels covers `total` bytes on this device.  (The limit is a property of the kernel,
@@ -3279,13 +3227,11 @@ bool small_reserve(int device, uint32_t total) {
     int& lds_limit = lds_limits[device & 63];
     std::lock_guard<std::mutex> lock(lds_mu);
     if ((int)total <= lds_limit) return true;
-    const void* const fns[] = {reinterpret_cast<const void*>(k_solve_small<256, false>), reinterpret_cast<const void*>(k_solve_small<1024, false>),
-                               reinterpret_cast<const void*>(k_solve_small<256, true>), reinterpret_cast<const void*>(k_solve_small<1024, true>),
-                               reinterpret_cast<const void*>(k_solve_small_batch<256, false>), reinterpret_cast<const void*>(k_solve_small_batch<1024, false>),
-                               reinterpret_cast<const void*>(k_solve_small_batch<256, true>), reinterpret_cast<const void*>(k_solve_small_batch<1024, true>)};
     hipError_t fe = hipSuccess;
-    for (const void* fn : fns)
-        if (fe == hipSuccess) fe = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
+    for (int threads : {256, 1024})
+        for (bool front : {false, true})
+            for (const void* fn : {reinterpret_cast<const void*>(small_kernel(threads, front)), reinterpret_cast<const void*>(small_batch_kernel(threads, front))})
+                if (fe == hipSuccess) fe = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
     if (fe != hipSuccess) { (void)hipGetLastError(); return false; }   // (the refusal must not surface later as some launch's error)
     lds_limit = (int)total;
     return true;
@@ -3999,11 +3945,8 @@ int mcf_solve(mcf_handle* h, int64_t max_pivots, mcf_progress_cb cb, void* user,
             if (h->small) {
                 const int32_t narrow = small_narrow_for(h->im, h->small_narrow_ok);   // (per launch: big-M may have grown)
                 h->stats.small_narrow = narrow;
-                auto kernel = k_solve_small<256, false>;
                 const bool front = small_front_for(narrow, h->opt.rule, h->view.key_mode, h->view);
-                if (h->small_threads == 1024) kernel = front ? k_solve_small<1024, true> : k_solve_small<1024, false>;
-                else if (front) kernel = k_solve_small<256, true>;
-                hipLaunchKernelGGL(kernel, dim3(1), dim3(h->small_threads == 1024 ? 1024 : 256), h->small_layout.total, h->stream, h->view,
+                hipLaunchKernelGGL(small_kernel(h->small_threads, front), dim3(1), dim3(h->small_threads == 1024 ? 1024 : 256), h->small_layout.total, h->stream, h->view,
                                    h->small_layout, h->opt.rule, h->d_cand, cap, h->h_ctx);
             }
             else {
@@ -4204,10 +4147,9 @@ int mcf_solve_batch(mcf_handle* const* handles, int32_t count, const int64_t* ma
         const unsigned n_rest = (unsigned)(small_jobs.size() - n_front);
         const SmallJob* rest = d_small;
         const SmallJob* fronts = d_small + n_rest;
-        auto k_rest = w1024 ? k_solve_small_batch<1024, false> : k_solve_small_batch<256, false>;
-        auto k_front = w1024 ? k_solve_small_batch<1024, true> : k_solve_small_batch<256, true>;
-        if (n_rest) hipLaunchKernelGGL(k_rest, dim3(n_rest), dim3(w1024 ? 1024 : 256), lds, s, rest);
-        if (n_front) hipLaunchKernelGGL(k_front, dim3((unsigned)n_front), dim3(w1024 ? 1024 : 256), lds, s, fronts);
+        const int width = w1024 ? 1024 : 256;
+        if (n_rest) hipLaunchKernelGGL(small_batch_kernel(width, false), dim3(n_rest), dim3(width), lds, s, rest);
+        if (n_front) hipLaunchKernelGGL(small_batch_kernel(width, true), dim3((unsigned)n_front), dim3(width), lds, s, fronts);
     }
     {
         // Two narrow workgroups per CU pay when there are more instances than CUs and the per-pivot passes are short

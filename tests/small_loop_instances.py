@@ -5,7 +5,7 @@ helper like ``planted_pivots.py``: seeded, no fixtures, every result computed on
   511 .. 514 tree nodes are one, two and three passes of a 256-lane workgroup;
 * arc counts around a step of ``m_pad`` (1 024): padded entries must never be priced;
 * a transportation instance whose heads all fall in the FIRST head bucket (nodes 0 .. 31 of 256): the lanes of that bucket price
-  far more arcs than they keep in registers (``SmallRegArcs``: 320 per bucket at 256 lanes, 384 at 1 024), the others none;
+  far more arcs than they keep in registers (``small_reg_arcs``: 320 per bucket at 256 lanes, 384 at 1 024), the others none;
 * netgen-style instances whose first bucket holds 319 .. 321 and 383 .. 385 arcs: the last register slot of a lane is the
   bucket's last arc, one short of it, and one arc goes to the LDS loop;
 * planted pivots whose two cycle sides are 63 .. 65 and 127 .. 129 arcs long -- one and two strides of the 64-lane ratio test --

@@ -18,8 +18,8 @@ import pytest
 
 import __graft_entry__ as ge
 
-# (THREADS, the two compiled slot counts): SmallRegArcsFew of the front kernels / SmallRegArcs of mcf_engine.hip at the two
-# compiled widths; GENERAL: the one sweep of SmallRegArcs slots (few == reg), as -DMCF_SMALL_EVEN_GENERAL / -DMCF_SMALL_EVEN_ALL_SLOTS build it
+# (THREADS, the two compiled slot counts): small_reg_arcs_few of the front kernels / small_reg_arcs of mcf_engine.hip at the two
+# compiled widths; GENERAL: the one sweep of small_reg_arcs slots (few == reg), which no kernel runs under the even deal today
 WIDTHS = ((256, 8, 10), (1024, 2, 3))
 GENERAL = ((256, 10, 10), (1024, 3, 3))
 
@@ -86,10 +86,12 @@ def test_cases_hold_the_edges():
 
 
 def test_constants_are_the_kernels():
-    """WIDTHS restates SmallRegArcs and the front kernels' SmallRegArcsFew: a change there has to show up here."""
+    """WIDTHS restates small_reg_arcs and the front kernels' small_reg_arcs_few: a change there has to show up here."""
     text = (ge.CSRC / "mcf_engine.hip").read_text()
-    assert "struct SmallRegArcs { static constexpr int value = THREADS <= 256 ? 10 : (THREADS <= 512 ? 5 : 3); };" in text
-    assert "static constexpr int value = !FRONT ? SmallRegArcs<THREADS>::value : (THREADS <= 256 ? 8 : (THREADS <= 512 ? 4 : 2));" in text
+    assert "constexpr int small_reg_arcs(int threads) { return threads == 256 ? 10 : 3; }" in text
+    assert ("constexpr int small_reg_arcs_few(int threads, bool front) "
+            "{ return !front ? small_reg_arcs(threads) : (threads == 256 ? 8 : 2); }") in text
+    assert 'static_assert(THREADS == 256 || THREADS == 1024, "the two widths the loop is tuned and instantiated for");' in text
 
 
 def test_bad_arguments_are_refused(host):
