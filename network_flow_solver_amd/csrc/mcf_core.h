@@ -125,6 +125,17 @@ __device__ __forceinline__ uint32_t mcf_wave_min_u32(uint32_t x) {
     x = mcf_dpp_min_u32_step<0x143, 0xc>(x);
     return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
+// Two independent minima side by side: the steps of the two chains alternate, so that neither waits for the other's DPP result.
+__device__ __forceinline__ void mcf_wave_min_u32_pair(uint32_t a, uint32_t b, uint32_t& mn_a, uint32_t& mn_b) {
+    a = mcf_dpp_min_u32_step<0xB1, 0xf>(a);  b = mcf_dpp_min_u32_step<0xB1, 0xf>(b);
+    a = mcf_dpp_min_u32_step<0x4E, 0xf>(a);  b = mcf_dpp_min_u32_step<0x4E, 0xf>(b);
+    a = mcf_dpp_min_u32_step<0x141, 0xf>(a); b = mcf_dpp_min_u32_step<0x141, 0xf>(b);
+    a = mcf_dpp_min_u32_step<0x140, 0xf>(a); b = mcf_dpp_min_u32_step<0x140, 0xf>(b);
+    a = mcf_dpp_min_u32_step<0x142, 0xa>(a); b = mcf_dpp_min_u32_step<0x142, 0xa>(b);
+    a = mcf_dpp_min_u32_step<0x143, 0xc>(a); b = mcf_dpp_min_u32_step<0x143, 0xc>(b);
+    mn_a = (uint32_t)__builtin_amdgcn_readlane((int)a, 63);
+    mn_b = (uint32_t)__builtin_amdgcn_readlane((int)b, 63);
+}
 __device__ __forceinline__ uint32_t mcf_wave_max_u32(uint32_t x) {
     x = mcf_dpp_max_u32_step<0xB1, 0xf>(x);
     x = mcf_dpp_max_u32_step<0x4E, 0xf>(x);
@@ -1338,6 +1349,7 @@ MCF_HD void mcf_pivot_swap(const McfView& v, const McfPaths& pp, const McfCycle&
     const McfNode* srec = result == 1 ? pp.rec1 : pp.rec2;
     const int32_t v_in = result == 1 ? second : first;
     const McfNode rq = srec[k];
+    const int32_t a0 = (result == 1 ? pp.ppos1 : pp.ppos2)[k];   // (beside the record: both hang on k alone -- one round trip)
     const bool tail_in_t2 = (result == 1) == (s > 0);
     c->pv_k = k;
     c->pv_vin = v_in;
@@ -1346,7 +1358,7 @@ MCF_HD void mcf_pivot_swap(const McfView& v, const McfPaths& pp, const McfCycle&
     c->pv_tail_in_t2 = tail_in_t2 ? 1 : 0;
     c->sigma = tail_in_t2 ? -rc : rc;  // potential shift that zeroes the entering arc's reduced cost
 
-    const int32_t S = rq.size, a0 = (result == 1 ? pp.ppos1 : pp.ppos2)[k];
+    const int32_t S = rq.size;
     // v_in is the entering arc's end point on the other side: its record and position were read at the start
     // (selects between loaded fields, not a record loaded through a selected address: a cycle held in registers -- the LDS
     //  loop's -- must not be forced into private memory)
@@ -2076,6 +2088,13 @@ MCF_HD int32_t mcf_apply_one(const McfView& v, const McfCtx& c, int32_t j) {
     }
 }
 
+// A position outside [lo, hi) catches up on what the previous apply changed in the other copy: node `nd` = order[cur][j] stays at j.
+// The one statement of that store: mcf_apply_one_paths below, and the fused LDS loop's apply pass, which reads nd early (small_apply).
+MCF_HD void mcf_apply_catch_up_store(const McfView& v, const McfCtx& c, int32_t j, int32_t nd) {
+    (c.cur ? v.order[0] : v.order[1])[j] = nd;
+    (c.cur ? v.posbuf[0] : v.posbuf[1])[nd] = j;
+}
+
 // mcf_apply_one on the dense layout without position-space sizes, its source from the recorded stem (mcf_apply_source_paths):
 // srec / spos are the leaving arc's side of the paths (pv_result == 1: rec1 / ppos1, else rec2 / ppos2).  Reads order[cur] and
 // the path arrays, reads and writes pi[] and node[].depth, writes order[cur ^ 1] and pos[cur ^ 1] -- no word that
@@ -2092,13 +2111,14 @@ MCF_HD void mcf_apply_one_paths(const McfView& v, const McfCtx& c, const McfNode
         dst[j] = nd;
         pnext[nd] = j;
         if (in_t2) {
-            v.pi[nd] += c.sigma;
-            if (dd) v.node[nd].depth += dd;
+            // both read-modify-writes hang on nd alone: read together, then stored together (the depth word only when it moves)
+            const int64_t pot = v.pi[nd];
+            const int32_t dep = v.node[nd].depth;
+            v.pi[nd] = pot + c.sigma;
+            if (dd) v.node[nd].depth = dep + dd;
         }
     } else {
-        const int32_t nd = src[j];
-        dst[j] = nd;  // catch up on what the previous apply changed in the other copy
-        pnext[nd] = j;
+        mcf_apply_catch_up_store(v, c, j, src[j]);
     }
 }
 

@@ -1626,6 +1626,38 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t 
 #define MCF_LAST_WAVE_BEGIN() do {} while (0)
 #define MCF_LAST_WAVE_STAMP() do {} while (0)
 #endif
+// (diagnostic build: EVERY wave's own clock, from the top of the iteration to where it stands -- slot 0: at the search barrier,
+//  1: behind the ratio tests, 2: behind decide, 3: behind apply (its arrival at the end barrier), 4: behind finish (last wave) --
+//  summed over the pivots that swap or flip; slot 5 (wave 0): one dependent broadcast LDS read, MCF_WAVE_PROBE.  A switch of
+//  its own on top of -DMCF_STAMPS, -DMCF_WAVE_STAMPS: five stamps per wave and pivot cost about 800 cycles of the loop, which
+//  lane 0's phase stamps, compared between builds, must not carry)
+#if defined(MCF_STAMPS) && defined(MCF_WAVE_STAMPS)
+__shared__ unsigned long long mcf_wave_acc[16][6];
+__shared__ unsigned long long mcf_wave_t0[16];
+#define MCF_WAVE_T0() do { if ((threadIdx.x & 63) == 0) mcf_wave_t0[threadIdx.x >> 6] = __builtin_amdgcn_s_memtime(); } while (0)
+#define MCF_WAVE_STAMP(slot)                                                                                                  \
+    do { if ((threadIdx.x & 63) == 0) mcf_wave_acc[threadIdx.x >> 6][slot] += __builtin_amdgcn_s_memtime() - mcf_wave_t0[threadIdx.x >> 6]; } while (0)
+// What one dependent broadcast read costs: three clocks, each waited for, with one LDS read of a uniform address between the
+// second and the third; (c - b) - (b - a) is the read's issue, latency and wait.
+#define MCF_WAVE_PROBE(word)                                                                                                  \
+    do {                                                                                                                      \
+        if (threadIdx.x < 64) {                                                                                               \
+            const unsigned long long a_ = __builtin_amdgcn_s_memtime();                                                       \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                \
+            const unsigned long long b_ = __builtin_amdgcn_s_memtime();                                                       \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                \
+            const int32_t x_ = *reinterpret_cast<const volatile int32_t*>(word);                                              \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(x_) : "memory");                                                        \
+            const unsigned long long c_ = __builtin_amdgcn_s_memtime();                                                       \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                \
+            if (threadIdx.x == 0) mcf_wave_acc[0][5] += (c_ - b_) - (b_ - a_);                                                \
+        }                                                                                                                     \
+    } while (0)
+#else
+#define MCF_WAVE_T0() do {} while (0)
+#define MCF_WAVE_STAMP(slot) do {} while (0)
+#define MCF_WAVE_PROBE(word) do {} while (0)
+#endif
 
 // ------------------------------------------------------------------ node-parallel cycle search (LDS loop)
 // A tree that fits one workgroup's lanes needs no walk at all: lane x asks whether NODE x is an ancestor of the entering arc's
@@ -1639,8 +1671,9 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t 
 // passes at 256 lanes), so the tree need not fit the workgroup; the caller gates on kSmallCycleMaxNodes.
 // After the barrier EVERY wave finishes for itself, uniformly: the per-wave counts are one LDS read per lane summed over scalar
 // lane reads, each side's ratio test is one DPP min reduction per 64 path indices with the winner taken from a ballot -- two
-// independent chains, which overlap -- and the join is two broadcast reads.  The finished cycle is then in every wave's scalar
-// registers: no McfCycle goes through LDS, and nobody waits for wave 0 to publish it.
+// independent chains, which overlap only where the code makes them (small_ratio_together) -- and the join is two broadcast
+// reads.  The finished cycle is then in every wave's scalar registers: no McfCycle goes through LDS, and nobody waits for wave 0
+// to publish it.
 // The end points' positions, depths and records come from the caller's registers (mcf_pivot_begin_t<true> read them): the
 // finish pass of a faster wave may already be rewriting node[u_in] when a slower one gets here.  For the same reason the
 // residuals and the by-depth table have LDS of their own (SmallLayout::scratch, 20 B per tree node) and not the segment
@@ -1699,12 +1732,25 @@ __device__ __forceinline__ void small_ratio_side(const int64_t* res, int32_t n, 
 // (profiles/small_loop_reduce_stamps.txt), and keeps one branch per side.
 constexpr bool small_search_one_branch(int threads) { return threads == 256; }
 
+// Both ratio tests from one round trip behind the search barrier: res1[lane] and res2[lane] are loaded beside the per-wave counts,
+// and when both sides fit one stride of 64 and are narrow (mcf_ratio_narrow_ok) -- one uniform test -- the two 32-bit reductions
+// run as one piece of straight-line code.  One side's load used to wait for the other side's whole reduction, behind the counts'
+// round trip: three dependent trips where the data needs one.  Every other case takes small_ratio_side; winners and ties are
+// mcf_ratio_take's either way.  At both widths: every wave runs the ratio tests for itself, so four waves per SIMD hide nothing of
+// them either -- 1 024 lanes measured -357 / -260 / -276 cycles per pivot under rules 0 / 1 / 2 (profiles/small_loop_trips_stamps.txt).
+constexpr bool small_ratio_together(int threads) { return threads == 256 || threads == 1024; }
+// The search reads a node's whole record at once (see the loop).  At 256 lanes only: at 1 024 it measured nothing (-26 / +9 / +2).
+constexpr bool small_record_once(int threads) { return threads == 256; }
+typedef int small_i32x4 __attribute__((ext_vector_type(4)));
+
 // `cy` as mcf_pivot_begin_t<true> left it (in registers, uniform); on return the finished cycle, uniform in every wave.
 template <int THREADS>
 __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycleAcc& A, int64_t* scratch, McfCycle& cy) {
     constexpr bool kScalar = small_scalar_control(THREADS);
     constexpr bool kSearchJoin = small_search_join(THREADS);
     constexpr bool kSearchOneBranch = small_search_one_branch(THREADS);
+    constexpr bool kRatioTogether = small_ratio_together(THREADS);
+    constexpr bool kRecordOnce = small_record_once(THREADS);
     const McfCtx* c = v.ctx;   // (the caller's registers)
     const int32_t* pcur = c->cur ? v.posbuf[1] : v.posbuf[0];
     const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth;
@@ -1722,7 +1768,13 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         const int32_t x = x0 + (int32_t)threadIdx.x;
         bool h1 = false, h2 = false;
         if (x < nx) {
-            const McfNode rec = v.node[x];
+            // (kRecordOnce) the record as ONE 16-byte read beside the position: an ancestor lane then holds depth, pred and parent
+            // and goes straight to its tree arc, where the fields, read one by one, came in a round trip of their own
+            McfNode rec;
+            if (kRecordOnce) {
+                const small_i32x4 raw = *reinterpret_cast<const small_i32x4*>(&v.node[x]);
+                rec.parent = raw.x; rec.pred = raw.y; rec.size = raw.z; rec.depth = raw.w;
+            } else rec = v.node[x];
             const int32_t px = pcur[x];
             const bool au = (uint32_t)(pu - px) < (uint32_t)rec.size, aw = (uint32_t)(pw - px) < (uint32_t)rec.size;
             if (au && aw) { if (kSearchJoin) by_depth[rec.depth] = x; }
@@ -1755,6 +1807,7 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         n2w += (int32_t)__popcll(__ballot(h2));
     }
     if ((threadIdx.x & 63) == 0) { A.c1[wave] = n1w; A.c2[wave] = n2w; }
+    MCF_WAVE_STAMP(0);
     __syncthreads();   // path / record / residual / by_depth entries and the per-wave counts -> every wave's ratio tests, its
                        // decision and the finish pass
     int32_t n1 = 0, n2 = 0;
@@ -1764,15 +1817,42 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         constexpr int kWaves = THREADS / 64;
         const int32_t lane = (int32_t)(threadIdx.x & 63);
         const int32_t c1 = lane < kWaves ? A.c1[lane] : 0, c2 = lane < kWaves ? A.c2[lane] : 0;   // one read, then scalar lane reads
+        // (kRatioTogether) both sides' first residuals ride in the same round trip as the counts: their addresses do not hang on
+        // the counts, only their masking does.  A lane past the scratch's end reads its last word; past a side's end, a word
+        // the search of an earlier pivot left there, or nothing anybody wrote: either is masked below.
+        const int32_t li = lane < N ? lane : N - 1;
+        int64_t q1 = 0, q2 = 0;
+        if (kRatioTogether) { q1 = res1[li]; q2 = res2[li]; }
 #pragma unroll
         for (int q = 0; q < kWaves; ++q) { n1 += __builtin_amdgcn_readlane(c1, q); n2 += __builtin_amdgcn_readlane(c2, q); }
         // the ratio tests, exactly the climb's: first side -- strictly smaller wins (lowest index among equals), second side --
         // smaller or equal wins (highest index among equals)
-        small_ratio_side<false>(res1, n1, &d1, &k1);
-        small_ratio_side<true>(res2, n2, &d2, &k2);
+        bool both = false;
+        if (kRatioTogether) {
+            const int64_t r1 = lane < n1 ? q1 : MCF_INF, r2 = lane < n2 ? q2 : MCF_INF;
+            // ONE uniform test: both sides fit one stride and are narrow.  Then the two 32-bit reductions are straight-line code
+            // with nothing between them, and their DPP steps interleave.
+            const bool odd = !mcf_ratio_narrow_ok(r1) || !mcf_ratio_narrow_ok(r2);
+            both = n1 <= 64 && n2 <= 64 && __ballot(odd) == 0;
+            if (both) {
+                const uint32_t key1 = mcf_ratio_key32(r1), key2 = mcf_ratio_key32(r2);
+                uint32_t mn1, mn2;
+                mcf_wave_min_u32_pair(key1, key2, mn1, mn2);
+                const uint64_t mask1 = __ballot(lane < n1 && key1 == mn1), mask2 = __ballot(lane < n2 && key2 == mn2);
+                d1 = MCF_INF; k1 = -1; d2 = MCF_INF; k2 = -1;
+                // (an empty side takes nothing, as the loop over its strides: its mask is empty)
+                if (n1 > 0) mcf_ratio_take<false>(mcf_ratio_unkey32(mn1), mask1, 0, d1, k1);
+                if (n2 > 0) mcf_ratio_take<true>(mcf_ratio_unkey32(mn2), mask2, 0, d2, k2);
+            }
+        }
+        if (!both) {   // a side longer than a stride, a wide residual or a negative one
+            small_ratio_side<false>(res1, n1, &d1, &k1);
+            small_ratio_side<true>(res2, n2, &d2, &k2);
+        }
     }
     cy.d1 = uni64<kScalar>(d1); cy.k1 = uni32<kScalar>(k1); cy.d2 = uni64<kScalar>(d2); cy.k2 = uni32<kScalar>(k2);
     cy.n1 = n1; cy.n2 = n2;
+    MCF_WAVE_STAMP(1);
     if (kSearchJoin) {
         const int32_t jn = uni32<kScalar>(by_depth[du0 - n1]);   // the join: the common ancestor right above the first side's path
         const McfNode rj = uni_node<kScalar>(v.node[jn]);        // (the finish pass leaves the join's record alone)
@@ -2106,13 +2186,25 @@ template <bool SCALAR> __device__ __forceinline__ void small_cycle_ends(McfCycle
 }
 // ---- apply: block permutation of the preorder array + potential shift, the descriptor straight from registers, the
 // sources from the recorded stem (mcf_apply_source_paths)
-template <int THREADS> __device__ __forceinline__ void small_apply(const McfView& v, const McfCtx& cx) {
+// The catch-up over [prev_lo, prev_hi) outside [lo, hi) copies order[cur][j] into order[cur ^ 1][j] and pos[cur ^ 1]: other j and
+// other nodes than the first loop's, and order[cur] is written by nobody between these two barriers.  So its first trip's read
+// is issued in front of the first loop (kCatchUpBeside) and only its stores follow it, where the whole loop used to start --
+// with a round trip of its own -- when the first one had ended.  In the 256-lane front kernel only: the general kernel measured
+// some 200 cycles per pivot SLOWER with it under Devex, and 1 024 lanes measured 0 (profiles/small_loop_trips_stamps.txt).
+constexpr bool small_catch_up_beside(int threads, bool front) { return threads == 256 && front; }
+template <int THREADS, bool FRONT> __device__ __forceinline__ void small_apply(const McfView& v, const McfCtx& cx) {
     if (!cx.apply) return;
+    constexpr bool kCatchUpBeside = small_catch_up_beside(THREADS, FRONT);
     const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
     const McfNode* const srec = cx.pv_result == 1 ? v.rec1 : v.rec2;
     const int32_t* const spos = cx.pv_result == 1 ? v.ppos1 : v.ppos2;
+    const int32_t jc = plo + (int32_t)threadIdx.x;   // the catch-up's first trip
+    const bool catch0 = kCatchUpBeside && jc < phi && (jc < lo || jc >= hi);
+    int32_t ndc = 0;
+    if (catch0) ndc = (cx.cur ? v.order[1] : v.order[0])[jc];
     for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one_paths(v, cx, srec, spos, j);
-    for (int32_t j = plo + threadIdx.x; j < phi; j += THREADS)
+    if (catch0) mcf_apply_catch_up_store(v, cx, jc, ndc);
+    for (int32_t j = jc + (kCatchUpBeside ? THREADS : 0); j < phi; j += THREADS)
         if (j < lo || j >= hi) mcf_apply_one_paths(v, cx, srec, spos, j);
 }
 
@@ -2156,6 +2248,9 @@ template <int THREADS> __device__ __forceinline__ void small_budget_check(const 
 //     reads and writes pi[] and node[].depth and writes order[cur ^ 1] and pos[cur ^ 1].  A wave that still runs its ratio
 //     tests or decides reads the residual scratch, the per-wave counts and the recorded paths: nothing either pass writes.
 //     The end-of-iteration barrier orders both passes' stores before the next sweep, begin and search;
+//   * inside the apply pass the catch-up range's read of order[cur] is issued in front of the first loop (small_apply): nobody
+//     writes order[cur] between these two barriers, and the catch-up's stores go to other positions of order[cur ^ 1] and other
+//     nodes of pos[cur ^ 1] than the first loop's;
 //   * the end points' records and positions (r0u / r0w / p0u / p0w) are begin's reads, taken before the search barrier:
 //     the finish pass rewrites node[u_in];
 //   * begin reads arcw[e].flow and state[e], finish writes them: all of begin's reads precede the search barrier;
@@ -2178,6 +2273,9 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     unsigned long long last_ = __builtin_amdgcn_s_memtime();
     unsigned long long last_wave_ = 0;
     if (threadIdx.x == 0) { for (int i = 0; i < 24; ++i) mcf_stamp_acc[i] = 0; mcf_stamp_last = last_; }
+#ifdef MCF_WAVE_STAMPS
+    if (threadIdx.x < 16 * 6) (&mcf_wave_acc[0][0])[threadIdx.x] = 0;
+#endif
 #endif
     const SmallSizes sizes = small_sizes(g);
     McfView v = small_map_view<FRONT>(g, L, smem);
@@ -2254,6 +2352,10 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     __shared__ SmallWaveSlot s_slot[THREADS / 64];               // the handing-over arg-max's per-wave slots (front kernels)
     for (;;) {
         if (cx.status != MCF_RUNNING) break;   // (uniform: every wave leaves together)
+#if defined(MCF_STAMPS) && defined(MCF_WAVE_STAMPS)
+        if ((cx.pivots & 15) == 0) { MCF_WAVE_PROBE(&s_acc.c1[0]); if (threadIdx.x == 64) mcf_wave_acc[1][5] += 1; }   // (the probe delays wave 0: one pivot in 16)
+#endif
+        MCF_WAVE_T0();
         const bool minor = listing && cx.minor_left > 0;
         int32_t bg0, bg1;
         devex_block_granules(cx, devex, bg0, bg1);
@@ -2411,6 +2513,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         if constexpr (!kDescOnce) { if (threadIdx.x == 0) small_desc_store(c, cx, adj2, adj3); }
         MCF_PSTAMP(16);
         STAMP(3);
+        MCF_WAVE_STAMP(2);
         // (no barrier: the finish pass reads the recorded paths, which the search barrier ordered, and the descriptor in registers)
         // finish and apply between the same two barriers: the LAST wave alone finishes (uniform per wave; the pass needs
         // n1 + n2 and k + 1 lanes, about ten on netgen_8_08a) while the others apply; it then takes the apply positions from
@@ -2419,9 +2522,11 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             MCF_LAST_WAVE_BEGIN();
             mcf_pivot_finish_t<true>(v, mcf_view_paths(v), (int32_t)threadIdx.x - (THREADS - 64), 64);
             MCF_LAST_WAVE_STAMP();
+            MCF_WAVE_STAMP(4);
         }
         STAMP(4);
-        small_apply<THREADS>(v, cx);
+        small_apply<THREADS, FRONT>(v, cx);
+        MCF_WAVE_STAMP(3);
         __syncthreads();   // the apply pass's order / position / potential / depth stores and the finish pass's flows and states
                            // -> the next iteration's sweep, begin and search
         cx.apply = 0;
@@ -2448,6 +2553,10 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         for (int i = 0; i < 24; ++i) g_pivot_stamps[i] += mcf_stamp_acc[i];
     }
     if (threadIdx.x == THREADS - 64) reinterpret_cast<unsigned long long*>(g.rec1)[7] = last_wave_;   // (0 when nothing ran beside)
+#ifdef MCF_WAVE_STAMPS
+    if (threadIdx.x < 16 * 6 && (int64_t)g.n_nodes * (int64_t)sizeof(McfNode) >= (8 + 16 * 6) * 8)   // (only where the path scratch holds them)
+        reinterpret_cast<unsigned long long*>(g.rec1)[8 + threadIdx.x] = (&mcf_wave_acc[0][0])[threadIdx.x];
+#endif
 #endif
 }
 
@@ -4577,6 +4686,16 @@ int mcf_debug_stamps(mcf_handle* h, unsigned long long* out8) {
     HIP_TRY(h, hipMemcpy(out8, h->d_rec1, 64, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
+#ifdef MCF_WAVE_STAMPS
+// the fused LDS loop's per-wave clocks: six words per wave, 16 waves (MCF_WAVE_STAMP)
+int mcf_debug_wave_stamps(mcf_handle* h, unsigned long long* out96) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::memset(out96, 0, 16 * 6 * 8);
+    if ((int64_t)h->im.n_nodes * (int64_t)sizeof(McfNode) < (8 + 16 * 6) * 8) return MCF_OK;   // (the kernel wrote none: its guard)
+    HIP_TRY(h, hipMemcpy(out96, reinterpret_cast<const char*>(h->d_rec1) + 64, 16 * 6 * 8, hipMemcpyDeviceToHost));
+    return MCF_OK;
+}
+#endif
 // k_pivot phase stamps (24 slots, [23] = launches that pivoted); clear = 1 zeroes them afterwards
 int mcf_debug_pivot_stamps(mcf_handle* h, unsigned long long* out24, int clear) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));

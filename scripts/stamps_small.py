@@ -1,4 +1,4 @@
-"""Diagnostic: phase shares of the fused small-instance kernel (build with -DMCF_STAMPS)."""
+"""Diagnostic: phase shares of the fused small-instance kernel (build with -DMCF_STAMPS; with -DMCF_WAVE_STAMPS on top, every wave's own clocks)."""
 import ctypes, os, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
@@ -26,4 +26,17 @@ for rule in (0, 1, 2):
     w = np.array(list(out2), dtype=np.float64)
     for n, x in zip(["(to walk start)", "begin", "cycle_init", "climb", "decide"], w[12:17]):
         print(f"      walk/{n:16s} per pivot {x / piv:9.1f}")
+    if hasattr(eng._lib, "mcf_debug_wave_stamps"):   # every wave's own clock from the top of the iteration (an A/B library of an earlier commit lacks it)
+        out3 = (ctypes.c_ulonglong * 96)()
+        eng._lib.mcf_debug_wave_stamps.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]
+        eng._lib.mcf_debug_wave_stamps(eng._h, out3)
+        u = np.array(list(out3), dtype=np.float64).reshape(16, 6)
+        waves = int(os.environ.get("MCF_SMALL_THREADS", "256")) // 64
+        for q in range(waves):
+            print(f"      wave {q:2d} per pivot: at search barrier {u[q, 0] / piv:8.1f}  behind ratio tests {u[q, 1] / piv:8.1f}  behind decide {u[q, 2] / piv:8.1f}"
+                  f"  behind apply {u[q, 3] / piv:8.1f}  behind finish {u[q, 4] / piv:8.1f}")
+        last = int(np.argmax(u[:waves, 3]))
+        print(f"      last at the end barrier: wave {last}, {(u[last, 3] - np.sort(u[:waves, 3])[-2]) / piv:.1f} behind the next")
+        if u[1, 5]:
+            print(f"      one dependent broadcast LDS read: {u[0, 5] / u[1, 5]:.1f} cycles (mean of {int(u[1, 5])} probes)")
     eng.close()
