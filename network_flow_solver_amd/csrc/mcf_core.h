@@ -1495,6 +1495,84 @@ MCF_HD void mcf_pivot_decide(const McfView& v, const McfPaths& pp, const McfCycl
     mcf_pivot_swap(v, pp, cy, result, result == 1 ? k1 : k2, 0);
 }
 
+// mcf_pivot_decide + mcf_pivot_swap once more, for the dense layout without a blocked list and without Devex weights
+// (!MCF_HAS_BPL(v) && !v.weight: the fused LDS loop's front kernels), as one straight line: from the same control block, cycle
+// and path arrays it leaves every byte of the control block that mcf_pivot_decide leaves (tests/test_small_loop_decide_cpu.py
+// compares the two with memcmp).  The three exits -- unbounded, bound flip, swap -- are selects on two flags instead of
+// returns: where the control block lives in vector registers the exits of the branching form leave it in different registers
+// and the point where they meet again copies all of it.  The leaving node's record and position are fetched unconditionally,
+// from index 0 when nobody leaves (the read stays inside the recorded-path arrays and its value is then dropped), so the
+// load's address hangs on two selects only and nothing is branched on before it is issued.
+MCF_HD void mcf_pivot_decide_flat(const McfView& v, const McfPaths& pp, const McfCycle& cy) {
+    McfCtx* c = v.ctx;
+    const int32_t e = c->pv_e, s = c->pv_s, first = c->pv_first, second = c->pv_second;
+    const int64_t d1 = cy.d1, d2 = cy.d2, rc = c->pv_rc;
+    const int32_t n1 = cy.n1, n2 = cy.n2;
+    const int64_t de = c->pv_cap;
+    // the source's tie order: the second side, then the entering arc itself, then the first side
+    const bool take2 = d2 <= de && d2 <= d1;
+    const bool take0 = !take2 && de <= d1;
+    const bool side1 = !take2 && !take0;
+    const int32_t result = take2 ? 2 : (take0 ? 0 : 1);
+    const int64_t delta = take2 ? d2 : (take0 ? de : d1);
+    const int32_t kq = side1 ? cy.k1 : cy.k2;
+    const int32_t k = (take0 || kq < 0) ? 0 : kq;
+    const McfNode rq = (side1 ? pp.rec1 : pp.rec2)[k];
+    const int32_t a0 = (side1 ? pp.ppos1 : pp.ppos2)[k];
+    const bool live = delta < MCF_INF;          // not unbounded (simplex.py:1231-1246)
+    const bool flip = live && take0;            // the entering arc is also the leaving arc (simplex.py:1320-1334)
+    const bool swap = live && !take0;
+
+    c->status = live ? c->status : (int32_t)MCF_UNBOUNDED;
+    c->unbounded_arc = live ? c->unbounded_arc : e;
+    c->degenerate += (live && delta == 0) ? 1 : 0;
+    c->pivots += live ? 1 : 0;
+    c->cycle_arcs += live ? n1 + n2 + 1 : 0;
+    c->pv_n1 = live ? n1 : c->pv_n1;
+    c->pv_n2 = live ? n2 : c->pv_n2;
+    c->pv_delta = live ? delta : c->pv_delta;
+    c->pv_result = live ? result : c->pv_result;
+    c->bound_flips += flip ? 1 : 0;
+
+    // --- basis swap (mcf_pivot_swap with leave_state 0): q = stem[k] on side `result` leaves, T2 = the subtree of q
+    const bool tail_in_t2 = side1 == (s > 0);
+    const int32_t S = rq.size;
+    const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth, zu0 = cy.r0u.size, zw0 = cy.r0w.size;
+    const int32_t vin_depth = side1 ? dw0 : du0, vin_size = side1 ? zw0 : zu0;
+    const int32_t pvin = side1 ? cy.p0w : cy.p0u;
+    const int32_t tA = pvin + 1, tB = pvin + vin_size;
+    const int32_t costA = tA <= a0 ? a0 - tA : tA - (a0 + S);
+    const int32_t costB = tB <= a0 ? a0 - tB : tB - (a0 + S);
+    const int32_t t = costA <= costB ? tA : tB;
+    const int32_t lo = t < a0 ? t : a0, hi = t > a0 + S ? t : a0 + S;
+    c->pv_k = swap ? k : c->pv_k;
+    c->pv_vin = swap ? (side1 ? second : first) : c->pv_vin;
+    c->pv_leave = swap ? (rq.pred >> 1) : c->pv_leave;
+    c->pv_leave_state = swap ? ((((rq.pred & 1) != 0) == side1) ? 1 : -1) : c->pv_leave_state;
+    c->pv_tail_in_t2 = swap ? (tail_in_t2 ? 1 : 0) : c->pv_tail_in_t2;
+    c->sigma = swap ? (tail_in_t2 ? -rc : rc) : c->sigma;
+    c->pv_vin_depth = swap ? vin_depth : c->pv_vin_depth;
+    c->pv_dd0 = swap ? vin_depth + 1 - (side1 ? du0 : dw0) : c->pv_dd0;
+    c->t2_old = swap ? a0 : c->t2_old;
+    c->t2_new = swap ? (t <= a0 ? t : t - S) : c->t2_new;
+    c->t2_size = swap ? S : c->t2_size;
+    c->lo = swap ? lo : c->lo;
+    c->hi = swap ? hi : c->hi;
+    c->nseg = swap ? 2 * k + 1 : c->nseg;
+    c->nchg = swap ? (side1 ? n1 : n2) - k - 1 : c->nchg;
+    c->apply = swap ? 1 : c->apply;
+    c->pending_flip = swap ? 1 : c->pending_flip;
+    c->subtree_nodes += swap ? S : 0;
+    c->nodes_moved += swap ? hi - lo : 0;
+    c->stage = swap ? 2 : (flip ? 1 : c->stage);
+    // T2 = {u_in}: the preview, and the second end point's adjacency range moves to the front when it is the one
+    const bool one = swap && S == 1, move = one && !side1;
+    c->pv_t2n = one ? 1 : c->pv_t2n;
+    c->pv_t2node = one ? (side1 ? first : second) : c->pv_t2node;
+    c->pv_adj[0] = move ? c->pv_adj[2] : c->pv_adj[0];
+    c->pv_adj[1] = move ? c->pv_adj[3] : c->pv_adj[1];
+}
+
 // ---------------------------------------------------------------------------
 // Dual pivots (mcf_update_rhs_dual; the rule is written out in include/mcf.h).  A supply / capacity edit leaves the basis
 // dual feasible -- slack = state * rc >= 0 on every non-basic arc -- while some tree flows leave their bounds.  One dual

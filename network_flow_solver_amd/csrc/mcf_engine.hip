@@ -1678,8 +1678,8 @@ __shared__ unsigned long long mcf_wave_t0[16];
 // finish pass of a faster wave may already be rewriting node[u_in] when a slower one gets here.  For the same reason the
 // residuals and the by-depth table have LDS of their own (SmallLayout::scratch, 20 B per tree node) and not the segment
 // table's, which the finish pass fills.
-struct SmallCycleAcc {
-    int32_t c1[16], c2[16];   // one-sided ancestors per wave, first / second side
+struct alignas(8) SmallCycleAcc {
+    int32_t c[16][2];   // one-sided ancestors per wave, first / second side (side by side: one 8-byte read fetches a wave's pair)
 };
 // The join is not looked for: nothing behind the search reads it (mcf_pivot_decide: d1 / d2 / k1 / k2 / n1 / n2; mcf_pivot_swap:
 // n1 / n2 and the end points' r0 / p0 / s0), so the common ancestors file nothing -- the loads of the look-up folded away on their
@@ -1742,6 +1742,13 @@ constexpr bool small_ratio_together(int threads) { return threads == 256 || thre
 // The search reads a node's whole record at once (see the loop).  At 256 lanes only: at 1 024 it measured nothing (-26 / +9 / +2).
 constexpr bool small_record_once(int threads) { return threads == 256; }
 typedef int small_i32x4 __attribute__((ext_vector_type(4)));
+// The ratio tests' inputs in the one trip they need: lane w fetches wave w's pair of counts with ONE unconditional 8-byte read (the
+// index clamped where an exec mask used to be: two masked reads, each with its own save and restore of exec), both residual loads
+// are in flight before the wait for the counts (left alone the compiler sank them behind the branch on the counts, a second
+// dependent round trip), and the 32-bit keys are made where the narrow test's compares are, so that no lane mask has to live in
+// a VGPR lane across the branch into the straight-line reductions.  At 256 lanes (the 1 024-lane kernels were not measured with it).
+constexpr bool small_ratio_one_trip(int threads) { return threads == 256; }
+typedef int small_i32x2 __attribute__((ext_vector_type(2)));
 
 // `cy` as mcf_pivot_begin_t<true> left it (in registers, uniform); on return the finished cycle, uniform in every wave.
 template <int THREADS>
@@ -1751,6 +1758,7 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
     constexpr bool kSearchOneBranch = small_search_one_branch(THREADS);
     constexpr bool kRatioTogether = small_ratio_together(THREADS);
     constexpr bool kRecordOnce = small_record_once(THREADS);
+    constexpr bool kRatioOneTrip = kRatioTogether && small_ratio_one_trip(THREADS);
     const McfCtx* c = v.ctx;   // (the caller's registers)
     const int32_t* pcur = c->cur ? v.posbuf[1] : v.posbuf[0];
     const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth;
@@ -1806,7 +1814,7 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         n1w += (int32_t)__popcll(__ballot(h1));
         n2w += (int32_t)__popcll(__ballot(h2));
     }
-    if ((threadIdx.x & 63) == 0) { A.c1[wave] = n1w; A.c2[wave] = n2w; }
+    if ((threadIdx.x & 63) == 0) { A.c[wave][0] = n1w; A.c[wave][1] = n2w; }
     MCF_WAVE_STAMP(0);
     __syncthreads();   // path / record / residual / by_depth entries and the per-wave counts -> every wave's ratio tests, its
                        // decision and the finish pass
@@ -1816,13 +1824,22 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
     {
         constexpr int kWaves = THREADS / 64;
         const int32_t lane = (int32_t)(threadIdx.x & 63);
-        const int32_t c1 = lane < kWaves ? A.c1[lane] : 0, c2 = lane < kWaves ? A.c2[lane] : 0;   // one read, then scalar lane reads
+        // one read, then scalar lane reads (of the lanes below kWaves only: the others may hold anything)
+        int32_t c1, c2;
+        if (kRatioOneTrip) {
+            const small_i32x2 cc = *reinterpret_cast<const small_i32x2*>(&A.c[lane < kWaves ? lane : kWaves - 1][0]);
+            c1 = cc.x; c2 = cc.y;
+        } else {
+            c1 = lane < kWaves ? A.c[lane][0] : 0; c2 = lane < kWaves ? A.c[lane][1] : 0;
+        }
         // (kRatioTogether) both sides' first residuals ride in the same round trip as the counts: their addresses do not hang on
         // the counts, only their masking does.  A lane past the scratch's end reads its last word; past a side's end, a word
         // the search of an earlier pivot left there, or nothing anybody wrote: either is masked below.
         const int32_t li = lane < N ? lane : N - 1;
         int64_t q1 = 0, q2 = 0;
         if (kRatioTogether) { q1 = res1[li]; q2 = res2[li]; }
+        // (the counts and both residuals wanted here: all three reads are issued before the one wait)
+        if (kRatioOneTrip) asm volatile("" ::"v"(c1), "v"(c2), "v"(q1), "v"(q2));
 #pragma unroll
         for (int q = 0; q < kWaves; ++q) { n1 += __builtin_amdgcn_readlane(c1, q); n2 += __builtin_amdgcn_readlane(c2, q); }
         // the ratio tests, exactly the climb's: first side -- strictly smaller wins (lowest index among equals), second side --
@@ -1833,9 +1850,10 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
             // ONE uniform test: both sides fit one stride and are narrow.  Then the two 32-bit reductions are straight-line code
             // with nothing between them, and their DPP steps interleave.
             const bool odd = !mcf_ratio_narrow_ok(r1) || !mcf_ratio_narrow_ok(r2);
+            uint32_t key1 = mcf_ratio_key32(r1), key2 = mcf_ratio_key32(r2);
+            if (kRatioOneTrip) asm volatile("" : "+v"(key1), "+v"(key2));   // (made here, beside the narrow test's compares)
             both = n1 <= 64 && n2 <= 64 && __ballot(odd) == 0;
             if (both) {
-                const uint32_t key1 = mcf_ratio_key32(r1), key2 = mcf_ratio_key32(r2);
                 uint32_t mn1, mn2;
                 mcf_wave_min_u32_pair(key1, key2, mn1, mn2);
                 const uint64_t mask1 = __ballot(lane < n1 && key1 == mn1), mask2 = __ballot(lane < n2 && key2 == mn2);
@@ -1926,11 +1944,15 @@ __device__ __forceinline__ void half_wave_argmax(int64_t& key, int64_t& arc) {
 }
 
 // ---- the front of a pivot on the plain register sweep: 32-bit keys, and an arg-max that hands the candidate over.
-// The pivot descriptor in the LDS image: at 256 lanes the general kernel carries it in registers across the loop and lane 0 stores
-// it once behind the loop (small_desc_store_all: -280 to -340 cycles per pivot under Devex and the candidate list, 0 B scratch);
-// the front kernel keeps lane 0's per-pivot stores (small_desc_store: -85 there, inside the repeat spread), and so do the
-// 1 024-lane kernels, where carrying it spilled (profiles/small_loop_back_stamps.txt).
-constexpr bool small_desc_once(int threads, bool front) { return threads == 256 && !front; }
+// The pivot descriptor in the LDS image: at 256 lanes the kernels carry it in registers across the loop and lane 0 stores it once
+// behind the loop (small_desc_store_all: -280 to -340 cycles per pivot under Devex and the candidate list, 0 B scratch; the front
+// kernel 2.90 -> 2.81 us per pivot against the same fourteen stores moved to wave 1, which neither holds the apply positions
+// lo .. lo + 63 nor finishes, and 3.00 with them in wave 0: profiles/small_loop_decide_parts.txt).  The 1 024-lane kernels keep
+// lane 0's per-pivot stores (small_desc_store): carrying the descriptor spilled there (profiles/small_loop_back_stamps.txt).
+constexpr bool small_desc_once(int threads, bool front) { return threads == 256; }
+// The straight-line decide (mcf_pivot_decide_flat: selects where mcf_pivot_decide returns early) where the control block lives in
+// vector registers and the kernel never carries Devex weights: the 256-lane front kernel.
+constexpr bool small_decide_flat(int threads, bool front) { return threads == 256 && front; }
 // What a lane remembers of its best arc besides the key: end points and slot in one word -- tail | head << 11 | slot << 22,
 // slot q = the lane's q-th arc, engine index r_lo + q * r_step (the lanes' stride: THREADS under the even deal) -- the invariant
 // part precomputed per register arc; bit 31 is the state's sign (set: -1, the arc sits at capacity).  11 bits per node and 9 per slot cover every instance of the LDS plan
@@ -2336,6 +2358,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     const bool reg_plain = sweep == kSweepPlain;
     constexpr bool nar = FRONT;
     constexpr bool kDescOnce = small_desc_once(THREADS, FRONT);
+    constexpr bool kDecideFlat = small_decide_flat(THREADS, FRONT);
     constexpr bool hand = FRONT;
     const int32_t* const pi32 = reinterpret_cast<const int32_t*>(v.pi);   // low words of the potentials
     // ---- control in registers (see above): a private copy of the control block in every wave
@@ -2353,7 +2376,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     for (;;) {
         if (cx.status != MCF_RUNNING) break;   // (uniform: every wave leaves together)
 #if defined(MCF_STAMPS) && defined(MCF_WAVE_STAMPS)
-        if ((cx.pivots & 15) == 0) { MCF_WAVE_PROBE(&s_acc.c1[0]); if (threadIdx.x == 64) mcf_wave_acc[1][5] += 1; }   // (the probe delays wave 0: one pivot in 16)
+        if ((cx.pivots & 15) == 0) { MCF_WAVE_PROBE(&s_acc.c[0][0]); if (threadIdx.x == 64) mcf_wave_acc[1][5] += 1; }   // (the probe delays wave 0: one pivot in 16)
 #endif
         MCF_WAVE_T0();
         const bool minor = listing && cx.minor_left > 0;
@@ -2494,7 +2517,8 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         if (v.n_nodes <= kSmallCycleMaxNodes && deep > 3) {
             small_cycle_parallel<THREADS>(v, s_acc, scratch, cy);   // (one barrier inside)
             MCF_PSTAMP(15);
-            mcf_pivot_decide(v, mcf_view_paths(v), cy);
+            if constexpr (kDecideFlat) mcf_pivot_decide_flat(v, mcf_view_paths(v), cy);
+            else mcf_pivot_decide(v, mcf_view_paths(v), cy);
         } else {
             if (threadIdx.x < 2) {
                 const bool ok = pivot_climb_2lanes(v, &s_cy);
