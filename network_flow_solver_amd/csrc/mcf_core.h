@@ -170,6 +170,35 @@ MCF_HD void mcf_ratio_take(int64_t mn, uint64_t mask, int32_t base, int64_t& d, 
 MCF_HD uint32_t mcf_argmax_viol(uint64_t packed) { return (uint32_t)(packed >> 32); }
 MCF_HD uint32_t mcf_argmax_second(uint64_t packed, uint32_t vmx) { return mcf_argmax_viol(packed) == vmx ? (uint32_t)packed : 0u; }
 
+// ---- the narrow register sweep of the fused LDS loop, counted in issue slots (mcf_engine.hip: solve_small_body, small_price_flat).
+// An arc's state s is -1 (at capacity), 0 (in the tree) or +1 (at zero flow) and rc its reduced cost in 32 bits; it is eligible
+// when s != 0 and -s * rc > 0, and that product is its violation.  The two-select form compares twice and waits for VCC twice:
+MCF_HD uint32_t mcf_narrow_violation_selects(int32_t s, int32_t rc) {
+    const int32_t viol = s > 0 ? (int32_t)(0u - (uint32_t)rc) : rc;
+    return (uint32_t)((s != 0 && viol > 0) ? viol : 0);
+}
+// ... the same number without a compare: -s * rc itself, SIGNED, for s in {-1, 0, +1}.  `on` is all ones for s = +-1; n is all ones
+// for s = -1; (x ^ ~n) + n + 1 is x for n = -1 and -x for n = 0.  An arc is eligible exactly when the result is > 0, and a sweep
+// that compares its packed keys as SIGNED 64-bit numbers needs no clamp: a key with a negative high word loses to every start value.
+MCF_HD int32_t mcf_narrow_violation_signed(int32_t s, int32_t rc) {
+    const uint32_t n = (uint32_t)(s >> 31);
+    uint32_t on = (uint32_t)((int32_t)((uint32_t)s << 31) >> 31);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(on));   // (opaque: seen through, the mask becomes a compare and a select again)
+#endif
+    return (int32_t)((((uint32_t)rc & on) ^ ~n) + n + 1u);
+}
+MCF_HD uint32_t mcf_narrow_violation(int32_t s, int32_t rc) {
+    const int32_t v = mcf_narrow_violation_signed(s, rc);
+    return (uint32_t)(v > 0 ? v : 0);
+}
+// The packed key of a slot -- (signed violation << 32) | ~id -- and the order of the sweep: the larger key as a signed 64-bit
+// number.  Among eligible arcs that is mcf_cand_better's order (larger violation, then lower id; ids are distinct, so keys never
+// tie); an ineligible arc's key is at most the start value mcf_narrow_start (violation 0, ~id all ones) and never replaces it.
+// The order is total, so any split of the slots over several accumulators merged by the same compare names the same winner.
+MCF_HD int64_t mcf_narrow_key(int32_t signed_viol, int32_t orig) { return (int64_t)(((uint64_t)(uint32_t)signed_viol << 32) | (uint32_t)~orig); }
+MCF_HD int64_t mcf_narrow_start() { return (int64_t)0xffffffffll; }
+
 // ---- even deal of the Dantzig register sweep (mcf_engine.hip: solve_small_body).  Dantzig's arg-max is over all arcs and
 // (violation, ~id) is a total order, so which lane prices an arc does not matter: lane t of `threads` takes the engine arcs
 // base + t + slot * threads, and a sweep runs mcf_even_slots(arcs, threads) slots -- every lane the same number, the last one
@@ -545,6 +574,41 @@ MCF_HD bool mcf_cand_better(int64_t key, int64_t arc, int64_t bkey, int64_t barc
 }
 
 MCF_HD int64_t mcf_pack_arc(int32_t orig, int64_t engine_idx) { return ((int64_t)orig << 32) | engine_idx; }
+
+// ---- the handing-over arg-max of the fused LDS loop's front kernels (mcf_engine.hip: small_handover_pick).
+// The candidate record of a sweep's winner from what the sweep hands over: the info word (tail | head << 11 | slot << 22, bit
+// 31: the state is -1), the violation -- the key of the plain sweep, so rc = -state * violation, exactly -- and both ids.
+MCF_HD McfCandX mcf_narrow_record(uint32_t info, int64_t viol, int32_t orig, int32_t e) {
+    McfCandX x;
+    x.state = (info >> 31) ? -1 : 1;
+    x.rc = x.state > 0 ? -viol : viol;
+    // mcf_pack_arc(orig, e) for ids >= 0, in unsigned arithmetic: the branch-free pick unpacks the slot of a wave that found
+    // nothing too (id word 0, so "orig" -1) before it discards the result
+    x.arc = (int64_t)(((uint64_t)(uint32_t)orig << 32) | (uint32_t)e);
+    x.tail = (int32_t)(info & 0x7ff); x.head = (int32_t)((info >> 11) & 0x7ff); x.pad = 0;
+    return x;
+}
+// The pick over N per-wave slots, each four words as they lie in LDS -- [0] the packed key's low word (~id), [1] its high word
+// (the violation; 0: that wave found nothing), [2] the engine index, [3] the info word -- without a branch, so that the words can all
+// be loaded before the first compare: the largest packed key wins (ids are distinct: keys with a violation never tie; slot 0
+// stays on equal keys, which are all "nothing"), and the record is unpacked with selects.  Nothing eligible anywhere: key 0, arc
+// -1 and the empty record -- what the loop starts a pivot with.
+template <int N>
+MCF_HD void mcf_narrow_pick(const uint32_t (&w)[N][4], int64_t& key, int64_t& arc, McfCandX& wx) {
+    uint32_t b0 = w[0][0], b1 = w[0][1], b2 = w[0][2], b3 = w[0][3];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int q = 1; q < N; ++q) {
+        const bool up = (((uint64_t)w[q][1] << 32) | w[q][0]) > (((uint64_t)b1 << 32) | b0);
+        b0 = up ? w[q][0] : b0; b1 = up ? w[q][1] : b1; b2 = up ? w[q][2] : b2; b3 = up ? w[q][3] : b3;
+    }
+    const bool any = b1 != 0;
+    const McfCandX r = mcf_narrow_record(b3, (int64_t)b1, (int32_t)~b0, (int32_t)b2);
+    key = (int64_t)b1;
+    arc = any ? r.arc : -1;
+    wx.rc = any ? r.rc : 0; wx.arc = arc; wx.tail = any ? r.tail : 0; wx.head = any ? r.head : 0; wx.state = any ? r.state : 0; wx.pad = 0;
+}
 
 // The pricing workgroup that sweeps engine arc e (k_price_rc / k_price: workgroup lb * 8 + x takes the groups of
 // four arcs  g_lo(x) + lb * 256 + lane + j * nlb * 256  of bucket x), or -1 when e is another rank's arc.

@@ -41,6 +41,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cstddef>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -1626,6 +1627,34 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, uint32_t 
 #define MCF_LAST_WAVE_BEGIN() do {} while (0)
 #define MCF_LAST_WAVE_STAMP() do {} while (0)
 #endif
+// (diagnostic build, -DMCF_SLOT_PROBE=N [-DMCF_SLOT_PROBE_KIND=K]: N further independent instructions behind the arg-max of every
+//  iteration, in every wave -- K = 0: s_nop 0; 1: a v_mov into a register nobody reads; 2: an s_mov likewise.  The time a pivot
+//  gains per added instruction is what an issue slot of that kind costs a wave of this loop: profiles/small_loop_slots_probe.txt.
+//  Never in the shipped library.)
+#if defined(MCF_SLOT_PROBE) && MCF_SLOT_PROBE > 0
+#ifndef MCF_SLOT_PROBE_KIND
+#define MCF_SLOT_PROBE_KIND 0
+#endif
+__device__ __forceinline__ void mcf_slot_probe() {
+#pragma unroll
+    for (int i = 0; i < MCF_SLOT_PROBE; ++i) {
+        if (MCF_SLOT_PROBE_KIND == 0) {
+            asm volatile("s_nop 0");
+        } else if (MCF_SLOT_PROBE_KIND == 1) {
+            int32_t dead;
+            asm volatile("v_mov_b32 %0, 0" : "=v"(dead));
+            asm volatile("" ::"v"(dead));
+        } else {
+            int32_t dead;
+            asm volatile("s_mov_b32 %0, 0" : "=s"(dead));
+            asm volatile("" ::"s"(dead));
+        }
+    }
+}
+#define MCF_SLOT_PROBE_HERE() mcf_slot_probe()
+#else
+#define MCF_SLOT_PROBE_HERE() do {} while (0)
+#endif
 // (diagnostic build: EVERY wave's own clock, from the top of the iteration to where it stands -- slot 0: at the search barrier,
 //  1: behind the ratio tests, 2: behind decide, 3: behind apply (its arrival at the end barrier), 4: behind finish (last wave) --
 //  summed over the pivots that swap or flip; slot 5 (wave 0): one dependent broadcast LDS read, MCF_WAVE_PROBE.  A switch of
@@ -1953,6 +1982,14 @@ constexpr bool small_desc_once(int threads, bool front) { return threads == 256;
 // The straight-line decide (mcf_pivot_decide_flat: selects where mcf_pivot_decide returns early) where the control block lives in
 // vector registers and the kernel never carries Devex weights: the 256-lane front kernel.
 constexpr bool small_decide_flat(int threads, bool front) { return threads == 256 && front; }
+// The loop budgeted in issue slots ("The slot budget"): at 256 lanes a wave is alone on its SIMD and pays for
+// every instruction it issues, waits for VCC included.  Each part has a switch of its own; the 1 024-lane kernels keep the forms
+// they were measured with.
+//   the narrow register sweep without compares for the violation, on kPriceChains accumulators (front kernels price narrow)
+constexpr bool small_price_flat(int threads, bool front) { return threads == 256 && front; }
+constexpr int small_price_chains(int threads, bool front) { return small_price_flat(threads, front) ? 2 : 1; }
+//   the arg-max's pick reads the waves' 16-byte slots whole, in one round trip, and unpacks with selects
+constexpr bool small_pick_one_trip(int threads) { return threads == 256; }
 // What a lane remembers of its best arc besides the key: end points and slot in one word -- tail | head << 11 | slot << 22,
 // slot q = the lane's q-th arc, engine index r_lo + q * r_step (the lanes' stride: THREADS under the even deal) -- the invariant
 // part precomputed per register arc; bit 31 is the state's sign (set: -1, the arc sits at capacity).  11 bits per node and 9 per slot cover every instance of the LDS plan
@@ -2175,7 +2212,27 @@ __device__ __forceinline__ void small_handover_pick(const SmallWaveSlot* slot, i
     constexpr bool kScalar = small_scalar_control(THREADS);
     const int32_t lane = (int32_t)(threadIdx.x & 63);
     SmallWaveSlot b;
-    if constexpr (kWaves <= 4) {   // one round trip, kWaves reads
+    if constexpr (kWaves <= 4 && small_pick_one_trip(THREADS)) {
+        // every slot whole, 16 bytes a read, and every word wanted here: left alone, the compiler reads the keys, branches on
+        // "any" and only then reads the winner's other half -- a second dependent round trip behind the barrier
+        // The words as mcf_narrow_pick wants them are the slot's own layout; the reads are of another type than the publish
+        // store's, and it is the caller's barrier between the two, not the types, that orders them behind it.
+        static_assert(sizeof(SmallWaveSlot) == 16 && offsetof(SmallWaveSlot, key) == 0 && offsetof(SmallWaveSlot, e) == 8 &&
+                      offsetof(SmallWaveSlot, info) == 12, "key low, key high, engine index, info word: four words of a 16-byte read");
+        typedef uint32_t pick_u32x4 __attribute__((ext_vector_type(4)));
+        pick_u32x4 raw[kWaves];
+#pragma unroll
+        for (int q = 0; q < kWaves; ++q) raw[q] = reinterpret_cast<const pick_u32x4*>(slot)[q];
+        static_assert(kWaves == 4, "the one statement below names every slot: one wait for all four reads");
+        asm volatile("" : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]), "+v"(raw[3]));
+        uint32_t w[kWaves][4];
+#pragma unroll
+        for (int q = 0; q < kWaves; ++q) { w[q][0] = raw[q].x; w[q][1] = raw[q].y; w[q][2] = raw[q].z; w[q][3] = raw[q].w; }
+        mcf_narrow_pick<kWaves>(w, key, arc, wx);
+        key = uni64<kScalar>(key); arc = uni64<kScalar>(arc);
+        wx.rc = uni64<kScalar>(wx.rc); wx.tail = uni32<kScalar>(wx.tail); wx.head = uni32<kScalar>(wx.head); wx.state = uni32<kScalar>(wx.state);
+        return;
+    } else if constexpr (kWaves <= 4) {   // one round trip, kWaves reads
         SmallWaveSlot sl[kWaves];
 #pragma unroll
         for (int q = 0; q < kWaves; ++q) sl[q] = slot[q];
@@ -2353,12 +2410,23 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         r_info[k] = small_info(r_tail[k], r_head[k], k);
         r_n += on ? 1 : 0;
     }
+    // (small_price_flat) a slot's packed key as a register pair of its own: ~id below, this sweep's violation above it -- the
+    // 64-bit compare reads the pair as it stands, where a key built per sweep costs an OR and a copy per slot
+    // (only there: every other kernel declares one dead element and compiles to what it was)
+    typedef uint32_t small_u32x2 __attribute__((ext_vector_type(2)));
+    small_u32x2 r_key[small_price_flat(THREADS, FRONT) ? kReg : 1];
+    if constexpr (small_price_flat(THREADS, FRONT)) {
+#pragma unroll
+        for (int k = 0; k < kReg; ++k) { r_key[k].x = (uint32_t)~r_orig[k]; r_key[k].y = 0; }
+    }
     // The front (compile-time): 32-bit keys on the plain register sweep, and with them the arg-max that hands the winner's
     // record to begin.  64-bit keys price from registers or LDS, reduce with block_argmax_all and let begin look the arc up.
     const bool reg_plain = sweep == kSweepPlain;
     constexpr bool nar = FRONT;
     constexpr bool kDescOnce = small_desc_once(THREADS, FRONT);
     constexpr bool kDecideFlat = small_decide_flat(THREADS, FRONT);
+    constexpr bool kPriceFlat = small_price_flat(THREADS, FRONT);
+    constexpr int kPriceChains = small_price_chains(THREADS, FRONT);
     constexpr bool hand = FRONT;
     const int32_t* const pi32 = reinterpret_cast<const int32_t*>(v.pi);   // low words of the potentials
     // ---- control in registers (see above): a private copy of the control block in every wave
@@ -2411,8 +2479,45 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
                         if (p > nbest) { nbest = p; info = r_info[k] | ((uint32_t)s & 0x80000000u); }
                     }
                 };
-                if (r_few) slots(SmallSlots<kRegFew>{});
-                else slots(SmallSlots<kReg>{});
+                // The same sweep counted in issue slots (kPriceFlat): the violation without a compare (mcf_narrow_violation_signed),
+                // keys compared as signed 64-bit numbers so that nothing is clamped, and kPriceChains accumulators over alternate
+                // slots merged by the same compare -- one chain's compare has the other's work behind it instead of a wait for VCC.
+                // A slot past the lane's last arc holds cost 0, tail = head = 0 and id 0: reduced cost 0 whatever state it reads,
+                // its key is the start value and replaces nothing -- no mask.
+                auto slots_flat = [&](auto ns) {
+                    constexpr int NS = decltype(ns)::value;
+                    int32_t st[NS], pt[NS], ph[NS];
+#pragma unroll
+                    for (int k = 0; k < NS; ++k) {
+                        st[k] = v.state[k < r_n ? r_lo + k * r_step : 0];
+                        pt[k] = pi32[2 * r_tail[k]];
+                        ph[k] = pi32[2 * r_head[k]];
+                    }
+                    int64_t nb[kPriceChains];
+                    uint32_t inf[kPriceChains];
+                    // (a chain starts from its first slot's key, eligible or not, and the start value is compared once, behind the
+                    //  merge: every ineligible key is <= mcf_narrow_start() < every eligible one)
+#pragma unroll
+                    for (int k = 0; k < NS; ++k) {
+                        const int32_t rc = (int32_t)((uint32_t)r_cost[k] + (uint32_t)pt[k] - (uint32_t)ph[k]);
+                        // mcf_narrow_key(violation, id) assembled in place: the low word never changes, the high one is written here
+                        r_key[k].y = (uint32_t)mcf_narrow_violation_signed(st[k], rc);
+                        const int64_t p = __builtin_bit_cast(int64_t, r_key[k]);
+                        const int a = k % kPriceChains;
+                        if (k < kPriceChains || p > nb[a]) { nb[a] = p; inf[a] = r_info[k] | ((uint32_t)st[k] & 0x80000000u); }
+                    }
+#pragma unroll
+                    for (int a = 1; a < kPriceChains; ++a) if (nb[a] > nb[0]) { nb[0] = nb[a]; inf[0] = inf[a]; }
+                    if (!(nb[0] > mcf_narrow_start())) { nb[0] = mcf_narrow_start(); inf[0] = 0; }
+                    nbest = (uint64_t)nb[0]; info = inf[0];   // (high word >= 0: the start value's or an eligible arc's)
+                };
+                if constexpr (kPriceFlat) {
+                    if (r_few) slots_flat(SmallSlots<kRegFew>{});
+                    else slots_flat(SmallSlots<kReg>{});
+                } else {
+                    if (r_few) slots(SmallSlots<kRegFew>{});
+                    else slots(SmallSlots<kReg>{});
+                }
                 int32_t q = kReg;   // (no trip when r_few)
                 for (int32_t i = r_lo + kReg * r_step; i < r_hi; i += r_step, ++q) small_price_lds_narrow(v, i, q, nbest, info);
                 // the present form, for the candidate list's entries and for the record
@@ -2489,6 +2594,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
             block_argmax_all<THREADS>(key, arc);
         }
         STAMP(2);
+        MCF_SLOT_PROBE_HERE();
         // ---- pivot: every wave decides, everything it touches is in LDS or in its registers
         if (cx.pivots < cx.max_pivots)
             cx.arcs_priced += minor ? (int64_t)MCF_NUM_BUCKETS : (devex ? (int64_t)uni32<kScalar>(s_gsum[bg1] - s_gsum[bg0]) : priced_all);
