@@ -212,6 +212,43 @@ MCF_HD int32_t mcf_even_reg_slots(int32_t arcs, int32_t threads, int32_t few, in
     return mcf_even_slots(arcs, threads) <= few ? few : reg;
 }
 
+// ---- the fused LDS loop's slot budget, second part (mcf_engine.hip).  The device code and
+// csrc/mcf_small_budget_host.cpp (CPU tests) both call these.
+#define MCF_SMALL_MAX_LDS (156 * 1024)     // dynamic LDS of the fused loop (160 KB per CU, under 4 KB static on top)
+#define MCF_SMALL_PLAN_BYTES (150 * 1024)  // what the arrays of an instance may need: 112 bytes a tree node among them
+#define MCF_SMALL_CYCLE_MAX_NODES 1024     // node-parallel cycle search up to this many tree nodes (strided over the lanes)
+// The arrays that come in pairs -- a side's or a buffer's -- lie side by side, every pair of a kind the same distance apart:
+// element i of the second array is element i + dist of the first.  4-byte arrays (order, pos, path, ppos) are rounded up to 16
+// bytes each, node records (rec) are 16 bytes already, and the search's residuals (two arrays of n_nodes 8-byte entries in the
+// scratch) are n_nodes apart like the records.
+MCF_HD int32_t mcf_pair_dist4(int32_t n_nodes) { return (n_nodes + 3) & ~3; }
+MCF_HD int32_t mcf_pair_dist16(int32_t n_nodes) { return n_nodes; }
+// The tree nodes of an instance of the plan stay below this: two of its per-side counts fit one word's halves (mcf_counts_pack).
+#define MCF_SMALL_MAX_NODES (MCF_SMALL_PLAN_BYTES / 112 + 1)
+static_assert(MCF_SMALL_MAX_NODES < (1 << 16), "a count of tree nodes fits 16 bits");
+// Which of the two: 0 the first side / buffer, 1 the second -- a NUMBER to multiply with, where a select between two base
+// addresses held in scalar registers costs two moves and the select.
+MCF_HD int32_t mcf_pair_bit(bool second) {
+    int32_t bit = second ? 1 : 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(bit));   // (opaque: seen through, the product becomes the select again)
+#endif
+    return bit;
+}
+// i + bit * dist; bit is 0 or 1 and |dist| < 2^23: one 24-bit multiply-add on the device
+MCF_HD int32_t mcf_pair_index(int32_t i, int32_t bit, int32_t dist) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return i + __mul24(bit, dist);
+#else
+    return i + bit * dist;
+#endif
+}
+// The per-wave counts of the search's two sides in one word, first side below: the waves' words add up without a carry between
+// the halves while the tree has fewer than 2^16 nodes (MCF_SMALL_MAX_NODES).
+MCF_HD uint32_t mcf_counts_pack(int32_t n1, int32_t n2) { return (uint32_t)n1 | ((uint32_t)n2 << 16); }
+MCF_HD int32_t mcf_counts_first(uint32_t sum) { return (int32_t)(sum & 0xffffu); }
+MCF_HD int32_t mcf_counts_second(uint32_t sum) { return (int32_t)(sum >> 16); }
+
 // Diagnostic build (-DMCF_STAMPS): cycle stamps of the one-workgroup pivot kernel, accumulated per phase.
 #if defined(MCF_STAMPS) && defined(__HIPCC__)
 __shared__ unsigned long long mcf_stamp_acc[24];
@@ -468,6 +505,44 @@ struct McfView {
     struct McfDirty* dirty;
     const struct McfDirty* dirty_hdr;   // a copy of *dirty's header (nlb, lo, hi) that is cheaper to read (LDS in the pivot kernel), or nullptr
 };
+
+// LDS plan of the fused small-instance path (every offset a multiple of 16) for an instance of m_pad padded arcs; false when it
+// does not fit the LDS capacity of k_solve_small.  Host side only; here so that the CPU tests see the very offsets the kernel gets.
+struct McfSmallLayout {
+    uint32_t tail, head, cost, orig, state, weight, arcw, pi, node, order0, order1, pos0, pos1, path1, path2, ppos1, ppos2, rec1, rec2, seg, scratch, ctx, total;
+};
+// (mcf_small_layout: the offsets alone, for any sizes whose sum stays below 2^32; mcf_small_plan: whether the kernel can run them)
+inline McfSmallLayout mcf_small_layout(int64_t m_pad, uint64_t arcw_count, int32_t n_nodes, bool devex) {
+    McfSmallLayout L;
+    uint32_t off = 0;
+    auto take = [&](uint64_t bytes) { const uint32_t o = off; off += (uint32_t)((bytes + 15) / 16 * 16); return o; };
+    const uint64_t mp = (uint64_t)m_pad, Nn = (uint64_t)n_nodes;
+    L.tail = take(mp * 4); L.head = take(mp * 4); L.cost = take(mp * 4); L.orig = take(mp * 4);
+    L.state = take(mp); L.weight = take(devex ? mp * 4 : 0);
+    L.arcw = take(arcw_count * 16); L.pi = take(Nn * 8); L.node = take(Nn * 16);
+    L.order0 = take(Nn * 4); L.order1 = take(Nn * 4); L.pos0 = take(Nn * 4); L.pos1 = take(Nn * 4);
+    L.path1 = take(Nn * 4); L.path2 = take(Nn * 4); L.ppos1 = take(Nn * 4); L.ppos2 = take(Nn * 4);
+    L.rec1 = take(Nn * 16); L.rec2 = take(Nn * 16);
+    L.seg = take((2 * Nn + 2) * sizeof(McfSeg));
+    // scratch of the node-parallel cycle search (two residuals and one by-depth entry per tree node); a larger tree is climbed
+    L.scratch = take(n_nodes <= MCF_SMALL_CYCLE_MAX_NODES ? Nn * 20 : 0);
+    L.ctx = take(sizeof(McfCtx));
+    L.total = off;
+    return L;
+}
+inline bool mcf_small_plan(int64_t m_pad, uint64_t arcw_count, int32_t n_nodes, bool devex, McfSmallLayout* out) {
+    const uint64_t need = (uint64_t)m_pad * 21 + arcw_count * 16 + (uint64_t)n_nodes * 112 + 4096;
+    if (need >= MCF_SMALL_PLAN_BYTES) return false;   // (before the offsets are formed: they are 32-bit)
+    const McfSmallLayout L = mcf_small_layout(m_pad, arcw_count, n_nodes, devex);
+    if (L.total > MCF_SMALL_MAX_LDS) return false;
+    // what the pair arithmetic and the packed counts of the 256-lane front kernel rest on
+    const uint32_t d4 = 4u * (uint32_t)mcf_pair_dist4(n_nodes), d16 = 16u * (uint32_t)mcf_pair_dist16(n_nodes);
+    if (L.order1 - L.order0 != d4 || L.pos1 - L.pos0 != d4 || L.path2 - L.path1 != d4 || L.ppos2 - L.ppos1 != d4 || L.rec2 - L.rec1 != d16 ||
+        (L.rec1 & 15u) || (L.rec2 & 15u) || n_nodes >= MCF_SMALL_MAX_NODES)
+        return false;
+    *out = L;
+    return true;
+}
 
 #define MCF_MAX_PRICE_BLOCKS 2048
 struct McfDirty {
@@ -1567,7 +1642,10 @@ MCF_HD void mcf_pivot_decide(const McfView& v, const McfPaths& pp, const McfCycl
 // and the point where they meet again copies all of it.  The leaving node's record and position are fetched unconditionally,
 // from index 0 when nobody leaves (the read stays inside the recorded-path arrays and its value is then dropped), so the
 // load's address hangs on two selects only and nothing is branched on before it is issued.
-MCF_HD void mcf_pivot_decide_flat(const McfView& v, const McfPaths& pp, const McfCycle& cy) {
+// PAIRS: the second side's records and positions lie d16 / d4 elements behind the first side's (mcf_small_plan), and the leaving
+// node's are fetched at k + bit * distance of the first side's arrays: no select between two base addresses.
+template <bool PAIRS>
+MCF_HD void mcf_pivot_decide_flat_t(const McfView& v, const McfPaths& pp, const McfCycle& cy, int32_t d4, int32_t d16) {
     McfCtx* c = v.ctx;
     const int32_t e = c->pv_e, s = c->pv_s, first = c->pv_first, second = c->pv_second;
     const int64_t d1 = cy.d1, d2 = cy.d2, rc = c->pv_rc;
@@ -1581,8 +1659,9 @@ MCF_HD void mcf_pivot_decide_flat(const McfView& v, const McfPaths& pp, const Mc
     const int64_t delta = take2 ? d2 : (take0 ? de : d1);
     const int32_t kq = side1 ? cy.k1 : cy.k2;
     const int32_t k = (take0 || kq < 0) ? 0 : kq;
-    const McfNode rq = (side1 ? pp.rec1 : pp.rec2)[k];
-    const int32_t a0 = (side1 ? pp.ppos1 : pp.ppos2)[k];
+    const int32_t bit = PAIRS ? mcf_pair_bit(!side1) : 0;
+    const McfNode rq = PAIRS ? pp.rec1[mcf_pair_index(k, bit, d16)] : (side1 ? pp.rec1 : pp.rec2)[k];
+    const int32_t a0 = PAIRS ? pp.ppos1[mcf_pair_index(k, bit, d4)] : (side1 ? pp.ppos1 : pp.ppos2)[k];
     const bool live = delta < MCF_INF;          // not unbounded (simplex.py:1231-1246)
     const bool flip = live && take0;            // the entering arc is also the leaving arc (simplex.py:1320-1334)
     const bool swap = live && !take0;
@@ -1636,6 +1715,7 @@ MCF_HD void mcf_pivot_decide_flat(const McfView& v, const McfPaths& pp, const Mc
     c->pv_adj[0] = move ? c->pv_adj[2] : c->pv_adj[0];
     c->pv_adj[1] = move ? c->pv_adj[3] : c->pv_adj[1];
 }
+MCF_HD void mcf_pivot_decide_flat(const McfView& v, const McfPaths& pp, const McfCycle& cy) { mcf_pivot_decide_flat_t<false>(v, pp, cy, 0, 0); }
 
 // ---------------------------------------------------------------------------
 // Dual pivots (mcf_update_rhs_dual; the rule is written out in include/mcf.h).  A supply / capacity edit leaves the basis
@@ -2130,6 +2210,111 @@ MCF_HD void mcf_pivot_finish(const McfView& v, const McfPaths& pp, int32_t lane,
     mcf_pivot_finish_t<false>(v, pp, lane, nlanes);
 }
 
+// mcf_pivot_finish_t<true> once more for the fused LDS loop's front kernels: the dense layout without Devex weights,
+// position-space sizes, coarse index or blocked list, on recorded paths whose second side lies d4 (path) / d16 (rec) elements
+// behind the first (mcf_small_plan).  The side that leaves is a NUMBER, pv_result - 1, and every array of "the stem's side" or
+// "the other side" is the first side's at an offset of that number times the distance: where the general pass selects between
+// two base addresses per array -- two moves and a select each once the addresses sit in scalar registers -- this one
+// multiplies.  Same stores, same values (csrc/mcf_small_budget_host.cpp runs the two side by side over whole solves).
+template <bool ONE_TRIP = true>
+MCF_HD void mcf_pivot_finish_pairs(const McfView& v, const McfPaths& pp, int32_t d4, int32_t d16, int32_t lane, int32_t nlanes) {
+    const McfCtx* c = v.ctx;
+    const int32_t stage = c->stage;
+    if (stage == 0) return;
+    const int32_t e = c->pv_e, s = c->pv_s, n1 = c->pv_n1, n2 = c->pv_n2, nf = n1 + n2;
+    const int64_t delta = c->pv_delta;
+    const int32_t skip = d16 - n1;   // rec2[i - n1] is rec1[i + d16 - n1]
+    // one element of the flow update along the cycle: distinct arcs, one per lane
+    auto flow_arc = [&](int32_t i, bool* gains) {
+        const bool side1 = i < n1;
+        const int32_t p = pp.rec1[side1 ? i : i + skip].pred;
+        *gains = side1 != ((p & 1) != 0);   // first side is walked against the flow, second side with it
+        return p >> 1;
+    };
+    if (stage == 1) {   // a bound flip
+        if (delta > 0) {
+            for (int32_t i = lane; i < nf; i += nlanes) {
+                bool gains;
+                const int32_t a = flow_arc(i, &gains);
+                v.arcw[a].flow += gains ? delta : -delta;
+            }
+            if (lane == 0) v.arcw[e].flow = c->pv_flow + (int64_t)s * delta;
+        }
+        if (lane == 0) {
+            v.state[e] = (int8_t)(-s);
+            if (v.vkey) v.vkey[e] = 0;
+            mcf_mark_dirty(v, e);
+        }
+        return;
+    }
+    const int32_t k = c->pv_k, v_in = c->pv_vin;
+    const int32_t sbit = c->pv_result - 1, obit = 1 - sbit;   // (a swap: pv_result is 1 or 2)
+    const int32_t* stem = pp.path1 + mcf_pair_index(0, sbit, d4);
+    const McfNode* srec = pp.rec1 + mcf_pair_index(0, sbit, d16);
+    const int32_t* other = pp.path1 + mcf_pair_index(0, obit, d4);
+    const McfNode* orec = pp.rec1 + mcf_pair_index(0, obit, d16);
+    const int32_t nstem_side = sbit ? n2 : n1, nother = sbit ? n1 : n2;
+    const int32_t S = c->t2_size;
+    // The four passes -- flows; sizes of the old ancestors of q (they lose S); sizes of v_in and its ancestors (they gain S); the
+    // re-hung stem -- store to distinct words and load from the recorded paths only (and the flows' own words), so their order is
+    // free.  The FIRST trip of all four: every load of the paths at once, one round trip; the flows' read behind it, a second; then
+    // the stores.  A lane without an element in a pass reads one that exists (index 0, or k) and stores nothing.  Run pass by
+    // pass, each one's loads waited for the one before it: four round trips and more where two do.  Further trips -- a cycle
+    // longer than the lanes -- run as they did.
+    auto rehang = [&](int32_t i, int32_t nd, int32_t below, const McfNode& rb) {
+        McfNode* const q = &v.node[nd];
+        if (i == 0) { q->parent = v_in; q->pred = (e << 1) | c->pv_tail_in_t2; q->size = S; }
+        else { q->parent = below; q->pred = rb.pred ^ 1; q->size = S - rb.size; }
+    };
+    if (!ONE_TRIP) {   // (pass by pass, as mcf_pivot_finish_t<true> runs them)
+        if (delta > 0) {
+            for (int32_t i = lane; i < nf; i += nlanes) {
+                bool g;
+                const int32_t a = flow_arc(i, &g);
+                v.arcw[a].flow += g ? delta : -delta;
+            }
+            if (lane == 0) v.arcw[e].flow = c->pv_flow + (int64_t)s * delta;
+        }
+        if (lane == 0) {
+            v.state[e] = 0;
+            mcf_mark_dirty(v, e);
+            if (c->pv_leave < v.m) { v.state[c->pv_leave] = (int8_t)c->pv_leave_state; mcf_mark_dirty(v, c->pv_leave); }
+        }
+        for (int32_t i = k + 1 + lane; i < nstem_side; i += nlanes) v.node[stem[i]].size = srec[i].size - S;
+        for (int32_t i = lane; i < nother; i += nlanes) v.node[other[i]].size = orec[i].size + S;
+        for (int32_t i = lane; i <= k; i += nlanes) rehang(i, stem[i], stem[i > 0 ? i - 1 : 0], srec[i > 0 ? i - 1 : 0]);
+        return;
+    }
+    const bool on_f = delta > 0 && lane < nf, on_d = k + 1 + lane < nstem_side, on_u = lane < nother, on_s = lane <= k;
+    bool gains;
+    const int32_t a_f = flow_arc(lane < nf ? lane : 0, &gains);
+    const int32_t j_d = on_d ? k + 1 + lane : k, j_u = on_u ? lane : 0, j_s = on_s ? lane : 0, j_p = j_s > 0 ? j_s - 1 : 0;
+    const int32_t nd_d = stem[j_d], z_d = srec[j_d].size;
+    const int32_t nd_u = other[j_u], z_u = orec[j_u].size;
+    const int32_t nd_s = stem[j_s], nd_p = stem[j_p];
+    const McfNode rp = srec[j_p];
+    int64_t fl = 0;
+    if (on_f) fl = v.arcw[a_f].flow;
+    if (on_f) v.arcw[a_f].flow = fl + (gains ? delta : -delta);
+    if (lane == 0) {
+        if (delta > 0) v.arcw[e].flow = c->pv_flow + (int64_t)s * delta;
+        v.state[e] = 0;
+        mcf_mark_dirty(v, e);
+        if (c->pv_leave < v.m) { v.state[c->pv_leave] = (int8_t)c->pv_leave_state; mcf_mark_dirty(v, c->pv_leave); }
+    }
+    if (on_d) v.node[nd_d].size = z_d - S;
+    if (on_u) v.node[nd_u].size = z_u + S;
+    if (on_s) rehang(j_s, nd_s, nd_p, rp);
+    if (delta > 0)
+        for (int32_t i = lane + nlanes; i < nf; i += nlanes) {
+            const int32_t a = flow_arc(i, &gains);
+            v.arcw[a].flow += gains ? delta : -delta;
+        }
+    for (int32_t i = k + 1 + lane + nlanes; i < nstem_side; i += nlanes) v.node[stem[i]].size = srec[i].size - S;
+    for (int32_t i = lane + nlanes; i < nother; i += nlanes) v.node[other[i]].size = orec[i].size + S;
+    for (int32_t i = lane + nlanes; i <= k; i += nlanes) rehang(i, stem[i], stem[i - 1], srec[i - 1]);
+}
+
 // Convenience for single-threaded callers (CPU emulation): the whole pivot.
 MCF_HD void mcf_pivot_seq(const McfView& v, int64_t best_key, int64_t best_arc, int32_t rule) {
     mcf_pivot_walk(v, best_key, best_arc, rule);
@@ -2232,6 +2417,11 @@ MCF_HD int32_t mcf_apply_one(const McfView& v, const McfCtx& c, int32_t j) {
 
 // A position outside [lo, hi) catches up on what the previous apply changed in the other copy: node `nd` = order[cur][j] stays at j.
 // The one statement of that store: mcf_apply_one_paths below, and the fused LDS loop's apply pass, which reads nd early (small_apply).
+// (dst / pnext: order[cur ^ 1] and pos[cur ^ 1], named by the caller)
+MCF_HD void mcf_apply_catch_up_store_at(int32_t* dst, int32_t* pnext, int32_t j, int32_t nd) {
+    dst[j] = nd;
+    pnext[nd] = j;
+}
 MCF_HD void mcf_apply_catch_up_store(const McfView& v, const McfCtx& c, int32_t j, int32_t nd) {
     (c.cur ? v.order[0] : v.order[1])[j] = nd;
     (c.cur ? v.posbuf[0] : v.posbuf[1])[nd] = j;
@@ -2241,6 +2431,28 @@ MCF_HD void mcf_apply_catch_up_store(const McfView& v, const McfCtx& c, int32_t 
 // srec / spos are the leaving arc's side of the paths (pv_result == 1: rec1 / ppos1, else rec2 / ppos2).  Reads order[cur] and
 // the path arrays, reads and writes pi[] and node[].depth, writes order[cur ^ 1] and pos[cur ^ 1] -- no word that
 // mcf_pivot_finish_t<true> writes.
+// (src / dst / pnext: order[cur], order[cur ^ 1] and pos[cur ^ 1], named by the caller -- by select below, by pair arithmetic in
+//  the fused LDS loop's front kernels)
+MCF_HD void mcf_apply_one_paths_at(const McfView& v, const McfCtx& c, const McfNode* srec, const int32_t* spos, const int32_t* src,
+                                   int32_t* dst, int32_t* pnext, int32_t j) {
+    if (j >= c.lo && j < c.hi) {
+        bool in_t2;
+        int32_t dd;
+        const int32_t i = mcf_apply_source_paths(c, srec, spos, j, &in_t2, &dd);
+        const int32_t nd = src[i];
+        dst[j] = nd;
+        pnext[nd] = j;
+        if (in_t2) {
+            // both read-modify-writes hang on nd alone: read together, then stored together (the depth word only when it moves)
+            const int64_t pot = v.pi[nd];
+            const int32_t dep = v.node[nd].depth;
+            v.pi[nd] = pot + c.sigma;
+            if (dd) v.node[nd].depth = dep + dd;
+        }
+    } else {
+        mcf_apply_catch_up_store_at(dst, pnext, j, src[j]);
+    }
+}
 MCF_HD void mcf_apply_one_paths(const McfView& v, const McfCtx& c, const McfNode* srec, const int32_t* spos, int32_t j) {
     const int32_t* src = c.cur ? v.order[1] : v.order[0];
     int32_t* dst = c.cur ? v.order[0] : v.order[1];

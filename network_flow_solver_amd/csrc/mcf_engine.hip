@@ -1568,12 +1568,10 @@ __device__ __forceinline__ bool pivot_climb_2lanes(const McfView& v, McfCycle* o
 // same mcf_apply_one) and copies the state back.  Same arc sets, same tie rule, same core functions
 // as the three-kernel path, so the pivot sequence is identical -- at every width: the workgroup is
 // THREADS lanes wide: 256, one wave per SIMD, or 1 024 when forced (small_threads_for; MCF_SMALL_THREADS).
-struct SmallLayout {
-    uint32_t tail, head, cost, orig, state, weight, arcw, pi, node, order0, order1, pos0, pos1, path1, path2, ppos1, ppos2, rec1, rec2, seg, scratch, ctx, total;
-};
+typedef McfSmallLayout SmallLayout;   // (mcf_core.h, beside mcf_small_plan: the CPU tests plan with the same function)
 
-constexpr int kSmallMaxLds = 156 * 1024;   // dynamic LDS of the fused small-instance loop (160 KB per CU, under 4 KB static on top)
-constexpr int kSmallCycleMaxNodes = 1024;  // node-parallel cycle search up to this many tree nodes (strided over the lanes)
+constexpr int kSmallMaxLds = MCF_SMALL_MAX_LDS;   // dynamic LDS of the fused small-instance loop (160 KB per CU, under 4 KB static on top)
+constexpr int kSmallCycleMaxNodes = MCF_SMALL_CYCLE_MAX_NODES;  // node-parallel cycle search up to this many tree nodes (strided over the lanes)
 
 // Arcs of a head bucket that one lane keeps in registers (tail, head, cost, orig: 4 VGPRs each).  THREADS / 8 lanes share a
 // bucket, so 320 (256 lanes) / 384 (1 024 lanes) arcs per bucket are register-resident -- netgen_8_08a's buckets hold
@@ -1778,9 +1776,26 @@ typedef int small_i32x4 __attribute__((ext_vector_type(4)));
 // a VGPR lane across the branch into the straight-line reductions.  At 256 lanes (the 1 024-lane kernels were not measured with it).
 constexpr bool small_ratio_one_trip(int threads) { return threads == 256; }
 typedef int small_i32x2 __attribute__((ext_vector_type(2)));
+// The slot budget, second part: the stages behind the pick counted in issue slots, in the 256-lane front
+// kernels.  (Diagnostic builds switch one part off alone with -DMCF_BUDGET_OFF=<bits>: 1 pairs, 2 ballots, 4 counts, 8 the
+// finish pass's loads in one trip.)
+#ifndef MCF_BUDGET_OFF
+#define MCF_BUDGET_OFF 0
+#endif
+//   side- and buffer-selected LDS addresses by arithmetic: small_plan lays the arrays of a pair a constant distance apart
+//   (mcf_pair_dist4 / mcf_pair_dist16), so the second one's element is the first one's at index + bit * distance -- one 24-bit
+//   multiply-add where a select between two base addresses in scalar registers is two moves and the select
+constexpr bool small_pair_arith(int threads, bool front) { return threads == 256 && front && !(MCF_BUDGET_OFF & 1); }
+//   ballots of the search and of the ratio tests straight from their compares, joined as lane masks in scalar registers: a
+//   ballot of a bool put together with && goes through a VGPR (v_cndmask 0, 1 and a v_cmp_ne of it)
+constexpr bool small_ballot_direct(int threads, bool front) { return threads == 256 && front && !(MCF_BUDGET_OFF & 2); }
+//   a wave's two counts in one word (mcf_counts_pack): four lane reads, three adds and the unpacking where eight and eight stood
+constexpr bool small_counts_packed(int threads, bool front) { return threads == 256 && front && !(MCF_BUDGET_OFF & 4); }
+//   the pair form of the finish pass issues the first trip's loads of all four of its passes together (mcf_pivot_finish_pairs<true>)
+constexpr bool small_finish_one_trip(int threads, bool front) { return small_pair_arith(threads, front) && !(MCF_BUDGET_OFF & 8); }
 
 // `cy` as mcf_pivot_begin_t<true> left it (in registers, uniform); on return the finished cycle, uniform in every wave.
-template <int THREADS>
+template <int THREADS, bool FRONT>
 __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycleAcc& A, int64_t* scratch, McfCycle& cy) {
     constexpr bool kScalar = small_scalar_control(THREADS);
     constexpr bool kSearchJoin = small_search_join(THREADS);
@@ -1788,8 +1803,12 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
     constexpr bool kRatioTogether = small_ratio_together(THREADS);
     constexpr bool kRecordOnce = small_record_once(THREADS);
     constexpr bool kRatioOneTrip = kRatioTogether && small_ratio_one_trip(THREADS);
+    constexpr bool kPairs = small_pair_arith(THREADS, FRONT) && kSearchOneBranch;
+    constexpr bool kBallot = small_ballot_direct(THREADS, FRONT) && kSearchOneBranch && !kSearchJoin && kRatioOneTrip;
+    constexpr bool kCounts = small_counts_packed(THREADS, FRONT) && kRatioOneTrip;
     const McfCtx* c = v.ctx;   // (the caller's registers)
-    const int32_t* pcur = c->cur ? v.posbuf[1] : v.posbuf[0];
+    const int32_t d4 = mcf_pair_dist4(v.n_nodes), d16 = mcf_pair_dist16(v.n_nodes);   // (kPairs; constants of the launch)
+    const int32_t* pcur = kPairs ? v.posbuf[0] + mcf_pair_index(0, c->cur, d4) : (c->cur ? v.posbuf[1] : v.posbuf[0]);
     const int32_t du0 = cy.r0u.depth, dw0 = cy.r0w.depth;
     const int32_t pu = cy.p0u, pw = cy.p0w;
     const int32_t wave = (int32_t)threadIdx.x >> 6;
@@ -1801,10 +1820,45 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
     int32_t* const by_depth = reinterpret_cast<int32_t*>(res2 + N);
     int32_t n1w = 0, n2w = 0;   // this wave's one-sided ancestors, over its passes
     const int32_t nx = kSearchJoin ? N : N - 1;   // (the root files nothing: see kSearchJoin)
+    // (kPairs) a one-sided ancestor files itself at index depth[end point] - depth[x] of its side's arrays: with the side as a
+    // number that is (du0 - depth[x]) + bit * (dw0 - du0) in the first side's terms, and the second side's arrays begin d4 / d16
+    // elements behind the first's -- one multiply-add per kind of array names the element in either
+    const int32_t side4 = dw0 - du0 + d4, side16 = dw0 - du0 + d16;
+    auto file_pairs = [&](bool au, const McfNode& rec, int32_t px, int32_t x) {
+        const McfArcW a = v.arcw[rec.pred >> 1];
+        const int32_t bit = mcf_pair_bit(!au), i0 = du0 - rec.depth;
+        const int32_t i4 = mcf_pair_index(i0, bit, side4), i16 = mcf_pair_index(i0, bit, side16);
+        v.path1[i4] = x; v.rec1[i16] = rec; v.ppos1[i4] = px;
+        const bool loses = ((rec.pred & 1) != 0) == au;
+        res1[i16] = loses ? a.flow : (a.cap >= MCF_INF ? MCF_INF : a.cap - a.flow);
+    };
     for (int32_t x0 = 0; x0 < nx; x0 += THREADS) {   // (uniform: every wave makes every pass)
         const int32_t x = x0 + (int32_t)threadIdx.x;
         bool h1 = false, h2 = false;
-        if (x < nx) {
+        uint64_t b1 = 0, b2 = 0;   // (kBallot) this pass's one-sided ancestors as lane masks
+        if constexpr (kBallot) {
+            // every lane reads -- one past the last node reads the last node's words -- so that the two ancestor tests are compares
+            // of this block and the ballots take their lane masks as they stand; "inside" and "one-sided" are mask arithmetic
+            const uint64_t bin = __builtin_amdgcn_ballot_w64(x < nx);
+            const int32_t xi = min(x, nx - 1);
+            const small_i32x4 raw = *reinterpret_cast<const small_i32x4*>(&v.node[xi]);
+            McfNode rec;
+            rec.parent = raw.x; rec.pred = raw.y; rec.size = raw.z; rec.depth = raw.w;
+            const int32_t px = pcur[xi];
+            const bool au = (uint32_t)(pu - px) < (uint32_t)rec.size, aw = (uint32_t)(pw - px) < (uint32_t)rec.size;
+            const uint64_t bu = __builtin_amdgcn_ballot_w64(au) & bin, bw = __builtin_amdgcn_ballot_w64(aw) & bin;
+            b1 = bu & ~bw; b2 = bw & ~bu;
+            if (x < nx && au != aw) {
+                if constexpr (kPairs) file_pairs(au, rec, px, x);
+                else {
+                    const McfArcW a = v.arcw[rec.pred >> 1];
+                    const int32_t idx = (au ? du0 : dw0) - rec.depth;
+                    (au ? v.path1 : v.path2)[idx] = x; (au ? v.rec1 : v.rec2)[idx] = rec; (au ? v.ppos1 : v.ppos2)[idx] = px;
+                    const bool loses = ((rec.pred & 1) != 0) == au;
+                    (au ? res1 : res2)[idx] = loses ? a.flow : (a.cap >= MCF_INF ? MCF_INF : a.cap - a.flow);
+                }
+            }
+        } else if (x < nx) {
             // (kRecordOnce) the record as ONE 16-byte read beside the position: an ancestor lane then holds depth, pred and parent
             // and goes straight to its tree arc, where the fields, read one by one, came in a round trip of their own
             McfNode rec;
@@ -1816,7 +1870,9 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
             const bool au = (uint32_t)(pu - px) < (uint32_t)rec.size, aw = (uint32_t)(pw - px) < (uint32_t)rec.size;
             if (au && aw) { if (kSearchJoin) by_depth[rec.depth] = x; }
             else if (kSearchOneBranch) {
-                if (au || aw) {
+                if constexpr (kPairs) {
+                    if (au || aw) { file_pairs(au, rec, px, x); h1 = au; h2 = aw; }
+                } else if (au || aw) {
                     const McfArcW a = v.arcw[rec.pred >> 1];
                     const int32_t idx = (au ? du0 : dw0) - rec.depth;
                     (au ? v.path1 : v.path2)[idx] = x; (au ? v.rec1 : v.rec2)[idx] = rec; (au ? v.ppos1 : v.ppos2)[idx] = px;
@@ -1840,10 +1896,13 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
                 h2 = true;
             }
         }
-        n1w += (int32_t)__popcll(__ballot(h1));
-        n2w += (int32_t)__popcll(__ballot(h2));
+        n1w += (int32_t)__popcll(kBallot ? b1 : (uint64_t)__ballot(h1));
+        n2w += (int32_t)__popcll(kBallot ? b2 : (uint64_t)__ballot(h2));
     }
-    if ((threadIdx.x & 63) == 0) { A.c[wave][0] = n1w; A.c[wave][1] = n2w; }
+    if ((threadIdx.x & 63) == 0) {
+        if (kCounts) A.c[wave][0] = (int32_t)mcf_counts_pack(n1w, n2w);   // (one word: the second of the wave's pair goes unused)
+        else { A.c[wave][0] = n1w; A.c[wave][1] = n2w; }
+    }
     MCF_WAVE_STAMP(0);
     __syncthreads();   // path / record / residual / by_depth entries and the per-wave counts -> every wave's ratio tests, its
                        // decision and the finish pass
@@ -1855,7 +1914,9 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         const int32_t lane = (int32_t)(threadIdx.x & 63);
         // one read, then scalar lane reads (of the lanes below kWaves only: the others may hold anything)
         int32_t c1, c2;
-        if (kRatioOneTrip) {
+        if (kCounts) {
+            c1 = A.c[lane < kWaves ? lane : kWaves - 1][0]; c2 = 0;
+        } else if (kRatioOneTrip) {
             const small_i32x2 cc = *reinterpret_cast<const small_i32x2*>(&A.c[lane < kWaves ? lane : kWaves - 1][0]);
             c1 = cc.x; c2 = cc.y;
         } else {
@@ -1869,12 +1930,37 @@ __device__ __forceinline__ void small_cycle_parallel(const McfView& v, SmallCycl
         if (kRatioTogether) { q1 = res1[li]; q2 = res2[li]; }
         // (the counts and both residuals wanted here: all three reads are issued before the one wait)
         if (kRatioOneTrip) asm volatile("" ::"v"(c1), "v"(c2), "v"(q1), "v"(q2));
+        if (kCounts) {
+            uint32_t sum = 0;   // (no carry from the first side's half into the second's: mcf_counts_pack)
 #pragma unroll
-        for (int q = 0; q < kWaves; ++q) { n1 += __builtin_amdgcn_readlane(c1, q); n2 += __builtin_amdgcn_readlane(c2, q); }
+            for (int q = 0; q < kWaves; ++q) sum += (uint32_t)__builtin_amdgcn_readlane(c1, q);
+            n1 = mcf_counts_first(sum); n2 = mcf_counts_second(sum);
+        } else {
+#pragma unroll
+            for (int q = 0; q < kWaves; ++q) { n1 += __builtin_amdgcn_readlane(c1, q); n2 += __builtin_amdgcn_readlane(c2, q); }
+        }
         // the ratio tests, exactly the climb's: first side -- strictly smaller wins (lowest index among equals), second side --
         // smaller or equal wins (highest index among equals)
         bool both = false;
-        if (kRatioTogether) {
+        if constexpr (kBallot) {
+            // the same tests on the loaded words: a lane is IN its side, its residual FINITE, or WIDE -- r = in ? q : MCF_INF is never
+            // formed; each ballot is of one compare, and the lane masks are joined in scalar registers
+            const bool in1 = lane < n1, in2 = lane < n2, f1 = q1 != MCF_INF, f2 = q2 != MCF_INF;
+            uint32_t key1 = (in1 && f1) ? (uint32_t)q1 : 0xffffffffu, key2 = (in2 && f2) ? (uint32_t)q2 : 0xffffffffu;   // (mcf_ratio_key32)
+            asm volatile("" : "+v"(key1), "+v"(key2));
+            const uint64_t m1 = __builtin_amdgcn_ballot_w64(in1), m2 = __builtin_amdgcn_ballot_w64(in2);
+            const uint64_t odd = (m1 & __builtin_amdgcn_ballot_w64(f1) & __builtin_amdgcn_ballot_w64((uint64_t)q1 > 0xfffffffeull)) |
+                                 (m2 & __builtin_amdgcn_ballot_w64(f2) & __builtin_amdgcn_ballot_w64((uint64_t)q2 > 0xfffffffeull));
+            both = n1 <= 64 && n2 <= 64 && odd == 0;
+            if (both) {
+                uint32_t mn1, mn2;
+                mcf_wave_min_u32_pair(key1, key2, mn1, mn2);
+                const uint64_t mask1 = m1 & __builtin_amdgcn_ballot_w64(key1 == mn1), mask2 = m2 & __builtin_amdgcn_ballot_w64(key2 == mn2);
+                d1 = MCF_INF; k1 = -1; d2 = MCF_INF; k2 = -1;
+                if (n1 > 0) mcf_ratio_take<false>(mcf_ratio_unkey32(mn1), mask1, 0, d1, k1);
+                if (n2 > 0) mcf_ratio_take<true>(mcf_ratio_unkey32(mn2), mask2, 0, d2, k2);
+            }
+        } else if (kRatioTogether) {
             const int64_t r1 = lane < n1 ? q1 : MCF_INF, r2 = lane < n2 ? q2 : MCF_INF;
             // ONE uniform test: both sides fit one stride and are narrow.  Then the two 32-bit reductions are straight-line code
             // with nothing between them, and their DPP steps interleave.
@@ -2275,16 +2361,33 @@ template <int THREADS, bool FRONT> __device__ __forceinline__ void small_apply(c
     if (!cx.apply) return;
     constexpr bool kCatchUpBeside = small_catch_up_beside(THREADS, FRONT);
     const int32_t lo = cx.lo, hi = cx.hi, plo = cx.prev_lo, phi = cx.prev_hi;
-    const McfNode* const srec = cx.pv_result == 1 ? v.rec1 : v.rec2;
-    const int32_t* const spos = cx.pv_result == 1 ? v.ppos1 : v.ppos2;
     const int32_t jc = plo + (int32_t)threadIdx.x;   // the catch-up's first trip
     const bool catch0 = kCatchUpBeside && jc < phi && (jc < lo || jc >= hi);
     int32_t ndc = 0;
-    if (catch0) ndc = (cx.cur ? v.order[1] : v.order[0])[jc];
-    for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one_paths(v, cx, srec, spos, j);
-    if (catch0) mcf_apply_catch_up_store(v, cx, jc, ndc);
-    for (int32_t j = jc + (kCatchUpBeside ? THREADS : 0); j < phi; j += THREADS)
-        if (j < lo || j >= hi) mcf_apply_one_paths(v, cx, srec, spos, j);
+    if constexpr (small_pair_arith(THREADS, FRONT)) {
+        // the leaving side and the two buffers as numbers -- a swap's pv_result is 1 or 2, cur is 0 or 1 -- times the pairs'
+        // distances, where five base addresses were selected (mcf_apply_one_paths_at: the same pass on addresses named here)
+        const int32_t d4 = mcf_pair_dist4(v.n_nodes), d16 = mcf_pair_dist16(v.n_nodes);
+        const int32_t sbit = cx.pv_result - 1, nbit = cx.cur ^ 1;
+        const McfNode* const srec = v.rec1 + mcf_pair_index(0, sbit, d16);
+        const int32_t* const spos = v.ppos1 + mcf_pair_index(0, sbit, d4);
+        const int32_t* const src = v.order[0] + mcf_pair_index(0, cx.cur, d4);
+        int32_t* const dst = v.order[0] + mcf_pair_index(0, nbit, d4);
+        int32_t* const pnext = v.posbuf[0] + mcf_pair_index(0, nbit, d4);
+        if (catch0) ndc = src[jc];
+        for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one_paths_at(v, cx, srec, spos, src, dst, pnext, j);
+        if (catch0) mcf_apply_catch_up_store_at(dst, pnext, jc, ndc);
+        for (int32_t j = jc + (kCatchUpBeside ? THREADS : 0); j < phi; j += THREADS)
+            if (j < lo || j >= hi) mcf_apply_one_paths_at(v, cx, srec, spos, src, dst, pnext, j);
+    } else {
+        const McfNode* const srec = cx.pv_result == 1 ? v.rec1 : v.rec2;
+        const int32_t* const spos = cx.pv_result == 1 ? v.ppos1 : v.ppos2;
+        if (catch0) ndc = (cx.cur ? v.order[1] : v.order[0])[jc];
+        for (int32_t j = lo + threadIdx.x; j < hi; j += THREADS) mcf_apply_one_paths(v, cx, srec, spos, j);
+        if (catch0) mcf_apply_catch_up_store(v, cx, jc, ndc);
+        for (int32_t j = jc + (kCatchUpBeside ? THREADS : 0); j < phi; j += THREADS)
+            if (j < lo || j >= hi) mcf_apply_one_paths(v, cx, srec, spos, j);
+    }
 }
 
 // ---- at the budget: is any arc still eligible?  (simplex.py:1678-1699; saves the host a pricing pass + three syncs)
@@ -2426,6 +2529,7 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
     constexpr bool kDescOnce = small_desc_once(THREADS, FRONT);
     constexpr bool kDecideFlat = small_decide_flat(THREADS, FRONT);
     constexpr bool kPriceFlat = small_price_flat(THREADS, FRONT);
+    constexpr bool kPairs = small_pair_arith(THREADS, FRONT);
     constexpr int kPriceChains = small_price_chains(THREADS, FRONT);
     constexpr bool hand = FRONT;
     const int32_t* const pi32 = reinterpret_cast<const int32_t*>(v.pi);   // low words of the potentials
@@ -2621,9 +2725,10 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         // (end points that hang close to the root -- the first pivots of a cold start -- are climbed: a level or two of
         //  LDS round trips beat the parallel search's fixed cost: 144 K vs 126 K pivots/s over the first 25 pivots)
         if (v.n_nodes <= kSmallCycleMaxNodes && deep > 3) {
-            small_cycle_parallel<THREADS>(v, s_acc, scratch, cy);   // (one barrier inside)
+            small_cycle_parallel<THREADS, FRONT>(v, s_acc, scratch, cy);   // (one barrier inside)
             MCF_PSTAMP(15);
-            if constexpr (kDecideFlat) mcf_pivot_decide_flat(v, mcf_view_paths(v), cy);
+            if constexpr (kDecideFlat && kPairs) mcf_pivot_decide_flat_t<true>(v, mcf_view_paths(v), cy, mcf_pair_dist4(v.n_nodes), mcf_pair_dist16(v.n_nodes));
+            else if constexpr (kDecideFlat) mcf_pivot_decide_flat(v, mcf_view_paths(v), cy);
             else mcf_pivot_decide(v, mcf_view_paths(v), cy);
         } else {
             if (threadIdx.x < 2) {
@@ -2650,7 +2755,8 @@ __device__ __forceinline__ void solve_small_body(const McfView& g, const SmallLa
         // lo + THREADS - 64 on, which most pivots do not have.  See THE RULE above for why the two never meet.
         if ((int32_t)threadIdx.x >= THREADS - 64) {
             MCF_LAST_WAVE_BEGIN();
-            mcf_pivot_finish_t<true>(v, mcf_view_paths(v), (int32_t)threadIdx.x - (THREADS - 64), 64);
+            if constexpr (kPairs) mcf_pivot_finish_pairs<small_finish_one_trip(THREADS, FRONT)>(v, mcf_view_paths(v), mcf_pair_dist4(v.n_nodes), mcf_pair_dist16(v.n_nodes), (int32_t)threadIdx.x - (THREADS - 64), 64);
+            else mcf_pivot_finish_t<true>(v, mcf_view_paths(v), (int32_t)threadIdx.x - (THREADS - 64), 64);
             MCF_LAST_WAVE_STAMP();
             MCF_WAVE_STAMP(4);
         }
@@ -3383,29 +3489,10 @@ void free_all(mcf_handle* h) {
     if (h->stream && h->stream_owned) (void)hipStreamDestroy(h->stream);
 }
 
-// LDS plan of the fused small-instance path (every offset a multiple of 16) for an instance of m_pad padded arcs; false when
-// it does not fit the LDS capacity of k_solve_small
+// LDS plan of the fused small-instance path: mcf_small_plan (mcf_core.h), which also checks what the 256-lane front kernel's
+// pair arithmetic and packed counts rest on
 bool small_plan(int64_t m_pad, size_t arcw_count, int32_t n_nodes, bool devex, SmallLayout* out) {
-    SmallLayout L;
-    uint32_t off = 0;
-    auto take = [&](uint64_t bytes) { const uint32_t o = off; off += (uint32_t)((bytes + 15) / 16 * 16); return o; };
-    const uint64_t mp = (uint64_t)m_pad, Nn = (uint64_t)n_nodes;
-    const uint64_t need = mp * 21 + (uint64_t)arcw_count * 16 + Nn * 112 + 4096;
-    if (need >= 150 * 1024) return false;   // (before the offsets are formed: they are 32-bit)
-    L.tail = take(mp * 4); L.head = take(mp * 4); L.cost = take(mp * 4); L.orig = take(mp * 4);
-    L.state = take(mp); L.weight = take(devex ? mp * 4 : 0);
-    L.arcw = take((uint64_t)arcw_count * 16); L.pi = take(Nn * 8); L.node = take(Nn * 16);
-    L.order0 = take(Nn * 4); L.order1 = take(Nn * 4); L.pos0 = take(Nn * 4); L.pos1 = take(Nn * 4);
-    L.path1 = take(Nn * 4); L.path2 = take(Nn * 4); L.ppos1 = take(Nn * 4); L.ppos2 = take(Nn * 4);
-    L.rec1 = take(Nn * 16); L.rec2 = take(Nn * 16);
-    L.seg = take((2 * Nn + 2) * sizeof(McfSeg));
-    // scratch of the node-parallel cycle search (two residuals and one by-depth entry per tree node); a larger tree is climbed
-    L.scratch = take(n_nodes <= kSmallCycleMaxNodes ? Nn * 20 : 0);
-    L.ctx = take(sizeof(McfCtx));
-    L.total = off;
-    if (L.total > kSmallMaxLds) return false;
-    *out = L;
-    return true;
+    return mcf_small_plan(m_pad, (uint64_t)arcw_count, n_nodes, devex, out);
 }
 
 // Width of the fused loop's workgroup, from the measured table in DESIGN.md (k_solve_small).  One wave per SIMD (256 lanes)
